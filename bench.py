@@ -2,7 +2,7 @@
 """Headline benchmark: Newton-Raphson iterations/s of the harmonic power flow on the synthetic 1 000-bus x
 25-harmonic radial feeder (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 Workload (per GPU, fixed as N grows -> weak scaling): `--scenarios` Monte-Carlo load scenarios (default 128 =
@@ -13,9 +13,16 @@ round-robin over ranks (rank + world*i).  Setup — CSV ingest, admittance build
 A *step* is one full NR iteration of every scenario on the GPU: Jacobian assembly + block-tree elimination +
 back-substitution, state update, mismatch + inf-norm (HG:537-540).  The W+K timed steps are the first W+K iterations
 of the real solves from the reference's start point (no scenario has converged yet: the reference needs 27), run
-with `hpf_iterate`, i.e. without host synchronisation.  value = scenarios_total * K / t  [NR iterations / s].
+with `hpf_iterate`, i.e. without host synchronisation.  value = scenarios_total * K / t  [NR iterations / s];
+ms_per_step = 1e3 * t / K.  A plain run times ONE block of exactly K steps and prints the headline line (rank 0, one JSON line).
 
-Untimed legs after the timed region (rank 0 prints ONE JSON line with all of them):
+--dump-outputs DIR: after the timed steps, the arrays a caller of the timed path receives -- the state hpf_get_state returns
+(Vm.npy, Va.npy: [scenarios][Hn * n], stacked order) and the inf-norm of the mismatch at that state (err.npy: [scenarios]) -- as
+float64, at most 64 MB in all (beyond that a fixed, seeded sample of scenarios and entries; ranks > 0 add a _rank<r> suffix).  The
+inputs are a function of the arguments alone (gen seed 0, seeded scenario loads), so two builds can be compared file for file.
+
+--full: the timed region as `--repeats` (default 5) blocks with the median reported, then the untimed legs below (rank 0 prints
+ONE JSON line with all of them):
   roofline        the dominant kernel ALONE -- k_level<52>, the factor sweep of the block tree, one launch per elimination level
                   (Gauss-Jordan workgroups + the level's scenario-batched workgroups in one grid; k_factor_q<B,false> for other
                   block sizes): device-clock span of every one of its launches over K more steps against its own algorithmic
@@ -54,6 +61,9 @@ def parse(argv=None):
     ap.add_argument("--buses", type=int, default=1000)
     ap.add_argument("--hmax", type=int, default=51)
     ap.add_argument("--solver", default="block_tree", choices=["block_tree", "dense"])
+    ap.add_argument("--full", action="store_true", help="also the untimed legs (roofline, kernel timing, sweeps, single scenario, meshed "
+                                                       "feeders, CPU baseline) and the repeated timed blocks; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step to DIR/<name>.npy")
     ap.add_argument("--cpu-iters", type=int, default=12, help="NR iterations of the CPU baseline sample (0 = skip)")
     ap.add_argument("--cpu-workers", type=int, default=0, help="worker processes of the all-cores CPU leg (0 = host cores, at most 16)")
     ap.add_argument("--no-finish", action="store_true", help="skip the untimed solve-to-convergence + stats gather")
@@ -62,9 +72,13 @@ def parse(argv=None):
     ap.add_argument("--sweep-1gpu", type=int, default=1024, help="(N = 1) scenarios of the single-GPU sweep leg (0 = skip)")
     ap.add_argument("--single", action="store_true", help="(default on rank 0 at N=1) also time a single-scenario solve: BASELINE config 3")
     ap.add_argument("--no-single", action="store_true", help="skip the single-scenario latency leg")
-    ap.add_argument("--repeats", type=int, default=5, help="the timed block of `steps` iterations is run this many times (each from the pf "
-                                                           "seed, each bracketed by barrier + synchronize); value = the median block")
-    return ap.parse_args(argv)
+    ap.add_argument("--repeats", type=int, default=None, help="the timed block of `steps` iterations is run this many times (each from the pf "
+                                                              "seed, each bracketed by barrier + synchronize); value = the median block "
+                                                              "(default 5 with --full, else 1)")
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def launch_plan(args, env):
@@ -164,7 +178,7 @@ def main():
     if world != args.gpus:
         raise SystemExit("bench.py: --gpus %d but WORLD_SIZE=%d (one rank per GPU: start it as `python bench.py --gpus N` or under "
                          "torch.distributed.run with --nproc-per-node N)" % (args.gpus, world))
-    cpu = cpu_baseline_start(args) if (rank == 0 and world == 1) else None      # N = 1 only (the other ranks of a larger job would wait for it); child processes, before any GPU initialisation
+    cpu = cpu_baseline_start(args) if (args.full and rank == 0 and world == 1) else None      # N = 1 only (the other ranks of a larger job would wait for it); child processes, before any GPU initialisation
     import torch
     import torch.distributed as dist
     if not torch.cuda.is_available():
@@ -254,46 +268,14 @@ def main():
         blocks.append(el)
     elapsed = float(np.median(blocks))
     median_block = int(np.argsort(blocks)[len(blocks) // 2])
-    # per-kernel HIP-event timing (on the streams the kernels run on) over K more steps of the same configuration, continued
-    # from the state the timed region left; kept out of the headline region because every span costs two event records
-    Kt = min(args.steps, 20)                     # steps of each timing leg (bounded: every span is a pair of event records)
-    dm.timing(True)
-    dm.timing_reset()
-    dm.iterate(Kt)
-    dm.sync()
-    tim = dm.timing_get()
-    dm.timing(False)
-    # ... and the dominant kernel's own duration on the device clock over K more steps WITHOUT event packets between the kernels
-    # (a HIP event record is a barrier packet with cache maintenance: it perturbs the ~25 us kernels it brackets)
-    dm.timing(2)
-    dm.timing_reset()
-    dm.iterate(Kt)
-    dm.sync()
-    tim["gj_dev"] = dm.timing_get()["gj_dev"]
-    dm.timing(False)
-    # ... and the same kernel with the chip to itself: the scenarios as ONE group (one launch per level, no other stream busy), K more steps
-    tim["gj_dev_one_group"] = None
-    if args.solver == "block_tree" and dm.scenario_groups(S) > 1 and not args.no_one_group:
-        g_now = dm.scenario_groups(S)
-        dm.set_option("scenario_groups", 1)
-        dm.iterate(2)
-        dm.timing(2)
-        dm.timing_reset()
-        dm.iterate(Kt)
-        dm.sync()
-        tim["gj_dev_one_group"] = dm.timing_get()["gj_dev"]
-        dm.timing(False)
-        dm.timing(True)                              # (HIP-event spans: the mismatch kernel of the one-group configuration)
-        dm.timing_reset()
-        dm.iterate(Kt)
-        dm.sync()
-        tim["mismatch_one_group"] = dm.timing_get()["mismatch"]
-        dm.timing(False)
-        dm.set_option("scenario_groups", g_now)
+    if args.dump_outputs:
+        dump_outputs(dm, args.dump_outputs, rank, world)
+    if args.full:
+        Kt, tim = kernel_timing(dm, args, S)
 
     # ---- untimed: finish the solves with the reference's stop rule, gather convergence statistics (RCCL) ----------
     sweep = None
-    if not args.no_finish:
+    if args.full and not args.no_finish:
         dm.set_state(seed[0], seed[1])
         dm.solve(inp["st"].thresh_h, inp["st"].max_iter_h)                   # warm (pinned buffers, repeat-pass state)
         dm.set_state(seed[0], seed[1])
@@ -322,8 +304,37 @@ def main():
     total_scen = S * world
     value = total_scen * K / elapsed
     ms_step = 1e3 * elapsed / K
-    b = 2 * Hn
     bt = args.solver == "block_tree"
+    out = {
+        "metric": "NR iterations/sec + ms/iter, 1 000-bus x 25-harmonic feeder; |dV| vs reference",
+        "value": value, "unit": "NR iterations/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
+        "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "syn%d radial feeder (gen seed 0), harmonics 1..%d odd (K=%d), coupled Norton (smps), "
+                               "%d Monte-Carlo load scenarios per GPU (%d total), block-tree Newton step"
+                               % (n, args.hmax, Hn - 1, S, total_scen) if bt else
+                               "syn%d, K=%d, coupled, %d scenarios per GPU, dense rocSOLVER" % (n, Hn - 1, S),
+                   "buses": n, "harmonics": Hn - 1, "unknowns_per_scenario": dm.N, "scenarios_per_gpu": S,
+                   "solver": dm.solver, "step": "one NR iteration of every scenario (HG:537-540)",
+                   "pf_iterations": int(nf.max())},
+        "repeats": len(blocks), "repeat_ms_per_step": [1e3 * b / K for b in blocks],
+        "repeat_note": "R timed blocks of exactly `steps` iterations, each from the pf seed after `warmup` iterations, each bracketed by "
+                       "barrier + synchronize and MAX-reduced over the ranks; ms_per_step / value are the MEDIAN block's",
+        "scenario_groups_probe": groups_probe,      # untimed: four groups (default) against three in this process; the default stays unless > 10 % slower
+        # build switches of the handle: none in a product run; under HPF_ENV_SWITCHES=1 (tools/) the HPF_* names found in the environment
+        "env_switches": (sorted(k for k in os.environ if k.startswith("HPF_") and k not in ("HPF_ENV_SWITCHES", "HPF_BENCH_BACKEND", "HPF_LIB_PATH"))
+                         if os.environ.get("HPF_ENV_SWITCHES", "0") not in ("", "0") else []),
+        "backend": backend if world > 1 else None,
+        "rccl_ranks": rccl_ranks,
+        "ms_per_step_ranks": [1e3 * t / K for t in blocks_ranks[median_block]],   # each rank's own time of the median block (value uses their MAX)
+        "scenario_ids_rank0": [int(scen_ids[0]), int(scen_ids[1]) if S > 1 else None, "... + %d" % world],
+        "ms_per_iter_per_scenario": ms_step / S,
+        "setup_ms": setup["model_setup_ms"], "setup": setup,
+    }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
+    b = 2 * Hn
     G = dm.scenario_groups(S) if bt else 1
     # ---- roofline of the dominant kernel, alone: k_factor_q<B,false> (block_tree) / the rocSOLVER LU (dense) ----------------------
     gj_ms, gj_n = tim["gj_dev"] if (bt and tim.get("gj_dev", (0, 0))[1]) else (tim["gj"] if bt else tim["solve"])
@@ -374,31 +385,7 @@ def main():
                  "Gauss-Jordan workgroups (one per bus and scenario: %d buses) and the scenario-batched workgroups of the constant-inverse "
                  "leaves (%d) and bordered buses (%d) of the level in one grid" % (ln_gj, census["gauss_jordan"], census["const_leaves"],
                                                                                   census["bordered"]))
-    out = {
-        "metric": "NR iterations/sec + ms/iter, 1 000-bus x 25-harmonic feeder; |dV| vs reference",
-        "value": value, "unit": "NR iterations/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
-        "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "syn%d radial feeder (gen seed 0), harmonics 1..%d odd (K=%d), coupled Norton (smps), "
-                               "%d Monte-Carlo load scenarios per GPU (%d total), block-tree Newton step"
-                               % (n, args.hmax, Hn - 1, S, total_scen) if bt else
-                               "syn%d, K=%d, coupled, %d scenarios per GPU, dense rocSOLVER" % (n, Hn - 1, S),
-                   "buses": n, "harmonics": Hn - 1, "unknowns_per_scenario": dm.N, "scenarios_per_gpu": S,
-                   "solver": dm.solver, "step": "one NR iteration of every scenario (HG:537-540)",
-                   "pf_iterations": int(nf.max())},
-        "repeats": len(blocks), "repeat_ms_per_step": [1e3 * b / K for b in blocks],
-        "repeat_note": "R timed blocks of exactly `steps` iterations, each from the pf seed after `warmup` iterations, each bracketed by "
-                       "barrier + synchronize and MAX-reduced over the ranks; ms_per_step / value are the MEDIAN block's",
-        "scenario_groups_probe": groups_probe,      # untimed: four groups (default) against three in this process; the default stays unless > 10 % slower
-        # build switches of the handle: none in a product run; under HPF_ENV_SWITCHES=1 (tools/) the HPF_* names found in the environment
-        "env_switches": (sorted(k for k in os.environ if k.startswith("HPF_") and k not in ("HPF_ENV_SWITCHES", "HPF_BENCH_BACKEND", "HPF_LIB_PATH"))
-                         if os.environ.get("HPF_ENV_SWITCHES", "0") not in ("", "0") else []),
-        "backend": backend if world > 1 else None,
-        "rccl_ranks": rccl_ranks,
-        "ms_per_step_ranks": [1e3 * t / K for t in blocks_ranks[median_block]],   # each rank's own time of the median block (value uses their MAX)
-        "scenario_ids_rank0": [int(scen_ids[0]), int(scen_ids[1]) if S > 1 else None, "... + %d" % world],
-        "ms_per_iter_per_scenario": ms_step / S,
-        "setup_ms": setup["model_setup_ms"], "setup": setup,
+    out.update({
         "roofline": {"bound": "hbm",
                      "kernel": kdesc, "tree_census": census,
                      "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -453,7 +440,7 @@ def main():
         "vs_reference_single_run_note": "not a like-for-like ratio and not reported as a number: the reference (one single-threaded pandas / SuperLU "
                                         "process, ONE scenario) measured 38.9 s per NR iteration on this feeder in the build container; `value` is "
                                         "the aggregate of %d scenarios in flight per GPU.  cpu_baseline is the comparator timed on this box." % S,
-    }
+    })
     if sweep is not None:
         out["sweep"] = sweep
         out["sweep_iters_per_s"] = sweep["iters_per_s_rank0"] * world
@@ -490,6 +477,72 @@ def main():
         out["meshed"] = meshed_feeder(hp, args)
     out["cpu_baseline"] = cpu
     print(json.dumps(out), flush=True)
+
+
+def kernel_timing(dm, args, S):
+    """Per-kernel timing legs (--full), continued from the state the timed region left -> (Kt, {phase: (ms, launches)})."""
+    # per-kernel HIP-event timing (on the streams the kernels run on) over K more steps of the same configuration; kept out of the
+    # headline region because every span costs two event records
+    Kt = min(args.steps, 20)                     # steps of each timing leg (bounded: every span is a pair of event records)
+    dm.timing(True)
+    dm.timing_reset()
+    dm.iterate(Kt)
+    dm.sync()
+    tim = dm.timing_get()
+    dm.timing(False)
+    # ... and the dominant kernel's own duration on the device clock over K more steps WITHOUT event packets between the kernels
+    # (a HIP event record is a barrier packet with cache maintenance: it perturbs the ~25 us kernels it brackets)
+    dm.timing(2)
+    dm.timing_reset()
+    dm.iterate(Kt)
+    dm.sync()
+    tim["gj_dev"] = dm.timing_get()["gj_dev"]
+    dm.timing(False)
+    # ... and the same kernel with the chip to itself: the scenarios as ONE group (one launch per level, no other stream busy), K more steps
+    tim["gj_dev_one_group"] = None
+    if args.solver == "block_tree" and dm.scenario_groups(S) > 1 and not args.no_one_group:
+        g_now = dm.scenario_groups(S)
+        dm.set_option("scenario_groups", 1)
+        dm.iterate(2)
+        dm.timing(2)
+        dm.timing_reset()
+        dm.iterate(Kt)
+        dm.sync()
+        tim["gj_dev_one_group"] = dm.timing_get()["gj_dev"]
+        dm.timing(False)
+        dm.timing(True)                              # (HIP-event spans: the mismatch kernel of the one-group configuration)
+        dm.timing_reset()
+        dm.iterate(Kt)
+        dm.sync()
+        tim["mismatch_one_group"] = dm.timing_get()["mismatch"]
+        dm.timing(False)
+        dm.set_option("scenario_groups", g_now)
+    return Kt, tim
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(dm, out_dir, rank, world):
+    """What a caller of the timed path (hpf_iterate) receives after its last step: the voltages of every scenario (hpf_get_state) and the
+    inf-norm of the mismatch at them, as float64 .npy files.  Larger than DUMP_BYTES_MAX / world per rank: a fixed, seeded sample of
+    scenarios (rows) and, if one row is still too large, of entries (columns)."""
+    dm.sync()
+    Vm, Va = dm.get_state()
+    _, err = dm.mismatch(want_f=False)
+    cap = DUMP_BYTES_MAX // world
+    rng = np.random.default_rng(0)
+    row_bytes = 2 * 8 * Vm.shape[1]
+    rows = np.arange(Vm.shape[0])
+    if len(rows) * (row_bytes + 8) > cap:
+        rows = np.sort(rng.choice(len(rows), max(1, cap // (row_bytes + 8)), replace=False))
+    cols = np.arange(Vm.shape[1])
+    if len(rows) * (row_bytes + 8) > cap:
+        cols = np.sort(rng.choice(len(cols), max(1, (cap - 8) // 16), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "_rank%d" % rank if rank else ""
+    for name, a in (("Vm", Vm[np.ix_(rows, cols)]), ("Va", Va[np.ix_(rows, cols)]), ("err", err[rows])):
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def lib_sha16():

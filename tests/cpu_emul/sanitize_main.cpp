@@ -68,7 +68,10 @@ static Feeder make(int n, int Hn, int n_pv, double frac_nl, int coupled, unsigne
     return F;
 }
 
-int main() {
+// argv[1]: where the planner's dump goes (WITH_LIBHPF; the test passes a file of its own temporary directory)
+int main(int argc, char** argv) {
+    const char* plan_path = argc > 1 ? argv[1] : "hpf_sanitize_plan.txt";
+    (void)plan_path;
     int checked = 0;
     for (unsigned seed = 1; seed <= 12; ++seed) {
         const int n = 5 + (int)(seed * 7 % 40), Hn = 2 + (int)(seed % 6), coupled = seed & 1, n_pv = seed % 3;
@@ -211,13 +214,13 @@ int main() {
         d.max_scenarios = t < 4 ? 8 : 512;
         d.rowptr = F.rowptr.data(); d.col = F.col.data(); d.Yval = (const double*)F.Y.data(); d.dev_of_bus = F.dev.data();
         d.Y_N = (const double*)F.YN.data(); d.I_N = (const double*)F.IN.data();
-        const int rc = hpf_tree_plan(&d, "/tmp/hpf_sanitize_plan.txt");
+        const int rc = hpf_tree_plan(&d, plan_path);
         if (rc != HPF_OK) {
             printf("hpf_tree_plan failed: %d (n %d Hn %d, %d ties)\n", rc, n, Hn, ties);
             return 3;
         }
         if (ties) {                                            // every marked bus must have come out as a plain Gauss-Jordan bus (last column 1, never -1)
-            FILE* fp = fopen("/tmp/hpf_sanitize_plan.txt", "r");
+            FILE* fp = fopen(plan_path, "r");
             char line[512];
             int marked = 0, bad = 0, meshed_line = 0;
             while (fp && fgets(line, sizeof line, fp)) {

@@ -17,7 +17,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLD, INPUTS
+from conftest import GOLD, INPUTS, REPO
 
 pytestmark = pytest.mark.gpu
 TOL_V = 1e-8
@@ -283,3 +283,42 @@ def test_queue_reports_flagged_scenarios_and_the_sweep_resolves_them_with_pivoti
             dm1.close()
         assert it1[0] == rec["n_iter"][s] and err1[0] == rec["err"][s]
         assert np.array_equal(Vm1[0], Vq[s]) and np.array_equal(Va1[0], Aq[s])
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_the_state_of_the_last_one(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (a fresh process): ONE timed block of K steps, the headline keys only, and
+    DIR/{Vm,Va,err}.npy = the state after W + K Newton iterations from the pf seed, bit for bit what the same iterations give in a handle here."""
+    import json
+    import subprocess
+    import sys
+    from harmonic_power_flow_amd import api, synth
+    n, hmax, S, K, W = 200, 11, 4, 3, 2
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--buses", str(n),
+                        "--hmax", str(hmax), "--scenarios", str(S), "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    j = json.loads(r.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j, k
+    assert j["steps"] == K and j["repeats"] == 1 and len(j["repeat_ms_per_step"]) == 1 and j["ms_per_step"] > 0
+    assert abs(j["value"] - S * K / (j["ms_per_step"] * K * 1e-3)) <= 1e-9 * j["value"]
+    assert "roofline" not in j and "cpu_baseline" not in j and "sweep" not in j
+    hp = _hp()
+    st, buses, Y, NE = _feeder(hp, n, hmax, tmp_path)
+    P0, Q0 = buses["P"].to_numpy(float), buses["Q"].to_numpy(float)
+    scale = np.stack([synth.scenario_scale(n, s) for s in range(S)])
+    dm = api._device_model(buses, Y, NE, True, st.HARMONICS, solver="block_tree", max_scenarios=S)
+    try:
+        dm.set_loads(P0 * scale, Q0 * scale)
+        dm.set_state(None, None, n_scen=S)
+        dm.fund_pf(st.thresh_f, st.max_iter_f)
+        dm.mismatch(want_f=False)
+        dm.iterate(W + K)
+        dm.sync()
+        Vm, Va = dm.get_state()
+        _, err = dm.mismatch(want_f=False)
+    finally:
+        dm.close()
+    for name, ref in (("Vm", Vm), ("Va", Va), ("err", err)):
+        a = np.load(out / (name + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, ref), name

@@ -114,7 +114,54 @@ def test_bench_gpus_flag_starts_one_rank_per_gpu(monkeypatch):
     assert cmd[-6:] == ["--gpus", "4", "--steps", "7", "--warmup", "2"] and cmd[-7].endswith("bench.py")
     assert bench.launch_plan(args, {"WORLD_SIZE": "4", "RANK": "0"}) is None           # already a rank
     assert bench.launch_plan(bench.parse(["--gpus", "1"]), {}) is None
-    assert bench.parse([]).gpus == 1 and bench.parse([]).repeats >= 5
+    assert bench.parse([]).gpus == 1 and bench.parse([]).repeats == 1 and not bench.parse([]).full   # a plain run times ONE block of --steps
+    assert bench.parse(["--full"]).repeats >= 5 and bench.parse(["--full", "--repeats", "3"]).repeats == 3
+
+
+def test_bench_dump_outputs_writes_the_state_of_the_last_step_within_64_mb(tmp_path, monkeypatch):
+    """--dump-outputs DIR: Vm, Va [scenarios][Hn*n] (hpf_get_state) and err [scenarios] as float64 .npy; beyond 64 MB a fixed, seeded sample
+    of scenarios (and of entries when one scenario alone is too large), the same from run to run."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class FakeModel:
+        def __init__(self, S, W):
+            r = np.random.default_rng(5)
+            self.Vm, self.Va, self.err = r.random((S, W)), r.random((S, W)), r.random(S)
+
+        def sync(self):
+            pass
+
+        def get_state(self):
+            return self.Vm.copy(), self.Va.copy()
+
+        def mismatch(self, want_f=True):
+            return None, self.err.copy()
+
+    dm = FakeModel(6, 40)
+    bench.dump_outputs(dm, str(tmp_path / "small"), 0, 1)
+    for name, ref in (("Vm", dm.Vm), ("Va", dm.Va), ("err", dm.err)):
+        a = np.load(tmp_path / "small" / (name + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, ref)
+    bench.dump_outputs(dm, str(tmp_path / "rank1"), 1, 2)
+    assert sorted(os.listdir(tmp_path / "rank1")) == ["Va_rank1.npy", "Vm_rank1.npy", "err_rank1.npy"]
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 2000)                     # 3 of the 6 scenarios fit (16 B per entry + 8 B of err each)
+    for d in ("a", "b"):
+        bench.dump_outputs(dm, str(tmp_path / d), 0, 1)
+    sizes = 0
+    for name in ("Vm", "Va", "err"):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert np.array_equal(a, b) and a.shape[0] == 3
+        sizes += a.nbytes
+    assert sizes <= 2000
+    rows = [int(np.nonzero((dm.err == e))[0][0]) for e in np.load(tmp_path / "a" / "err.npy")]
+    assert np.array_equal(np.load(tmp_path / "a" / "Vm.npy"), dm.Vm[rows])
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 400)                      # not even one scenario fits: entries of one scenario
+    bench.dump_outputs(dm, str(tmp_path / "c"), 0, 1)
+    vm, va, err = (np.load(tmp_path / "c" / (n + ".npy")) for n in ("Vm", "Va", "err"))
+    assert vm.shape[0] == 1 and 0 < vm.shape[1] < 40 and vm.nbytes + va.nbytes + err.nbytes <= 400
 
 
 def test_get_THD_equals_the_reference_to_the_last_bit():

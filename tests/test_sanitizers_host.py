@@ -31,7 +31,7 @@ def test_device_arithmetic_on_host_under_asan_ubsan():
     assert "12 cases clean" in r.stdout
 
 
-def test_host_side_of_libhpf_under_asan_ubsan():
+def test_host_side_of_libhpf_under_asan_ubsan(tmp_path):
     hipcc, clang = "/opt/rocm/bin/hipcc", "/opt/rocm/lib/llvm/bin/clang++"
     if not (os.path.exists(hipcc) and os.path.exists(clang)):
         pytest.skip("ROCm toolchain not present")
@@ -46,6 +46,6 @@ def test_host_side_of_libhpf_under_asan_ubsan():
     if not _newer(exe, [SRC, lib]):
         subprocess.check_call([clang] + FLAGS + ["-DWITH_LIBHPF", "-I", CSRC, SRC, "-o", exe, lib, "-Wl,-rpath," + OUT, "-Wl,-rpath,/opt/rocm/lib"])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")      # (the HIP runtime's start-up allocations are not ours to free)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    r = subprocess.run([exe, str(tmp_path / "plan.txt")], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "20 cases clean" in r.stdout

@@ -5,7 +5,7 @@ export HPF_ENV_SWITCHES=1
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 TAG=${1:-c5}; shift
 WHAT=${@:-stats}
-ARGS="--buses 10000 --hmax 99 --steps 5 --warmup 2 --repeats 1 --cpu-iters 0 --no-finish --no-probe --no-single --sweep-1gpu 0"
+ARGS="--full --buses 10000 --hmax 99 --steps 5 --warmup 2 --repeats 1 --cpu-iters 0 --no-finish --no-probe --no-single --sweep-1gpu 0"
 export HPF_GROUPS=1
 for w in $WHAT; do
   case $w in

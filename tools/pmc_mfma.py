@@ -46,7 +46,7 @@ for d in ("pmc_SQ_VALU_MFMA_BUSY_CYCLES", "pmc_SQ_INSTS_VALU_MFMA_F64"):
         if d.endswith("BUSY_CYCLES") and key not in seen:
             seen.add(key)
             calls[k] += 1
-res = {"command": "rocprofv3 --pmc <counters> --kernel-trace --output-format csv -- python3 bench.py --steps 5 --warmup 2 --cpu-iters 0 "
+res = {"command": "rocprofv3 --pmc <counters> --kernel-trace --output-format csv -- python3 bench.py --full --steps 5 --warmup 2 --cpu-iters 0 "
                   "--no-finish --no-single --sweep-1gpu 0 (two passes; tools/measure.sh <tag> mfma)", "steps_profiled": steps, "kernels": {}}
 for k, c in sorted(agg.items(), key=lambda kv: -kv[1].get("SQ_BUSY_CYCLES", 0)):
     d = {n: v for n, v in c.items()}

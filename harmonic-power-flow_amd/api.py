@@ -367,6 +367,19 @@ def _dims_from_context(N):
     return (n, c, Hn) if rem == 0 and Hn >= 1 else None
 
 
+# update_harmonic_state_vec: the relative residual above which hpf_sparse_solve's result is not taken, and the largest dense N x N system
+# (bytes) it hands to the dense LU instead
+SPARSE_RESIDUAL_MAX = 1e-10
+DENSE_FALLBACK_BYTES = 16e9
+
+
+def _relative_residual(J, dx, f):
+    """|f - J dx|_inf / (| |J| |_inf |dx|_inf + |f|_inf) of a CSR matrix, in float64."""
+    r = np.abs(f - J @ dx).max() if f.size else 0.0
+    den = float(abs(J).sum(axis=1).max()) * np.abs(dx).max() + np.abs(f).max()
+    return float(r / den) if den > 0 else float(r)
+
+
 def update_harmonic_state_vec(J, x, f, device=0, dims=None):
     """HG:476-479: x - spsolve(J, f), the linear solve on the GPU.
 
@@ -375,9 +388,12 @@ def update_harmonic_state_vec(J, x, f, device=0, dims=None):
     1 000-bus x 26-harmonic Jacobian (N = 51 998, 1.2 M entries) is solved like the 46-unknown one.  The row / column numbering of the reference's
     stacked matrix is a function of (n, c, Hn): taken from `dims=(n, c, Hn)`, else from the matrix itself (the Jacobians this package returns
     carry it), else from the network of the last `init_network` call.  A meshed network's Jacobian (spanning tree + loop-closing lines) takes the
-    same route -- tree part factorised once, dense border system of the lines' endpoint buses.  Dense arrays, and sparse matrices the sparse route
+    same route -- tree part factorised once, dense border system of the lines' endpoint buses.  hpf_sparse_solve pivots only inside a bus block,
+    so its result is checked here: the relative residual |f - J dx|_inf / (| |J| |_inf |dx|_inf + |f|_inf) (float64, one host matvec) above
+    SPARSE_RESIDUAL_MAX, or a bus block without a pivot (HPF_E_SINGULAR), sends the system to the dense LU with partial pivoting over the whole
+    matrix -- where that fits DENSE_FALLBACK_BYTES, else a RuntimeError names the cause.  Dense arrays, and sparse matrices the sparse route
     refuses (bus graph not connected from bus 0, block pattern not symmetric, border beyond 16 384 unknowns), go to the dense rocSOLVER LU
-    (`hpf_dense_solve`), which is bounded by 8 N^2 bytes of host and device memory."""
+    (`hpf_dense_solve`), which is bounded by 8 N^2 bytes of host and device memory (DENSE_FALLBACK_BYTES)."""
     lib = _lib.load()
     fv = np.ascontiguousarray(f, dtype=np.float64)
     N = fv.size
@@ -397,11 +413,20 @@ def update_harmonic_state_vec(J, x, f, device=0, dims=None):
             ip = C.POINTER(C.c_int32)
             rc = lib.hpf_sparse_solve(int(device), int(d[0]), int(d[1]), int(d[2]), indptr.ctypes.data_as(ip), indices.ctypes.data_as(ip),
                                       data.ctypes.data_as(dp), fv.ctypes.data_as(dp), dx.ctypes.data_as(dp))
+            why = None
             if rc == 0:
-                return np.asarray(x, dtype=np.float64) - dx
-            if rc != -3:                                   # (HPF_E_TOPOLOGY: a pattern the sparse route does not take -> the dense LU below)
+                eta = _relative_residual(Jc, dx, fv)
+                if eta <= SPARSE_RESIDUAL_MAX:
+                    return np.asarray(x, dtype=np.float64) - dx
+                why = "its result has a relative residual of %.1e (> %.0e): a near-singular bus block" % (eta, SPARSE_RESIDUAL_MAX)
+            elif rc == 3:                                  # HPF_E_SINGULAR: a bus block (or the border system) without a pivot
+                why = "a bus block without a pivot (HPF_E_SINGULAR)"
+            elif rc != -3:                                 # (HPF_E_TOPOLOGY: a pattern the sparse route does not take -> the dense LU below)
                 raise RuntimeError("hpf_sparse_solve failed: %s (code %d)" % (lib.hpf_strerror(rc).decode(), rc))
-        if 8.0 * N * N > 16e9:
+            if why is not None and 8.0 * N * N > DENSE_FALLBACK_BYTES:
+                raise RuntimeError("update_harmonic_state_vec: hpf_sparse_solve met %s, and the dense LU that would solve it needs %.1f GB "
+                                   "(limit %.1f GB)" % (why, 8e-9 * N * N, 1e-9 * DENSE_FALLBACK_BYTES))
+        if 8.0 * N * N > DENSE_FALLBACK_BYTES:
             raise ValueError("update_harmonic_state_vec: a sparse Jacobian of %d unknowns %s; the dense fallback would need %.1f GB on the host -- "
                              "solve such a network with hpf() (bordered block-tree step)"
                              % (N, "that hpf_sparse_solve refuses (HPF_E_TOPOLOGY)" if d is not None else "whose (n, c, Hn) is unknown (pass dims=)", 8e-9 * N * N))

@@ -197,6 +197,9 @@ int  hpf_dense_solve(int device, int N, const double* J_colmajor, const double* 
  * + 20 lines: 27 ms, 1e-12 of the step from SuperLU).  HPF_E_TOPOLOGY when the bus graph is not connected from bus 0, the block pattern is not
  * symmetric (a block (i, j) without (j, i)) or the border exceeds that bound -- use hpf_dense_solve where it fits --, HPF_E_ARG for 2 Hn > 128 or an
  * inconsistent CSR, HPF_E_SINGULAR when a bus block or the border system has no pivot.  Stateless like the reference's function: no handle.
+ * Pivoting stays inside a bus block and only an EXACTLY zero pivot is reported: a near-singular bus block of a nonsingular J returns an
+ * inaccurate dx with HPF_OK, and an exactly singular one HPF_E_SINGULAR where a dense LU would succeed.  A C caller gets no residual check;
+ * check |f - J dx| itself and fall back to hpf_dense_solve (the Python update_harmonic_state_vec does both).
  * (env HPF_SPARSE_INFO=1 prints its phase times to stderr.) */
 int  hpf_sparse_solve(int device, int n, int c, int Hn, const int32_t* indptr, const int32_t* indices, const double* data, const double* f,
                       double* dx);

@@ -1,11 +1,12 @@
 """Build libhpf.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
+import glob
 import os
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["hpf_lib.hip", "hpf_block.hip", "hpf_csr_solve.hip"]
-HEADERS = ["hpf_assembly.hpp", "hpf_internal.hpp", "hpf_gj.hpp", "hpf_gj_mfma.hpp", "hpf_gj_dense.hpp", "hpf_quad.hpp", "hpf_lin2x2.hpp", "hpf_leafbatch.hpp", "hpf_tree_plan.hpp", os.path.join("..", "..", "include", "hpf.h")]
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(HERE, "..", "include", "hpf.h")]   # (every header: an edit rebuilds)
 OUT = os.path.join(HERE, "libhpf.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
@@ -14,7 +15,7 @@ def needs_build():
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS]
+    deps = [os.path.join(CSRC, f) for f in SOURCES] + HEADERS
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 

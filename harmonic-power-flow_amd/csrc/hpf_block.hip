@@ -698,13 +698,8 @@ template <int B>
 int launch_factor_w(hpf_handle* h, const TreeDev& T, const int* nodes, int count, const int* active) {
     ScopedTimer t(h, T_SOLVE);
     hipLaunchKernelGGL((k_factor_w<B>), dim3((unsigned)count, (unsigned)h->cur_S), dim3(64), 0, h->cur_stream, h->M, T, nodes,
-                       2 * h->Hn, h->N, h->Nc, active, h->d_U, h->d_E, h->d_f, h->d_Z, h->d_w, h->d_linA, h->d_pivflag, h->debug_ablate, h->cur_s0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        return HPF_E_HIP;
-    }
-    return HPF_OK;
+                       2 * h->Hn, h->N, h->Nc, active, h->d_U, h->d_E, h->d_f, h->d_Z, h->d_w, h->d_linA, h->d_pivflag, h->sw.debug_ablate, h->cur_s0);
+    return launch_status(h);
 }
 
 template <int B>
@@ -712,12 +707,7 @@ int launch_back_w(hpf_handle* h, const TreeDev& T, const int* nodes, int count, 
     hipLaunchKernelGGL((k_back_w<B>), dim3((unsigned)count, (unsigned)h->cur_S), dim3(64), 0, h->cur_stream, h->M, T, nodes,
                        2 * h->Hn, h->N, h->Nc, active, h->d_U, h->d_E, h->d_Z, h->d_w, h->d_x, h->d_f,
                        h->gj_mode ? h->d_H : nullptr, h->cur_s0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        return HPF_E_HIP;
-    }
-    return HPF_OK;
+    return launch_status(h);
 }
 
 #include "hpf_quad.hpp"
@@ -806,14 +796,9 @@ int launch_level(hpf_handle* h, const TreeDev& T, const int* nodes, int kind, in
     if (grid == 0) return HPF_OK;
     hipLaunchKernelGGL((k_level<B>), dim3(grid), dim3(256), 0, h->cur_stream, h->M, T, nodes, kind, nbatch, ngen, 2 * h->Hn,
                        h->N, h->Nc, active, h->cur_S, h->d_U, h->d_E, h->d_fb, h->d_Z, h->d_w, h->d_linA, h->d_C, h->d_H, h->d_I0, h->d_chG,
-                       h->d_chH, h->d_chD, h->d_chy, tr.d_Minv, tr.d_lbimg, tr.d_sbimg, h->d_lfK, h->d_lfS, h->d_dbg, h->debug_ablate,
+                       h->d_chH, h->d_chD, h->d_chy, tr.d_Minv, tr.d_lbimg, tr.d_sbimg, h->d_lfK, h->d_lfS, h->d_dbg, h->sw.debug_ablate,
                        h->cur_s0, h->d_pivflag, h->piv_limit, ts);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        return HPF_E_HIP;
-    }
-    return HPF_OK;
+    return launch_status(h);
 }
 
 // padded block size of the multi-wave MFMA path: 12 / 28 / 52, and 100 for 52 < b <= 100 (K <= 49: BASELINE config 5; the general
@@ -857,12 +842,7 @@ int launch_factor(hpf_handle* h, const TreeDev& T, const int* nodes, int count, 
     }
     hipLaunchKernelGGL((k_tree_factor<R>), dim3((unsigned)count, (unsigned)h->cur_S), dim3(256), lds, h->cur_stream, h->M, T,
                        nodes, b, h->N, h->Nc, active, h->d_U, h->d_E, h->d_f, h->d_Z, h->d_w, h->cur_s0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        return HPF_E_HIP;
-    }
-    return HPF_OK;
+    return launch_status(h);
 }
 
 
@@ -919,12 +899,7 @@ int launch_level_back(hpf_handle* h, const TreeDev& T, const int* sl_nodes, int 
     hipLaunchKernelGGL((k_level_back<B>), dim3(grid), dim3(256), 0, h->cur_stream, h->M, T, sl_nodes, n_sl, lf_nodes, n_lf, gj_nodes, n_gj, 2 * h->Hn,
                        h->N, h->Nc, active, h->cur_S, h->d_Z, h->d_w, h->d_x, h->d_H, tr.d_Minv, tr.d_lbimg, tr.d_sbimg, tr.d_lzimg, h->d_lfK, h->d_lfS,
                        h->cur_s0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        return HPF_E_HIP;
-    }
-    return HPF_OK;
+    return launch_status(h);
 }
 
 // =============================================================================================================
@@ -1015,8 +990,8 @@ namespace hpf {
 // the batched workgroups of elimination level l (lazy leaves at level 0, vector-only bordered buses above: 16 scenarios each);
 // kind 1 / 2 / 0 (none) -- the one place the factor sweep and the census take it from
 static int level_batched(const hpf_handle* h, const Tree& T, int l, int* kind) {
-    int nbatch = (l == 0 && h->leafbatch && h->has_ctree && T.lvl_all_leaf[0]) ? T.n_lazy_level0 : 0;
-    const bool slbatch = l > 0 && h->leafbatch && h->has_ctree && l < (int)T.lvl_nbatch.size() && T.lvl_nbatch[l] > 0;
+    int nbatch = (l == 0 && h->sw.leafbatch && h->has_ctree && T.lvl_all_leaf[0]) ? T.n_lazy_level0 : 0;
+    const bool slbatch = l > 0 && h->sw.leafbatch && h->has_ctree && l < (int)T.lvl_nbatch.size() && T.lvl_nbatch[l] > 0;
     if (slbatch) nbatch = T.lvl_nbatch[l];
     if (kind) *kind = nbatch > 0 ? (slbatch ? 2 : 1) : 0;
     return nbatch;
@@ -1025,7 +1000,7 @@ static int level_batched(const hpf_handle* h, const Tree& T, int l, int* kind) {
 // elimination level l of the current mode is ONE launch of k_level<BW> (else: k_leaf_batch / k_sleaf_batch + k_factor_q, or k_factor_q
 // alone): blocks of 52 always, smaller blocks only where the level has batched workgroups to put next to the per-scenario ones
 static bool level_is_fused(const hpf_handle* h, const Tree& T, int l, int BW) {
-    if (h->gj_mode != 1 || !h->fuse_levels || (BW != 12 && BW != 28 && BW != 52)) return false;
+    if (h->gj_mode != 1 || !h->sw.fuse_levels || (BW != 12 && BW != 28 && BW != 52)) return false;
     return BW == 52 || level_batched(h, T, l, nullptr) > 0;
 }
 
@@ -1084,7 +1059,7 @@ int tree_alloc_scenarios(hpf_handle* h) {
                           (e = hipMalloc((void**)&h->d_chZ, sizeof(double) * S * n * (size_t)h->Hn * 4)) != hipSuccess ||
                           (e = hipMalloc((void**)&h->d_lfK, sizeof(double) * S * n * 12)) != hipSuccess ||
                           (e = hipMalloc((void**)&h->d_lfS, sizeof(double) * S * n * (size_t)h->Hn * 4)) != hipSuccess)) ||
-        ((h->debug_ablate & 16) && (e = hipMalloc((void**)&h->d_dbg, sizeof(long long) * S * n * 8)) != hipSuccess) ||
+        ((h->sw.debug_ablate & 16) && (e = hipMalloc((void**)&h->d_dbg, sizeof(long long) * S * n * 8)) != hipSuccess) ||
         (bw && (e = hipMalloc((void**)&h->d_C, sizeof(double) * S * n * (size_t)(((bw + 16) / 16) * ((bw + 16) / 16) * 256))) != hipSuccess) ||
         (h->has_ctree && h->ctree.n_comp > 0 &&
          ((e = hipMalloc((void**)&h->d_F, sizeof(double) * S * (size_t)h->ctree.n_comp * 3 * ct)) != hipSuccess ||
@@ -1098,7 +1073,8 @@ int tree_alloc_scenarios(hpf_handle* h) {
 
 
 // Fundamental power-flow Newton step on a radial network (pf, HG:244-275): every bus is a plain power bus there, so the whole
-// tree is one "linear subtree" at harmonic position 0 -> the same 2x2 elimination, one thread per scenario walking the post-order.
+// tree is one "linear subtree" at harmonic position 0 -> the same 2x2 elimination (fund = 1): level-parallel where the tree has multi-wave
+// kernels, else one thread per scenario walking the post-order.
 int tree_fund_step(hpf_handle* h, bool only_active) {
     Tree& T = h->tree;
     const int* active = only_active ? h->d_active : nullptr;
@@ -1108,7 +1084,7 @@ int tree_fund_step(hpf_handle* h, bool only_active) {
     const int Bst = BW ? BW : b;
     ScopedTimer t(h, T_SOLVE);
     if (BW) {
-        // level-parallel: one launch per height of the tree, one thread per (bus, scenario) (k_lin_level_*, fund = 1)
+        // level-parallel: one launch per height of the tree, one thread per (bus, scenario) (k_lin_level_*)
         for (int hh = 0; hh < T.n_all_heights; ++hh) {
             const int cnt = T.ah_ptr[hh + 1] - T.ah_ptr[hh];
             hipLaunchKernelGGL(k_lin_level_factor, dim3((unsigned)((cnt + 127) / 128), (unsigned)h->cur_S), dim3(128), 0,
@@ -1121,269 +1097,252 @@ int tree_fund_step(hpf_handle* h, bool only_active) {
                                h->M, td, T.d_arec + 8 * (size_t)T.ah_ptr[hh], cnt, h->Nf, h->n - 1, Bst, active, h->d_U, h->d_E,
                                h->d_linA, h->d_w, h->d_x, h->d_f, 1, h->cur_s0);
         }
-        hipError_t e2 = hipGetLastError();
-        if (e2 != hipSuccess) {
-            h->last_detail = (int)e2;
-            return HPF_E_HIP;
-        }
-        return HPF_OK;
+    } else {
+        // one thread per scenario walks the post-order of the whole tree (k_lin_factor / k_lin_back)
+        hipLaunchKernelGGL((k_lin_factor<true>), dim3(1, (unsigned)h->cur_S), dim3(128), 0, h->cur_stream, h->M, td, 1, h->Nf,
+                           h->n - 1, Bst, active, h->d_U, h->d_E, h->d_f, h->d_linA, h->d_w, nullptr, h->cur_s0);
+        hipLaunchKernelGGL((k_lin_back<true>), dim3(1, (unsigned)h->cur_S), dim3(128), 0, h->cur_stream, h->M, td, 1, h->Nf,
+                           h->n - 1, Bst, active, h->d_U, h->d_E, h->d_linA, h->d_w, h->d_x, h->d_f, h->cur_s0);
     }
-    hipLaunchKernelGGL((k_lin_factor<true>), dim3(1, (unsigned)h->cur_S), dim3(128), 0, h->cur_stream, h->M, td, 1, h->Nf,
-                       h->n - 1, Bst, active, h->d_U, h->d_E, h->d_f, h->d_linA, h->d_w, nullptr, h->cur_s0);
-    hipLaunchKernelGGL((k_lin_back<true>), dim3(1, (unsigned)h->cur_S), dim3(128), 0, h->cur_stream, h->M, td, 1, h->Nf,
-                       h->n - 1, Bst, active, h->d_U, h->d_E, h->d_linA, h->d_w, h->d_x, h->d_f, h->cur_s0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        return HPF_E_HIP;
-    }
-    return HPF_OK;
+    return launch_status(h);
 }
 
-int tree_newton_step(hpf_handle* h, bool only_active) {
-    Tree& T = active_tree(h);
-    const int* active = only_active ? h->d_active : nullptr;
-    const TreeDev td{T.d_parent, T.d_child_ptr, T.d_child, T.d_e_up, T.d_e_dn, T.d_child_mid, T.d_lin_ptr, T.d_lin_post, T.d_child3, T.d_dchild, T.d_chain_ptr, T.d_chain_nodes, T.d_chain_ch, T.d_lzrec, T.d_lzimg,
-                     h->d_F, h->d_H2, T.d_comp_child, T.n_comp};
-    const int b = 2 * h->Hn;
-    const int R = (b + 15) / 16;
-    const int BW = wave_block_size(b);
-    const int lin_threads = T.n_lin_roots * h->Hn;
-    const int Bst = BW ? BW : b;
-    if (!h->tree_back_only) {                                        // (factor-once bordered step: its second pass is a back sweep alone)
-        const bool lvl2x2 = h->has_ctree && h->gj_mode == 1;         // level-parallel 2x2 kernels (records of the contracted tree)
-        if (lvl2x2) {
-            if (T.n_lin_bundles2 > 0) {                            // ... with one memory round trip (k_lin_bundle_factor)
-                const dim3 g2((unsigned)T.n_lin_bundles2, (unsigned)h->cur_S);
-#define HPF_LB_F(NP_)                                                                                                                  \
-    hipLaunchKernelGGL((k_lin_bundle_factor<NP_>), g2, dim3(256), 0, h->cur_stream, h->M, T.d_lb2rec, (const int2*)T.d_lb2x, T.d_lb2ptr, \
-                       T.n_lin_heights, Bst, active, h->d_U, h->d_E, h->d_fb, h->d_linA, h->d_w, h->d_I0, h->cur_s0, td,                   \
-                       T.chains_bundled ? T.d_lb2cptr : (const int*)nullptr, T.d_lb2clist, T.d_crec, T.d_cnode, h->d_chG, h->d_chH, h->d_chD, \
-                       h->d_chy, h->d_chZ)
-                if (T.lin_np == 1) HPF_LB_F(1);
-                else if (T.lin_np == 2) HPF_LB_F(2);
-                else HPF_LB_F(4);
-#undef HPF_LB_F
-            } else if (T.n_lin_bundles > 0)                        // every height of the all-linear subtrees in one launch
-                hipLaunchKernelGGL(k_lin_tree_factor, dim3((unsigned)T.n_lin_bundles, (unsigned)h->cur_S), dim3(256), 0, h->cur_stream,
-                                   h->M, td, T.d_lbrec, T.d_lbptr, T.n_lin_heights, h->N, h->Nc, Bst, active, h->d_U, h->d_E,
-                                   h->d_fb, h->d_linA, h->d_w, h->d_I0, h->cur_s0);
-            for (int hh = 0; hh < T.n_lin_heights && T.n_lin_bundles == 0 && T.n_lin_bundles2 == 0; ++hh) {
+// ---- the block-tree Newton step: factor sweep (2x2 algebra, then the dense levels leaves first), back sweep (dense depths root first,
+//      the scenario-batched leaves, then the 2x2 algebra).  Bst: padded block size of the bus-major images.
+
+// one-round-trip bundles of the linear subtrees (and of the chains with them, Tree::chains_bundled), NP items per thread
+template <int NP>
+static void lin_bundle_launch(hpf_handle* h, const Tree& T, const TreeDev& td, const int* active, int Bst, bool back) {
+    const dim3 grid((unsigned)T.n_lin_bundles2, (unsigned)h->cur_S);
+    const int* cptr = T.chains_bundled ? T.d_lb2cptr : (const int*)nullptr;
+    if (!back)
+        hipLaunchKernelGGL((k_lin_bundle_factor<NP>), grid, dim3(256), 0, h->cur_stream, h->M, T.d_lb2rec, (const int2*)T.d_lb2x, T.d_lb2ptr,
+                           T.n_lin_heights, Bst, active, h->d_U, h->d_E, h->d_fb, h->d_linA, h->d_w, h->d_I0, h->cur_s0, td, cptr, T.d_lb2clist,
+                           T.d_crec, T.d_cnode, h->d_chG, h->d_chH, h->d_chD, h->d_chy, h->d_chZ);
+    else
+        hipLaunchKernelGGL((k_lin_bundle_back<NP>), grid, dim3(256), 0, h->cur_stream, h->M, T.d_lb2rec, (const int2*)T.d_lb2x, T.d_lb2ptr,
+                           T.n_lin_heights, Bst, active, h->d_U, h->d_E, h->d_linA, h->d_w, h->d_x, h->cur_s0, cptr, T.d_lb2clist, T.d_crec,
+                           T.d_cnode, h->d_chZ);
+}
+
+static void lin_bundle(hpf_handle* h, const Tree& T, const TreeDev& td, const int* active, int Bst, bool back) {
+    if (T.lin_np == 1) lin_bundle_launch<1>(h, T, td, active, Bst, back);
+    else if (T.lin_np == 2) lin_bundle_launch<2>(h, T, td, active, Bst, back);
+    else lin_bundle_launch<4>(h, T, td, active, Bst, back);
+}
+
+// factor part of the 2x2 algebra: the all-linear subtrees in the tree's form, then the contracted chains
+static int lin_factor(hpf_handle* h, const Tree& T, const TreeDev& td, const int* active, int Bst) {
+    switch (T.lin_form) {
+        case LIN_ROOTS: {
+            const int lin_threads = T.n_lin_roots * h->Hn;
+            if (lin_threads > 0)
+                hipLaunchKernelGGL((k_lin_factor<false>), dim3((unsigned)((lin_threads + 127) / 128), (unsigned)h->cur_S), dim3(128), 0,
+                                   h->cur_stream, h->M, td, T.n_lin_roots, h->N, h->Nc, Bst, active, h->d_U, h->d_E, h->d_f,
+                                   h->d_linA, h->d_w, h->d_I0, h->cur_s0);
+            break;
+        }
+        case LIN_BUNDLE: lin_bundle(h, T, td, active, Bst, false); break;
+        case LIN_TREE:
+            hipLaunchKernelGGL(k_lin_tree_factor, dim3((unsigned)T.n_lin_bundles, (unsigned)h->cur_S), dim3(256), 0, h->cur_stream,
+                               h->M, td, T.d_lbrec, T.d_lbptr, T.n_lin_heights, h->N, h->Nc, Bst, active, h->d_U, h->d_E,
+                               h->d_fb, h->d_linA, h->d_w, h->d_I0, h->cur_s0);
+            break;
+        case LIN_LEVELS:
+            for (int hh = 0; hh < T.n_lin_heights; ++hh) {
                 const int cnt = T.lh_ptr[hh + 1] - T.lh_ptr[hh];
                 if (cnt == 0) continue;
                 hipLaunchKernelGGL(k_lin_level_factor, dim3((unsigned)((cnt * h->Hn + 127) / 128), (unsigned)h->cur_S), dim3(128), 0,
                                    h->cur_stream, h->M, td, T.d_lrec + 8 * (size_t)T.lh_ptr[hh], cnt, h->N, h->Nc, Bst, active,
                                    h->d_U, h->d_E, h->d_fb, h->d_linA, h->d_w, h->d_I0, 0, h->cur_s0);
             }
-            if (T.n_chains > 0 && !(T.chains_bundled && T.n_lin_bundles2 > 0))
-                hipLaunchKernelGGL(k_chain_factor2, dim3((unsigned)((T.n_chains * h->Hn + 127) / 128), (unsigned)h->cur_S), dim3(128),
-                                   0, h->cur_stream, h->M, td, T.d_crec, T.d_cnode, T.n_chains, h->N, h->Nc, Bst, active, h->d_U,
-                                   h->d_E, h->d_fb, h->d_linA, h->d_w, h->d_I0, h->d_chG, h->d_chH, h->d_chD, h->d_chy, h->d_chZ,
-                                   h->cur_s0);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) {
-                h->last_detail = (int)e;
-                return HPF_E_HIP;
-            }
-        }
-        if (!lvl2x2 && lin_threads > 0) {
-            hipLaunchKernelGGL((k_lin_factor<false>), dim3((unsigned)((lin_threads + 127) / 128), (unsigned)h->cur_S), dim3(128), 0,
-                               h->cur_stream, h->M, td, T.n_lin_roots, h->N, h->Nc, Bst, active, h->d_U, h->d_E, h->d_f,
-                               h->d_linA, h->d_w, h->d_I0, h->cur_s0);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) {
-                h->last_detail = (int)e;
-                return HPF_E_HIP;
-            }
-        }
-        for (int l = 0; l < T.n_levels; ++l) {
-            const int cnt = T.lvl_ptr[l + 1] - T.lvl_ptr[l];
-            if (cnt == 0) continue;
-            const int* nodes = T.d_lvl_nodes + T.lvl_ptr[l];
-            int r;
-            // level 0 of the contracted tree: its lazy leaves come first and go 16 scenarios per workgroup (k_leaf_batch)
-            int bkind = 0;                                      // (h->leafbatch == 0: one workgroup per (leaf, scenario), no batched ones)
-            const int nbatch = level_batched(h, T, l, &bkind);
-            const bool slbatch = bkind == 2;
-            switch (BW) {                       // (timing spans: one per kernel launch, inside the launch helpers)
-#define HPF_FACTOR_CASE(BB_)                                                                                  \
-    case BB_:                                                                                                 \
-        if (level_is_fused(h, T, l, BB_)) {                 /* one launch per level: batched and per-scenario workgroups                          \
-                                                      side by side (small blocks without batched workgroups: k_factor_q's own grid and LDS) */ \
-            r = launch_level<BB_>(h, td, T.d_fdesc + FDESC * (size_t)T.lvl_ptr[l], nbatch > 0 ? (slbatch ? 2 : 1) : 0, nbatch,       \
-                                  cnt - nbatch, active);                                                      \
-            break;                                                                                            \
-        }                                                                                                     \
-        if (h->gj_mode == 1 && nbatch > 0) {                                                                  \
-            r = slbatch ? launch_sleaf_batch<BB_>(h, td, T.d_fdesc + FDESC * (size_t)T.lvl_ptr[l], nbatch, active) \
-                        : launch_leaf_batch<BB_>(h, td, T.d_fdesc + FDESC * (size_t)T.lvl_ptr[l], nbatch, active); \
-            if (!r && cnt > nbatch)                                                                           \
-                r = launch_factor_q<BB_>(h, td, T.d_fdesc + FDESC * (size_t)(T.lvl_ptr[l] + nbatch), cnt - nbatch, active, !slbatch); \
-            break;                                                                                            \
-        }                                                                                                     \
-        r = h->gj_mode == 1 ? launch_factor_q<BB_>(h, td, T.d_fdesc + FDESC * (size_t)T.lvl_ptr[l], cnt, active, \
-                                                  T.lvl_all_leaf[l] != 0)                                       \
-                            : launch_factor_w<BB_>(h, td, nodes, cnt, active);                               \
-        break
-                HPF_FACTOR_CASE(12);
-                HPF_FACTOR_CASE(28);
-                HPF_FACTOR_CASE(52);
-#undef HPF_FACTOR_CASE
-                case 100:       // 52 < b <= 100: general multi-wave kernel for every dense bus; pivoted mode = generic kernels below
-                    if (h->gj_mode == 1) {
-                        r = launch_factor_q<100>(h, td, T.d_fdesc + FDESC * (size_t)T.lvl_ptr[l], cnt, active, T.lvl_all_leaf[l] != 0);
-                        break;
-                    }
-                    [[fallthrough]];
-                default:
-                    switch (R) {
-                        case 4: r = launch_factor<4>(h, td, nodes, cnt, active); break;
-                        case 5: r = launch_factor<5>(h, td, nodes, cnt, active); break;
-                        case 6: r = launch_factor<6>(h, td, nodes, cnt, active); break;
-                        case 7: r = launch_factor<7>(h, td, nodes, cnt, active); break;
-                        default: return HPF_E_ARG;
-                    }
-            }
-            if (r) return r;
-        }
+            break;
     }
+    if (T.chain_launches)
+        hipLaunchKernelGGL(k_chain_factor2, dim3((unsigned)((T.n_chains * h->Hn + 127) / 128), (unsigned)h->cur_S), dim3(128),
+                           0, h->cur_stream, h->M, td, T.d_crec, T.d_cnode, T.n_chains, h->N, h->Nc, Bst, active, h->d_U,
+                           h->d_E, h->d_fb, h->d_linA, h->d_w, h->d_I0, h->d_chG, h->d_chH, h->d_chD, h->d_chy, h->d_chZ,
+                           h->cur_s0);
+    return launch_status(h);
+}
+
+// back part of the 2x2 algebra: the contracted chains, then the all-linear subtrees in the tree's form
+static int lin_back(hpf_handle* h, const Tree& T, const TreeDev& td, const int* active, int Bst) {
+    if (T.chain_launches)
+        hipLaunchKernelGGL(k_chain_back2, dim3((unsigned)((T.n_chains * h->Hn + 127) / 128), (unsigned)h->cur_S), dim3(128), 0,
+                           h->cur_stream, h->M, td, T.d_crec, T.d_cnode, T.n_chains, h->N, h->Nc, Bst, active, h->d_U, h->d_E,
+                           h->d_linA, h->d_w, h->d_x, (double*)nullptr, h->d_chZ, h->cur_s0);
+    switch (T.lin_form) {
+        case LIN_ROOTS: {
+            const int lin_threads = T.n_lin_roots * h->Hn;
+            if (lin_threads > 0)
+                hipLaunchKernelGGL((k_lin_back<false>), dim3((unsigned)((lin_threads + 127) / 128), (unsigned)h->cur_S), dim3(128), 0,
+                                   h->cur_stream, h->M, td, T.n_lin_roots, h->N, h->Nc, Bst, active, h->d_U, h->d_E, h->d_linA, h->d_w,
+                                   h->d_x, h->d_f, h->cur_s0);
+            break;
+        }
+        case LIN_BUNDLE: lin_bundle(h, T, td, active, Bst, true); break;
+        case LIN_TREE:
+            hipLaunchKernelGGL(k_lin_tree_back, dim3((unsigned)T.n_lin_bundles, (unsigned)h->cur_S), dim3(256), 0, h->cur_stream, h->M,
+                               td, T.d_lbrec, T.d_lbptr, T.n_lin_heights, h->N, h->Nc, Bst, active, h->d_U, h->d_E, h->d_linA, h->d_w,
+                               h->d_x, h->cur_s0);
+            break;
+        case LIN_LEVELS:
+            for (int hh = T.n_lin_heights - 1; hh >= 0; --hh) {
+                const int cnt = T.lh_ptr[hh + 1] - T.lh_ptr[hh];
+                if (cnt == 0) continue;
+                hipLaunchKernelGGL(k_lin_level_back, dim3((unsigned)((cnt * h->Hn + 127) / 128), (unsigned)h->cur_S), dim3(128), 0,
+                                   h->cur_stream, h->M, td, T.d_lrec + 8 * (size_t)T.lh_ptr[hh], cnt, h->N, h->Nc, Bst, active, h->d_U,
+                                   h->d_E, h->d_linA, h->d_w, h->d_x, (double*)nullptr, 0, h->cur_s0);
+            }
+            break;
+    }
+    return launch_status(h);
+}
+
+// elimination level l on the multi-wave kernels of blocks of BW = 12 / 28 / 52 rows (timing spans: one per launch, inside the launch helpers)
+template <int BW>
+static int factor_level(hpf_handle* h, const Tree& T, const TreeDev& td, int l, const int* active) {
+    const int cnt = T.lvl_ptr[l + 1] - T.lvl_ptr[l];
+    const int* fdesc = T.d_fdesc + FDESC * (size_t)T.lvl_ptr[l];
+    int kind = 0;                                   // (h->sw.leafbatch == 0: one workgroup per (leaf, scenario), no batched ones)
+    const int nbatch = level_batched(h, T, l, &kind);
+    if (level_is_fused(h, T, l, BW))                // one launch per level: batched and per-scenario workgroups side by side
+        return launch_level<BW>(h, td, fdesc, kind, nbatch, cnt - nbatch, active);
+    if (h->gj_mode != 1) return launch_factor_w<BW>(h, td, T.d_lvl_nodes + T.lvl_ptr[l], cnt, active);
+    if (nbatch == 0) return launch_factor_q<BW>(h, td, fdesc, cnt, active, T.lvl_all_leaf[l] != 0);
+    // the level's batched workgroups first (lazy leaves at level 0, vector-only bordered buses above: 16 scenarios each), then the rest
+    int r = kind == 2 ? launch_sleaf_batch<BW>(h, td, fdesc, nbatch, active) : launch_leaf_batch<BW>(h, td, fdesc, nbatch, active);
+    if (!r && cnt > nbatch) r = launch_factor_q<BW>(h, td, fdesc + FDESC * (size_t)nbatch, cnt - nbatch, active, kind != 2);
+    return r;
+}
+
+// the generic 256-thread kernel (b > 100, and the pivoted variant for 52 < b <= 100)
+static int factor_level_generic(hpf_handle* h, const TreeDev& td, const int* nodes, int cnt, const int* active) {
+    switch ((2 * h->Hn + 15) / 16) {
+        case 4: return launch_factor<4>(h, td, nodes, cnt, active);
+        case 5: return launch_factor<5>(h, td, nodes, cnt, active);
+        case 6: return launch_factor<6>(h, td, nodes, cnt, active);
+        case 7: return launch_factor<7>(h, td, nodes, cnt, active);
+        default: return HPF_E_ARG;
+    }
+}
+
+static int factor_sweep(hpf_handle* h, const Tree& T, const TreeDev& td, const int* active, int Bst) {
+    int r = lin_factor(h, T, td, active, Bst);
+    if (r) return r;
+    const int BW = wave_block_size(2 * h->Hn);
+    for (int l = 0; l < T.n_levels; ++l) {
+        const int cnt = T.lvl_ptr[l + 1] - T.lvl_ptr[l];
+        if (cnt == 0) continue;
+        switch (BW) {
+            case 12: r = factor_level<12>(h, T, td, l, active); break;
+            case 28: r = factor_level<28>(h, T, td, l, active); break;
+            case 52: r = factor_level<52>(h, T, td, l, active); break;
+            case 100:       // 52 < b <= 100: general multi-wave kernel for every dense bus; pivoted mode = generic kernels
+                if (h->gj_mode == 1) {
+                    r = launch_factor_q<100>(h, td, T.d_fdesc + FDESC * (size_t)T.lvl_ptr[l], cnt, active, T.lvl_all_leaf[l] != 0);
+                    break;
+                }
+                [[fallthrough]];
+            default: r = factor_level_generic(h, td, T.d_lvl_nodes + T.lvl_ptr[l], cnt, active);
+        }
+        if (r) return r;
+    }
+    return HPF_OK;
+}
+
+// one launch per depth for all bus kinds (k_level_back) where the batched bodies exist and every body has four wavefronts
+// (groups of up to 32 scenarios only: larger launches are throughput-bound, and k_back_q alone runs at twice the
+//  occupancy of the fused kernel -- 5.2 vs 5.4 ms per step at 1 024 scenarios, 0.297 vs 0.288 ms at one)
+static bool back_is_fused(const hpf_handle* h, const Tree& T, int BW) {
+    bool fused = h->sw.fuse_back && h->cur_S <= h->sw.fuse_back_max && h->sw.leafbatch && h->has_ctree && h->gj_mode == 1 && BW == 52 &&
+                 (int)T.bsl_dep_ptr.size() == T.n_depths + 1 && (int)T.bleaf_dep_ptr.size() == T.n_depths + 1 && (int)T.dep_nleaf.size() >= T.n_depths;
+    for (int dl = 1; fused && dl < T.n_depths; ++dl)            // (a depth's batched records are exactly its leaves + bordered buses)
+        fused = T.bsl_dep_ptr[dl + 1] - T.bsl_dep_ptr[dl] + T.bleaf_dep_ptr[dl + 1] - T.bleaf_dep_ptr[dl] == T.dep_nleaf[dl];
+    return fused && T.bsl_dep_ptr[1] == 0 && T.bleaf_dep_ptr[1] == 0;
+}
+
+// back-sweep depth dl on the multi-wave kernels of blocks of BW = 12 / 28 / 52 rows; its first nlb buses are constant-inverse leaves
+// that wait for the one batched launch after the last depth
+template <int BW>
+static int back_depth(hpf_handle* h, const Tree& T, const TreeDev& td, int dl, int nlb, const int* active) {
+    const int cnt = T.dep_ptr[dl + 1] - T.dep_ptr[dl];
+    if (h->gj_mode != 1) return launch_back_w<BW>(h, td, T.d_dep_nodes + T.dep_ptr[dl], cnt, active);
+    return cnt > nlb ? launch_back_q<BW>(h, td, T.d_bdesc + 4 * (size_t)(T.dep_ptr[dl] + nlb), cnt - nlb, active) : HPF_OK;
+}
+
+// every bordered bus and constant-inverse leaf at once, 16 scenarios per workgroup: a leaf's x needs its parent's only, and nothing of the
+// dense tree hangs below a leaf (the 2x2 kernels that do come next)
+template <int BW>
+static int back_batched(hpf_handle* h, const Tree& T, const int* active) {
+    // bordered buses first (leaves hang below them), in groups by nesting order: nested ones first
+    for (size_t gi = 0; gi + 1 < T.bsleaf_ptr.size() && T.n_bsleaf > 0; ++gi) {
+        const int b0 = T.bsleaf_ptr[gi], cnt = T.bsleaf_ptr[gi + 1] - b0;
+        if (cnt <= 0) continue;
+        if (int r = launch_sleaf_back_batch<BW>(h, T.d_bsleaf + 8 * (size_t)b0, cnt, active)) return r;
+    }
+    return T.n_bleaf > 0 ? launch_leaf_back_batch<BW>(h, T.d_bleaf, T.n_bleaf, active) : HPF_OK;
+}
+
+static int back_sweep(hpf_handle* h, const Tree& T, const TreeDev& td, const int* active, int Bst) {
     ScopedTimer tb(h, T_BACK);
-    // one launch per depth for all bus kinds (k_level_back) where the batched bodies exist and every body has four wavefronts
-    // (groups of up to 32 scenarios only: larger launches are throughput-bound, and k_back_q alone runs at twice the
-    //  occupancy of the fused kernel -- 5.2 vs 5.4 ms per step at 1 024 scenarios, 0.297 vs 0.288 ms at one)
-    bool fused_back = h->fuse_back && h->cur_S <= h->fuse_back_max && h->leafbatch && h->has_ctree && h->gj_mode == 1 && BW == 52 &&
-                      (int)T.bsl_dep_ptr.size() == T.n_depths + 1 && (int)T.bleaf_dep_ptr.size() == T.n_depths + 1 && (int)T.dep_nleaf.size() >= T.n_depths;
-    for (int dl = 1; fused_back && dl < T.n_depths; ++dl)         // (a depth's batched records are exactly its leaves + bordered buses)
-        fused_back = T.bsl_dep_ptr[dl + 1] - T.bsl_dep_ptr[dl] + T.bleaf_dep_ptr[dl + 1] - T.bleaf_dep_ptr[dl] == T.dep_nleaf[dl];
-    if (fused_back && (T.bsl_dep_ptr[1] != 0 || T.bleaf_dep_ptr[1] != 0)) fused_back = false;
+    const int BW = wave_block_size(2 * h->Hn);
+    const bool fused_back = back_is_fused(h, T, BW);
     for (int dl = 0; dl < T.n_depths; ++dl) {
         const int cnt = T.dep_ptr[dl + 1] - T.dep_ptr[dl];
         if (cnt == 0) continue;
         const int* nodes = T.d_dep_nodes + T.dep_ptr[dl];
+        const int nlb = (h->sw.leafbatch && h->has_ctree && dl > 0 && dl < (int)T.dep_nleaf.size()) ? T.dep_nleaf[dl] : 0;
         int r = HPF_OK;
-        const int leafbatch_b = h->leafbatch;
-        const int nlb = (leafbatch_b && h->has_ctree && dl > 0 && dl < (int)T.dep_nleaf.size()) ? T.dep_nleaf[dl] : 0;
         if (fused_back) {
             const int n_sl = dl > 0 ? T.bsl_dep_ptr[dl + 1] - T.bsl_dep_ptr[dl] : 0, n_lf = dl > 0 ? T.bleaf_dep_ptr[dl + 1] - T.bleaf_dep_ptr[dl] : 0;
-            if ((r = launch_level_back<52>(h, td, T.d_bsleaf_dep + 8 * (size_t)T.bsl_dep_ptr[dl], n_sl, T.d_bleaf + 4 * (size_t)T.bleaf_dep_ptr[dl], n_lf,
-                                           T.d_bdesc + 4 * (size_t)(T.dep_ptr[dl] + nlb), cnt - nlb, active)))
-                return r;
-            continue;
-        }
-        switch (BW) {
-            case 12:
-                if (h->gj_mode == 1 && nlb > 0) {                    // (the leaves of this depth wait for the one batched launch below)
-                    if (cnt > nlb) r = launch_back_q<12>(h, td, T.d_bdesc + 4 * (size_t)(T.dep_ptr[dl] + nlb), cnt - nlb, active);
-                    break;
-                }
-                r = h->gj_mode == 1 ? launch_back_q<12>(h, td, T.d_bdesc + 4 * (size_t)T.dep_ptr[dl], cnt, active) : launch_back_w<12>(h, td, nodes, cnt, active);
-                break;
-            case 28:
-                if (h->gj_mode == 1 && nlb > 0) {                    // (the leaves of this depth wait for the one batched launch below)
-                    if (cnt > nlb) r = launch_back_q<28>(h, td, T.d_bdesc + 4 * (size_t)(T.dep_ptr[dl] + nlb), cnt - nlb, active);
-                    break;
-                }
-                r = h->gj_mode == 1 ? launch_back_q<28>(h, td, T.d_bdesc + 4 * (size_t)T.dep_ptr[dl], cnt, active) : launch_back_w<28>(h, td, nodes, cnt, active);
-                break;
-            case 52:
-                if (h->gj_mode == 1 && nlb > 0) {                    // (the leaves of this depth wait for the one batched launch below)
-                    if (cnt > nlb) r = launch_back_q<52>(h, td, T.d_bdesc + 4 * (size_t)(T.dep_ptr[dl] + nlb), cnt - nlb, active);
-                    break;
-                }
-                r = h->gj_mode == 1 ? launch_back_q<52>(h, td, T.d_bdesc + 4 * (size_t)T.dep_ptr[dl], cnt, active) : launch_back_w<52>(h, td, nodes, cnt, active);
-                break;
-            case 100:
-                if (h->gj_mode == 1) {
-                    r = launch_back_q<100>(h, td, T.d_bdesc + 4 * (size_t)T.dep_ptr[dl], cnt, active);
-                    break;
-                }
-                [[fallthrough]];
-            default: {
-                hipLaunchKernelGGL(k_tree_back, dim3((unsigned)cnt, (unsigned)h->cur_S), dim3(256), 0, h->cur_stream, h->n, h->c,
-                                   h->Hn, td, nodes, b, h->N, h->Nc, active, h->d_Z, h->d_w, h->d_x, h->d_f, h->cur_s0);
-                hipError_t e = hipGetLastError();
-                if (e != hipSuccess) {
-                    h->last_detail = (int)e;
-                    return HPF_E_HIP;
-                }
+            r = launch_level_back<52>(h, td, T.d_bsleaf_dep + 8 * (size_t)T.bsl_dep_ptr[dl], n_sl, T.d_bleaf + 4 * (size_t)T.bleaf_dep_ptr[dl], n_lf,
+                                      T.d_bdesc + 4 * (size_t)(T.dep_ptr[dl] + nlb), cnt - nlb, active);
+        } else {
+            switch (BW) {
+                case 12: r = back_depth<12>(h, T, td, dl, nlb, active); break;
+                case 28: r = back_depth<28>(h, T, td, dl, nlb, active); break;
+                case 52: r = back_depth<52>(h, T, td, dl, nlb, active); break;
+                case 100:
+                    if (h->gj_mode == 1) {
+                        r = launch_back_q<100>(h, td, T.d_bdesc + 4 * (size_t)T.dep_ptr[dl], cnt, active);
+                        break;
+                    }
+                    [[fallthrough]];
+                default:
+                    hipLaunchKernelGGL(k_tree_back, dim3((unsigned)cnt, (unsigned)h->cur_S), dim3(256), 0, h->cur_stream, h->n, h->c,
+                                       h->Hn, td, nodes, 2 * h->Hn, h->N, h->Nc, active, h->d_Z, h->d_w, h->d_x, h->d_f, h->cur_s0);
+                    r = launch_status(h);
             }
         }
         if (r) return r;
     }
-    {
-        // every constant-inverse leaf at once, 16 scenarios per workgroup: a leaf's x needs its parent's only, and nothing of the
-        // dense tree hangs below a leaf (the 2x2 kernels that do come next)
-        const int leafbatch_e = h->leafbatch && !fused_back;
-        if (leafbatch_e && h->has_ctree && h->gj_mode == 1 && T.n_bsleaf > 0) {    // super-leaves first: leaves hang below them
-            int r = HPF_OK;
-            for (size_t gi = 0; gi + 1 < T.bsleaf_ptr.size() && !r; ++gi) {      // nested bordered buses first (by nesting order)
-                const int b0 = T.bsleaf_ptr[gi], bc2 = T.bsleaf_ptr[gi + 1] - b0;
-                if (bc2 <= 0) continue;
-                switch (BW) {
-                    case 12: r = launch_sleaf_back_batch<12>(h, T.d_bsleaf + 8 * (size_t)b0, bc2, active); break;
-                    case 28: r = launch_sleaf_back_batch<28>(h, T.d_bsleaf + 8 * (size_t)b0, bc2, active); break;
-                    case 52: r = launch_sleaf_back_batch<52>(h, T.d_bsleaf + 8 * (size_t)b0, bc2, active); break;
-                    default: break;
-                }
-            }
-            if (r) return r;
+    if (h->sw.leafbatch && !fused_back && h->has_ctree && h->gj_mode == 1) {
+        int r = HPF_OK;
+        switch (BW) {
+            case 12: r = back_batched<12>(h, T, active); break;
+            case 28: r = back_batched<28>(h, T, active); break;
+            case 52: r = back_batched<52>(h, T, active); break;
+            default: break;
         }
-        if (leafbatch_e && h->has_ctree && h->gj_mode == 1 && T.n_bleaf > 0) {
-            int r = HPF_OK;
-            switch (BW) {
-                case 12: r = launch_leaf_back_batch<12>(h, T.d_bleaf, T.n_bleaf, active); break;
-                case 28: r = launch_leaf_back_batch<28>(h, T.d_bleaf, T.n_bleaf, active); break;
-                case 52: r = launch_leaf_back_batch<52>(h, T.d_bleaf, T.n_bleaf, active); break;
-                default: break;
-            }
-            if (r) return r;
-        }
+        if (r) return r;
     }
-    const bool lvl2x2b = h->has_ctree && h->gj_mode == 1;
-    if (lvl2x2b) {
-        if (T.n_chains > 0 && !(T.chains_bundled && T.n_lin_bundles2 > 0))
-            hipLaunchKernelGGL(k_chain_back2, dim3((unsigned)((T.n_chains * h->Hn + 127) / 128), (unsigned)h->cur_S), dim3(128), 0,
-                               h->cur_stream, h->M, td, T.d_crec, T.d_cnode, T.n_chains, h->N, h->Nc, Bst, active, h->d_U, h->d_E,
-                               h->d_linA, h->d_w, h->d_x, (double*)nullptr, h->d_chZ, h->cur_s0);
-        if (T.n_lin_bundles2 > 0) {
-            const dim3 g2((unsigned)T.n_lin_bundles2, (unsigned)h->cur_S);
-#define HPF_LB_B(NP_)                                                                                                                \
-    hipLaunchKernelGGL((k_lin_bundle_back<NP_>), g2, dim3(256), 0, h->cur_stream, h->M, T.d_lb2rec, (const int2*)T.d_lb2x, T.d_lb2ptr, \
-                       T.n_lin_heights, Bst, active, h->d_U, h->d_E, h->d_linA, h->d_w, h->d_x, h->cur_s0,                                 \
-                       T.chains_bundled ? T.d_lb2cptr : (const int*)nullptr, T.d_lb2clist, T.d_crec, T.d_cnode, h->d_chZ)
-            if (T.lin_np == 1) HPF_LB_B(1);
-            else if (T.lin_np == 2) HPF_LB_B(2);
-            else HPF_LB_B(4);
-#undef HPF_LB_B
-        } else if (T.n_lin_bundles > 0)
-            hipLaunchKernelGGL(k_lin_tree_back, dim3((unsigned)T.n_lin_bundles, (unsigned)h->cur_S), dim3(256), 0, h->cur_stream, h->M,
-                               td, T.d_lbrec, T.d_lbptr, T.n_lin_heights, h->N, h->Nc, Bst, active, h->d_U, h->d_E, h->d_linA, h->d_w,
-                               h->d_x, h->cur_s0);
-        for (int hh = T.n_lin_heights - 1; hh >= 0 && T.n_lin_bundles == 0 && T.n_lin_bundles2 == 0; --hh) {
-            const int cnt = T.lh_ptr[hh + 1] - T.lh_ptr[hh];
-            if (cnt == 0) continue;
-            hipLaunchKernelGGL(k_lin_level_back, dim3((unsigned)((cnt * h->Hn + 127) / 128), (unsigned)h->cur_S), dim3(128), 0,
-                               h->cur_stream, h->M, td, T.d_lrec + 8 * (size_t)T.lh_ptr[hh], cnt, h->N, h->Nc, Bst, active, h->d_U,
-                               h->d_E, h->d_linA, h->d_w, h->d_x, (double*)nullptr, 0, h->cur_s0);
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            h->last_detail = (int)e;
-            return HPF_E_HIP;
-        }
-        return HPF_OK;
+    return lin_back(h, T, td, active, Bst);
+}
+
+int tree_newton_step(hpf_handle* h, bool only_active) {
+    const Tree& T = active_tree(h);
+    const int* active = only_active ? h->d_active : nullptr;
+    const TreeDev td{T.d_parent, T.d_child_ptr, T.d_child, T.d_e_up, T.d_e_dn, T.d_child_mid, T.d_lin_ptr, T.d_lin_post, T.d_child3, T.d_dchild, T.d_chain_ptr, T.d_chain_nodes, T.d_chain_ch, T.d_lzrec, T.d_lzimg,
+                     h->d_F, h->d_H2, T.d_comp_child, T.n_comp};
+    const int b = 2 * h->Hn, BW = wave_block_size(b);
+    const int Bst = BW ? BW : b;
+    if (!h->tree_back_only) {                                        // (factor-once bordered step: its second pass is a back sweep alone)
+        const int r = factor_sweep(h, T, td, active, Bst);
+        if (r) return r;
     }
-    if (lin_threads > 0) {
-        hipLaunchKernelGGL((k_lin_back<false>), dim3((unsigned)((lin_threads + 127) / 128), (unsigned)h->cur_S), dim3(128), 0, h->cur_stream,
-                           h->M, td, T.n_lin_roots, h->N, h->Nc, Bst, active, h->d_U, h->d_E, h->d_linA, h->d_w, h->d_x,
-                           h->d_f, h->cur_s0);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            h->last_detail = (int)e;
-            return HPF_E_HIP;
-        }
-    }
-    return HPF_OK;
+    return back_sweep(h, T, td, active, Bst);
 }
 
 // BFS spanning tree of the admittance pattern from bus 0 (the SAME visiting order as tree_build_into) and the entries that are
@@ -1447,8 +1406,7 @@ int tree_find_ties(hpf_handle* h, const hpf_desc* d) {
     h->mesh_sel = false;
     h->sel_forced.clear();
     {
-        const char* ms = h->sw("HPF_MESH_SEL");
-        if (!(ms && atoi(ms) == 0) && d->coupled) {
+        if (h->sw.mesh_sel && d->coupled) {
             std::vector<char> fp(n, 0);
             size_t nP = 0;
             for (int i : tb_bus)
@@ -1491,7 +1449,7 @@ int ensure_blas(hpf_handle* h) {
 // runs in the throughput regime of the tree kernels: 6.5 us per scenario-step at 256 live slots, 5.5 at 1 024; 72 MB of state per slot)
 int border_slots(const hpf_handle* h) {
     if (h->mesh_sel) return 0;                           // factor-once form: the scenarios are swept in their own slots
-    const int c = h->border_slot_cap < 16 ? 16 : h->border_slot_cap;   // (HPF_BORDER_SLOTS, read by hpf_create into the handle)
+    const int c = h->sw.border_slot_cap < 16 ? 16 : h->sw.border_slot_cap;   // (HPF_BORDER_SLOTS, read by hpf_create into the handle)
     return h->m_border + 1 < 256 ? h->m_border + 1 : (h->m_border + 1 < c ? ((h->m_border + 1 + 15) / 16) * 16 : c);
 }
 
@@ -1814,15 +1772,12 @@ int tree_sel_build(hpf_handle* h, const hpf_desc* d) {
     // together): as many as fit HPF_MESH_BATCH_GB (default 48) of the handle's capacity, at least one.
     const size_t mb = (size_t)h->m_border;
     {
-        const char* bg = h->sw("HPF_BORDER_GJ");
-        const int lim = bg ? atoi(bg) : 96;
-        h->border_gj = mT <= lim && mT >= 1;
+        h->border_gj = mT <= h->sw.border_gj && mT >= 1;
         const double per = 8.0 * ((double)bb * (3.0 * nP + npairs + (double)nP * mT + (h->border_gj ? (double)mT * (mT + 1) : 0.0)) + (double)mb * mb + (double)nP * b +
                                   3.0 * mb + 8.0 * h->n_ties * h->Hn);
-        const char* gb = h->sw("HPF_MESH_BATCH_GB");
-        double budget = (gb ? atof(gb) : 48.0) * 1073741824.0;
+        double budget = h->sw.mesh_batch_gb * 1073741824.0;
         size_t free_b = 0, total_b = 0;                  // (never more than half of what the device has free at this point: the scenario state follows)
-        if (!gb && hipMemGetInfo(&free_b, &total_b) == hipSuccess && budget > 0.5 * (double)free_b) budget = 0.5 * (double)free_b;
+        if (!h->sw.mesh_batch_gb_given && hipMemGetInfo(&free_b, &total_b) == hipSuccess && budget > 0.5 * (double)free_b) budget = 0.5 * (double)free_b;
         long long cap = (long long)(budget / per);
         cap = cap < 1 ? 1 : (cap > h->S_max ? h->S_max : cap);
         h->sel_cap = (int)cap;
@@ -1886,31 +1841,25 @@ int tree_sel_build(hpf_handle* h, const hpf_desc* d) {
     // fallback of the border solve stay), scales block row k, and eliminates block column k from every other row -- three launches per step;
     // the right-hand side rides as block column n_tb.  Measured on syn1000 + 5 / 20 / 40 / 80 ties (n_tb = 10 / 39 / 78 / 150): 1.40 / 3.2 / 9.0 / 47 ms
     // per Newton step against 2.2 / 5.7 / 11.7 / 31 ms with rocSOLVER (1.5 x the flops of an LU, block products at ~2 TFLOP/s).
-    {
-        const char* bl = h->sw("HPF_BORDER_PIVLIM");
-        if (bl && atof(bl) > 0.0) h->border_piv_limit = atof(bl);
-        const char* bm = h->sw("HPF_BORDER_GJ_MFMA");
-        h->border_gj_mfma = !(bm && atoi(bm) == 0);     // 0: the diagonal blocks through the VALU Gauss-Jordan (gj_dense_invert_npvt; A/B)
-        if (h->border_gj) {
-            const size_t W = (size_t)mT + 1;
-            if (!dalloc(&h->d_bB, cap * (size_t)mT * W * bb)) return HPF_E_NOMEM;
-            const long long sB = (long long)((size_t)mT * W * bb);
-            std::vector<BlkJob> gj;
-            h->bgj_beg.assign(1, 0);
-            auto blk = [&](size_t s2, size_t t2) { return h->d_bB + (s2 * W + t2) * bb; };
-            for (size_t k = 0; k < (size_t)mT; ++k) {
-                for (size_t t2 = k + 1; t2 < W; ++t2) gj.push_back({blk(k, k), blk(k, t2), nullptr, blk(k, t2), 1.0, sB, sB, 0, sB});
-                h->bgj_beg.push_back(gj.size());
-                for (size_t i = 0; i < (size_t)mT; ++i)
-                    if (i != k)
-                        for (size_t t2 = k + 1; t2 < W; ++t2) gj.push_back({blk(i, k), blk(k, t2), blk(i, t2), blk(i, t2), -1.0, sB, sB, sB, sB});
-                h->bgj_beg.push_back(gj.size());
-            }
-            if (hipMalloc(&h->d_bgj_jobs, sizeof(BlkJob) * (gj.size() ? gj.size() : 1)) != hipSuccess) return HPF_E_NOMEM;
-            if (hipMemcpy(h->d_bgj_jobs, gj.data(), sizeof(BlkJob) * gj.size(), hipMemcpyHostToDevice) != hipSuccess) return HPF_E_HIP;
+    if (h->border_gj) {
+        const size_t W = (size_t)mT + 1;
+        if (!dalloc(&h->d_bB, cap * (size_t)mT * W * bb)) return HPF_E_NOMEM;
+        const long long sB = (long long)((size_t)mT * W * bb);
+        std::vector<BlkJob> gj;
+        h->bgj_beg.assign(1, 0);
+        auto blk = [&](size_t s2, size_t t2) { return h->d_bB + (s2 * W + t2) * bb; };
+        for (size_t k = 0; k < (size_t)mT; ++k) {
+            for (size_t t2 = k + 1; t2 < W; ++t2) gj.push_back({blk(k, k), blk(k, t2), nullptr, blk(k, t2), 1.0, sB, sB, 0, sB});
+            h->bgj_beg.push_back(gj.size());
+            for (size_t i = 0; i < (size_t)mT; ++i)
+                if (i != k)
+                    for (size_t t2 = k + 1; t2 < W; ++t2) gj.push_back({blk(i, k), blk(k, t2), blk(i, t2), blk(i, t2), -1.0, sB, sB, sB, sB});
+            h->bgj_beg.push_back(gj.size());
         }
+        if (hipMalloc(&h->d_bgj_jobs, sizeof(BlkJob) * (gj.size() ? gj.size() : 1)) != hipSuccess) return HPF_E_NOMEM;
+        if (hipMemcpy(h->d_bgj_jobs, gj.data(), sizeof(BlkJob) * gj.size(), hipMemcpyHostToDevice) != hipSuccess) return HPF_E_HIP;
     }
-    if (h->sw("HPF_TREE_INFO"))
+    if (h->sw.tree_info)
         fprintf(stderr, "hpf tree: factor-once bordered step: %d ties, %d endpoint buses (border %d), %zu buses on their root paths, %zu forward pairs, "
                         "%zu block products per Newton step and scenario\n", h->n_ties, mT, h->m_border, nP, npairs, jobs.size());
     return HPF_OK;
@@ -1945,7 +1894,7 @@ static void border_block_gj(hpf_handle* h, int cn, hipStream_t st) {
     hipLaunchKernelGGL(k_border_rhs_blocks, dim3((unsigned)((mT * bb + 255) / 256), (unsigned)cn), dim3(256), 0, st, b, mT, (const double*)h->d_sel_rhs, h->d_bB);
     for (int k = 0; k < mT; ++k) {
         double* dk = h->d_bB + ((size_t)k * W + k) * bb;
-        if (!h->border_gj_mfma || !launch_invert_mfma(wave_block_size(b), b, dk, sB, cn, h->border_piv_limit, h->d_sel_info, st)) launch_invert(R, b, dk, sB, cn, h->d_sel_info, st);
+        if (!h->sw.border_gj_mfma || !launch_invert_mfma(wave_block_size(b), b, dk, sB, cn, h->sw.border_pivlim, h->d_sel_info, st)) launch_invert(R, b, dk, sB, cn, h->d_sel_info, st);
         launch_jobs(R, b, (int)(h->bgj_beg[2 * k + 1] - h->bgj_beg[2 * k]), jobs + h->bgj_beg[2 * k], st, cn);
         launch_jobs(R, b, (int)(h->bgj_beg[2 * k + 2] - h->bgj_beg[2 * k + 1]), jobs + h->bgj_beg[2 * k + 1], st, cn);
     }
@@ -1989,10 +1938,10 @@ static int tree_newton_step_sel(hpf_handle* h, bool only_active) {
         if (hipMemcpyAsync(h->sel_res_host.data(), h->d_sel_res, sizeof(unsigned long long) * 2 * cn, hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipMemcpyAsync(h->sel_info_host.data(), h->d_sel_info, sizeof(int) * cn, hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess) {
-            h->last_detail = (int)hipGetLastError();
+            launch_status(h);                             // (last_detail <- the failed call's error)
             return HPF_E_HIP;
         }
-        const bool info_on = h->sw("HPF_BORDER_INFO") != nullptr;
+        const bool info_on = h->sw.border_info;
         for (int y = 0; y < cn; ++y) {
             const int sc = only_active ? ((size_t)(sb + y) < h->host_act.size() ? h->host_act[sb + y] : -1) : sb + y;
             if (sc < 0) continue;
@@ -2013,7 +1962,7 @@ static int tree_newton_step_sel(hpf_handle* h, bool only_active) {
                 rocsolver_dgetrs(h->blas, rocblas_operation_none, m, 1, h->d_bM, m, h->d_bipiv, h->d_sel_g + (size_t)y * m, m) != rocblas_status_success)
                 return HPF_E_ROCSOLVER;
             if (hipMemcpyAsync(&pinfo, h->d_binfo, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-                h->last_detail = (int)hipGetLastError();
+                launch_status(h);                             // (last_detail <- the failed call's error)
                 return HPF_E_HIP;
             }
             if (pinfo != 0) {                             // exactly singular border system
@@ -2030,12 +1979,7 @@ static int tree_newton_step_sel(hpf_handle* h, bool only_active) {
     rc = tree_newton_step(h, only_active);
     h->tree_back_only = false;
     if (rc) return rc;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        return HPF_E_HIP;
-    }
-    return HPF_OK;
+    return launch_status(h);
 }
 
 int tree_newton_step_bordered(hpf_handle* h, bool only_active) {
@@ -2106,10 +2050,10 @@ int tree_newton_step_bordered(hpf_handle* h, bool only_active) {
         hipLaunchKernelGGL(k_border_absmax, dim3(1), dim3(1024), 0, st, m, (const double*)rwork, res);
         if (hipMemcpyAsync(&info, h->d_binfo, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipMemcpyAsync(hres, res, sizeof(double) * 2, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-            h->last_detail = (int)hipGetLastError();
+            launch_status(h);                             // (last_detail <- the failed call's error)
             return HPF_E_HIP;
         }
-        if (h->sw("HPF_BORDER_INFO"))
+        if (h->sw.border_info)
             fprintf(stderr, "hpf border system (m = %d, scenario %d): |rhs - M g| / |rhs| = %.2e, info %d\n", m, r, hres[1] > 0.0 ? hres[0] / hres[1] : 0.0, info);
         if (h->border_pivoting || info != 0 || !(hres[0] <= 1e-10 * hres[1]) || !(hres[1] < INFINITY)) {
             hipMemcpyAsync(h->d_bM, h->d_bM0, sizeof(double) * (size_t)m * m, hipMemcpyDeviceToDevice, st);       // the kept system, untouched
@@ -2119,7 +2063,7 @@ int tree_newton_step_bordered(hpf_handle* h, bool only_active) {
                 rocsolver_dgetrs(h->blas, rocblas_operation_none, m, 1, h->d_bM, m, h->d_bipiv, h->d_brhs, m) != rocblas_status_success)
                 return HPF_E_ROCSOLVER;
             if (hipMemcpyAsync(&info, h->d_binfo, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-                h->last_detail = (int)hipGetLastError();
+                launch_status(h);                             // (last_detail <- the failed call's error)
                 return HPF_E_HIP;
             }
         }
@@ -2134,12 +2078,7 @@ int tree_newton_step_bordered(hpf_handle* h, bool only_active) {
         hipLaunchKernelGGL(k_border_finish, dim3((unsigned)((std::max(cmax, VC) + 255) / 256)), dim3(256), 0, st, cmax, r, v0, VC, h->d_x,
                            h->d_pivflag);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        return HPF_E_HIP;
-    }
-    return HPF_OK;
+    return launch_status(h);
 }
 
 }  // namespace hpf

@@ -12,8 +12,17 @@
 
 #include "../../include/hpf.h"
 #include "hpf_assembly.hpp"
+#include "hpf_switches.hpp"
 
 namespace hpf {
+
+// form of the 2x2 algebra of the all-linear subtrees in a block-tree Newton step (Tree::lin_form, decided by the planner)
+enum LinForm {
+    LIN_ROOTS = 0,                    // uncontracted tree: one thread per (linear root, harmonic) walks its subtree (k_lin_factor / k_lin_back)
+    LIN_BUNDLE,                       // one-round-trip bundles, Tree::lin_np items per thread (k_lin_bundle_factor / _back)
+    LIN_TREE,                         // bundles of whole subtrees, every height in one launch (k_lin_tree_factor / _back)
+    LIN_LEVELS                        // one launch per height (k_lin_level_factor / _back)
+};
 
 enum { T_MISMATCH = 0, T_JACOBIAN = 1, T_SOLVE = 2, T_UPDATE = 3, T_BACK = 4, T_GJ = 5, T_GJ_DEV = 6, T_COUNT = 7 };
 
@@ -88,6 +97,8 @@ struct Tree {
     int* d_lb2cptr = nullptr;
     int* d_lb2clist = nullptr;
     int n_lin_bundles = 0;
+    LinForm lin_form = LIN_ROOTS;
+    bool chain_launches = false;      // the contracted chains get their own launches (k_chain_factor2 / k_chain_back2)
     int* d_lbrec = nullptr;
     int* d_lbptr = nullptr;
     int* d_crec = nullptr;            // chain headers
@@ -138,21 +149,7 @@ struct Tree {
 }  // namespace hpf
 
 struct hpf_handle {
-    // Build switches (A/B runs, diagnostics: "HPF_LAZY=0 HPF_SLEAF=1 ..."): the option string of hpf_create_opts, and -- ONLY when the process
-    // opts in with HPF_ENV_SWITCHES=1 (the test-suite, tools/) -- the process environment.  Without that opt-in nothing a handle computes
-    // depends on environment variables.
-    std::string opts;
-    bool env_switches = false;
-    const char* sw(const char* name) const {
-        const size_t ln = strlen(name);
-        size_t pos = 0;
-        while ((pos = opts.find(name, pos)) != std::string::npos) {
-            const bool starts = pos == 0 || opts[pos - 1] == ' ' || opts[pos - 1] == ',' || opts[pos - 1] == ';';
-            if (starts && pos + ln < opts.size() && opts[pos + ln] == '=') return opts.c_str() + pos + ln + 1;   // (atoi / the readers stop at the separator)
-            pos += ln;
-        }
-        return env_switches ? getenv(name) : nullptr;
-    }
+    hpf::Switches sw;                 // build switches (hpf_switches.hpp), parsed once by hpf_create
     hpf::Model M{};                   // device pointers
     int n = 0, m = 0, c = 0, Hn = 0, nnz = 0, n_dev = 0, coupled = 0, solver = 0, device = 0;
     int S_max = 0, S = 0;
@@ -190,8 +187,6 @@ struct hpf_handle {
     int* d_sel_info = nullptr;        // [sel_cap] weak / zero pivot of the block Gauss-Jordan solve, info of the unpivoted LU
     std::vector<unsigned long long> sel_res_host;
     std::vector<int> sel_info_host;
-    double border_piv_limit = 1e3;    // ... amplification of a 4 x 4 pivot block's inverse beyond which that border system goes to the pivoted LU
-    bool border_gj_mfma = true;       // ... its diagonal blocks inverted on the matrix cores (k_blk_invert_mfma; HPF_BORDER_GJ_MFMA=0: VALU)
     bool border_gj = false;           // border system by block Gauss-Jordan on the b x b grid (n_tb <= HPF_BORDER_GJ, default 96) instead of rocSOLVER's LU
     double *d_bB = nullptr;           // [n_tb][n_tb + 1][b][b] the border system in block layout, right-hand side in block column n_tb
     void *d_bgj_jobs = nullptr;       // its block-product jobs: per step the row scaling, then the elimination
@@ -205,14 +200,8 @@ struct hpf_handle {
     const char* plan_path = nullptr;  // hpf_tree_plan: file the planning run writes (instead of env HPF_TREE_DUMP) ...
     bool plan_only = false;           // ... and it stops before the uploads
     bool plan_written = false;
-    int gj_mode = 1;                  // BLOCK_TREE block inversion: 0 pivoted wave Gauss-Jordan (VALU, uncontracted tree), 1 MFMA static 4x4 blocks, NT waves per bus (hpf_quad.hpp)
+    int gj_mode = 1;                  // (initially sw.gj_mode) BLOCK_TREE block inversion: 0 pivoted wave Gauss-Jordan (VALU, uncontracted tree), 1 MFMA static 4x4 blocks, NT waves per bus (hpf_quad.hpp)
     double piv_limit = 1e10;          // static pivot order: amplification of a 4x4 pivot block's inverse beyond which a scenario is repeated with partial pivoting
-    int fuse_back = 1;                // HPF_FUSEBACK (read by hpf_create): 0 = the back sweep's batched launches after the last depth instead of inside the depths' launches
-    int fuse_back_max = 32;           // HPF_FUSEBACK_MAX (read by hpf_create): largest scenario group that takes the fused back sweep
-    int border_slot_cap = 1024;       // HPF_BORDER_SLOTS (read by hpf_create): cap of the virtual scenario slots of a meshed handle's bordered step
-    int fuse_levels = 1;              // HPF_FUSELEVEL (read by hpf_create): 0 = separate launches for the batched and the per-scenario workgroups of a level
-    int leafbatch = 1;                // HPF_LEAFBATCH (read by hpf_create): 0 = one workgroup per (leaf, scenario) instead of 16 scenarios per workgroup
-    int debug_ablate = 0;             // HPF_DEBUG_ABLATE: timing-only ablation of factor-kernel phases (results invalid)
 
     // model (device)
     int* d_rowrec = nullptr;          // [n][8] row records of the mismatch kernel (Model::rowrec)
@@ -286,7 +275,7 @@ struct hpf_handle {
     // pipelines on their own streams so that the latency-bound upper tree levels of one group overlap the others)
     hipStream_t cur_stream = nullptr;
     int cur_s0 = 0, cur_S = 0;
-    int n_groups = 4;
+    int n_groups = 4;                 // (initially sw.n_groups) "scenario_groups"
     hipStream_t gstream[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // groups 1..7 (group 0: the handle's stream, group_stream)
     hipEvent_t fork_ev = nullptr, join_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     rocblas_handle blas = nullptr;
@@ -301,6 +290,14 @@ struct hpf_handle {
 };
 
 namespace hpf {
+
+// status of the kernel launches since the last check: HPF_OK, or HPF_E_HIP with the HIP error in last_detail
+inline int launch_status(hpf_handle* h) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return HPF_OK;
+    h->last_detail = (int)e;
+    return HPF_E_HIP;
+}
 
 // Stream of scenario group g: group 0 runs on the handle's stream itself, so a step of G groups keeps G hardware queues busy, not G + 1 (the
 // runtime maps streams onto four queues; a fifth busy stream shares one and serialises two groups: 1.25 instead of 0.90 ms per step at G = 4)

@@ -268,12 +268,7 @@ int launch_leaf_batch(hpf_handle* h, const TreeDev& T, const int* nodes, int cou
     hipLaunchKernelGGL((k_leaf_batch<B>), grid, dim3(256), 0, h->cur_stream, h->M, T, nodes, 2 * h->Hn, active, h->cur_S, h->d_U,
                        h->d_E, h->d_fb, h->d_w, h->d_linA, h->d_C, h->d_H, h->d_chG, h->d_chH, h->d_chD, h->d_chy,
                        active_tree(h).d_lbimg, h->d_lfK, h->d_lfS, h->cur_s0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        return HPF_E_HIP;
-    }
-    return HPF_OK;
+    return launch_status(h);
 }
 
 // Back sweep of the constant-inverse leaves, 16 scenarios per workgroup:  x_k = w_k - S^-1 Drect^-1 t,  t = A(k,parent) x_parent,
@@ -393,12 +388,7 @@ int launch_leaf_back_batch(hpf_handle* h, const int* nodes, int count, const int
     const dim3 grid((unsigned)count, (unsigned)((h->cur_S + LB_SB - 1) / LB_SB));
     hipLaunchKernelGGL((k_leaf_back_batch<B>), grid, dim3(256), 0, h->cur_stream, h->M, nodes, 2 * h->Hn, active, h->cur_S, h->d_w,
                        h->d_x, h->d_H, active_tree(h).d_lbimg, h->d_lfK, h->d_lfS, h->cur_s0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        return HPF_E_HIP;
-    }
-    return HPF_OK;
+    return launch_status(h);
 }
 
 // Back sweep of the super-leaves, 16 scenarios per workgroup:  x_k = w_k - S_k^-1 M_k^-1 (Wd^-1 t),  t = A(k,parent) x_parent,
@@ -548,12 +538,7 @@ int launch_sleaf_back_batch(hpf_handle* h, const int* nodes, int count, const in
     const dim3 grid((unsigned)count, (unsigned)((h->cur_S + LB_SB - 1) / LB_SB));
     hipLaunchKernelGGL((k_sleaf_back_batch<B>), grid, dim3(256), 0, h->cur_stream, h->M, nodes, 2 * h->Hn, active, h->cur_S, h->d_w,
                        h->d_x, h->d_H, active_tree(h).d_sbimg, active_tree(h).d_lzimg, h->d_Z, h->d_lfS, h->cur_s0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        return HPF_E_HIP;
-    }
-    return HPF_OK;
+    return launch_status(h);
 }
 
 // Factor sweep of the super-leaves whose parent rebuilds their Schur complement (HPF_SLLAZY), 16 scenarios per workgroup: such a
@@ -987,11 +972,6 @@ int launch_sleaf_batch(hpf_handle* h, const TreeDev& T, const int* nodes, int co
     const dim3 grid((unsigned)count, (unsigned)((h->cur_S + LB_SB - 1) / LB_SB));
     hipLaunchKernelGGL((k_sleaf_batch<B>), grid, dim3(256), 0, h->cur_stream, h->M, T, nodes, 2 * h->Hn, active, h->cur_S, h->d_U,
                        h->d_E, h->d_fb, h->d_w, h->d_linA, h->d_C, h->d_H, h->d_I0, h->d_chG, h->d_chH, h->d_chD, h->d_chy,
-                       active_tree(h).d_sbimg, h->d_Z, h->d_lfK, h->d_lfS, h->cur_s0, h->d_dbg, h->debug_ablate);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        return HPF_E_HIP;
-    }
-    return HPF_OK;
+                       active_tree(h).d_sbimg, h->d_Z, h->d_lfK, h->d_lfS, h->cur_s0, h->d_dbg, h->sw.debug_ablate);
+    return launch_status(h);
 }

@@ -870,8 +870,7 @@ int launch_polar(hpf_handle* h) {
     const int count = FUND ? h->n : h->n * h->Hn;
     hipLaunchKernelGGL((k_polar<FUND>), grid2(count, h->S), dim3(TPB), 0, h->stream, count, h->n * h->Hn, h->Hn, h->d_Vm,
                        h->d_Va, h->d_U, h->d_E);
-    HIPCHK(hipGetLastError());
-    return HPF_OK;
+    return launch_status(h);
 }
 
 // the Newton step of the multi-wave block-tree sweep works on bus-major images of the mismatch and of the step
@@ -903,7 +902,7 @@ int launch_mismatch(hpf_handle* h, const int* active, bool stacked = true) {
         hipLaunchKernelGGL((k_mismatch<FUND>), xcd_grid(nbx, h->cur_S), dim3(TPB), lds, h->cur_stream, h->M, count, N, Nc,
                            active, h->d_U, h->d_P, h->d_Q, (stacked || !img) ? h->d_f : nullptr, h->d_errpart, h->errpart_stride, h->d_I0,
                            img ? h->d_fb : nullptr, tree_bst(h), h->cur_s0, h->cur_S, div_magic(h->Hn));
-        HIPCHK(hipGetLastError());
+        if (launch_status(h)) return HPF_E_HIP;
     }
     return HPF_OK;
 }
@@ -917,12 +916,12 @@ int launch_jacobian_dense(hpf_handle* h, const int* active) {
     const int total = (FUND ? 1 : h->Hn) * h->nnz;
     hipLaunchKernelGGL((k_jac_dense<FUND>), grid2(total, h->S), dim3(TPB), 0, h->stream, h->M, total, N, Nc,
                        h->J_elems_per_scen, active, h->d_erow, h->d_U, h->d_E, h->d_J);
-    HIPCHK(hipGetLastError());
+    if (launch_status(h)) return HPF_E_HIP;
     if (!FUND && h->coupled && h->n > h->m) {
         const int tot = (h->n - h->m) * h->Hn * h->Hn;
         hipLaunchKernelGGL(k_jac_cross_dense, grid2(tot, h->S), dim3(TPB), 0, h->stream, h->M, tot, N, Nc,
                            h->J_elems_per_scen, active, h->d_U, h->d_E, h->d_J);
-        HIPCHK(hipGetLastError());
+        if (launch_status(h)) return HPF_E_HIP;
     }
     return HPF_OK;
 }
@@ -973,8 +972,7 @@ int launch_update(hpf_handle* h, const int* active) {
     hipLaunchKernelGGL((k_update<FUND>), grid2(count, h->cur_S), dim3(TPB), 0, h->cur_stream, h->n, h->Hn, h->c, count,
                        h->n * h->Hn, N, Nc, active, h->d_f, h->d_Vm, h->d_Va, h->d_U, h->d_E,
                        busx ? h->d_x : nullptr, bw, h->cur_s0, div_magic(h->Hn));
-    HIPCHK(hipGetLastError());
-    return HPF_OK;
+    return launch_status(h);
 }
 
 // One Newton step: Jacobian at the current state, step = J^{-1} f into d_f.
@@ -1231,7 +1229,7 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
     int r = HPF_OK;
     const int n = h->n, Hn = h->Hn, S_max = h->S_max;
     const size_t count = (size_t)n * Hn;
-    const bool info = h->sw("HPF_QUEUE_INFO") != nullptr;
+    const bool info = h->sw.queue_info;
     const auto t_0 = std::chrono::steady_clock::now();
     auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
     double *qP = nullptr, *qQ = nullptr, *sVm = nullptr, *sVa = nullptr, *qVm = nullptr, *qVa = nullptr;
@@ -1303,7 +1301,7 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
         if (rr) return rr;
         hipLaunchKernelGGL(k_queue_first, dim3((unsigned)S_max), dim3(64), 0, h->stream, S_max, thresh, max_iter, newlist, base,
                            h->d_errpart, h->errpart_stride, err_parts<false>(h), h->d_err, h->d_active);
-        HIPCHK(hipGetLastError());
+        if (launch_status(h)) return HPF_E_HIP;
         HIPCHK(hipMemcpyAsync(h->h_act[buf], h->d_nactive, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(h->h_act[buf] + 1, next, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipEventRecord(h->poll_ev[buf], h->stream));
@@ -1442,21 +1440,14 @@ int hpf_create_opts(hpf_handle** out, const hpf_desc* d, const char* options) {
     h->Nc = d->n * d->Hn - 1;
     h->N = 2 * h->Nc - (d->c - 1);
     h->Nf = 2 * d->n - 1 - d->c;
-    if (options) h->opts = options;
-    if (const char* es = getenv("HPF_ENV_SWITCHES")) h->env_switches = atoi(es) != 0;
+    h->sw = parse_switches(options, env_switches_opted_in());
+    h->gj_mode = h->sw.gj_mode;
+    h->n_groups = h->sw.n_groups;
     // (dense systems beyond N * N = 2^31 -- 1 000 buses x 26 harmonics is already N = 51 998 -- go through rocSOLVER's 64-bit entry
     //  points, dense_solve; memory, 8 N^2 bytes per scenario, is what bounds them: HPF_E_NOMEM from the allocation)
-    if (const char* ab = h->sw("HPF_DEBUG_ABLATE")) h->debug_ablate = atoi(ab);
-    if (const char* gm = h->sw("HPF_GJ_MODE")) h->gj_mode = atoi(gm) ? 1 : 0;
-    if (const char* lb = h->sw("HPF_LEAFBATCH")) h->leafbatch = atoi(lb) ? 1 : 0;
-    if (const char* fl = h->sw("HPF_FUSELEVEL")) h->fuse_levels = atoi(fl) ? 1 : 0;
-    if (const char* fb = h->sw("HPF_FUSEBACK")) h->fuse_back = atoi(fb) ? 1 : 0;
-    if (const char* fm = h->sw("HPF_FUSEBACK_MAX")) h->fuse_back_max = atoi(fm);
-    if (const char* bs = h->sw("HPF_BORDER_SLOTS")) h->border_slot_cap = atoi(bs);
     if (hipSetDevice(d->device) != hipSuccess) return fail(HPF_E_HIP);
     if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) return fail(HPF_E_HIP);
     h->stream = h->own_stream;
-    if (const char* gs = h->sw("HPF_GROUPS")) h->n_groups = atoi(gs) < 1 ? 1 : (atoi(gs) > 8 ? 8 : atoi(gs));
     for (int g = 0; g < 8; ++g) {
         if (g > 0 && hipStreamCreateWithFlags(&h->gstream[g], hipStreamNonBlocking) != hipSuccess) return fail(HPF_E_HIP);   // (group 0: group_stream)
         if (hipEventCreateWithFlags(&h->join_ev[g], hipEventDisableTiming) != hipSuccess) return fail(HPF_E_HIP);
@@ -1594,7 +1585,7 @@ int hpf_set_state(hpf_handle* h, int n_scen, const double* Vm, const double* Va)
         HIPCHK(hipStreamSynchronize(h->stream));
     } else {
         hipLaunchKernelGGL(k_init_voltages, grid2(count, n_scen), dim3(TPB), 0, h->stream, h->Hn, count, h->d_Vm, h->d_Va);
-        HIPCHK(hipGetLastError());
+        if (launch_status(h)) return HPF_E_HIP;
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     h->state_set = true;
@@ -1697,7 +1688,7 @@ static int jacobian_csr_impl(hpf_handle* h, int scen, int32_t* indptr, int32_t* 
     const size_t so = (size_t)scen * h->n * h->Hn;
     hipLaunchKernelGGL(k_jcsr_fill, dim3((unsigned)((h->N + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, h->M, h->N, h->Nc, h->d_jptr,
                        h->d_U + so, h->d_E + so, indices ? h->d_jcol : (int*)nullptr, h->d_jval);
-    HIPCHK(hipGetLastError());
+    if (launch_status(h)) return HPF_E_HIP;
     HIPCHK(hipStreamSynchronize(h->stream));
     if (indptr) HIPCHK(hipMemcpy(indptr, h->d_jptr, sizeof(int32_t) * ((size_t)h->N + 1), hipMemcpyDeviceToHost));
     if (indices) HIPCHK(hipMemcpy(indices, h->d_jcol, sizeof(int32_t) * (size_t)h->jnnz, hipMemcpyDeviceToHost));

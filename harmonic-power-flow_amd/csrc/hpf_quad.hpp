@@ -1612,14 +1612,9 @@ int launch_factor_q2(hpf_handle* h, const TreeDev& T, const int* nodes, int coun
 #endif
     hipLaunchKernelGGL((k_factor_q<B, LEAF>), grid, dim3(64 * NT), 0, h->cur_stream, h->M, T, nodes,
                        2 * h->Hn, h->N, h->Nc, active, h->d_U, h->d_E, h->d_fb, h->d_Z, h->d_w, h->d_linA, h->d_C, h->d_H,
-                       h->d_I0, h->d_chG, h->d_chH, h->d_chD, h->d_chy, active_tree(h).d_Minv, h->d_lfK, h->d_lfS, h->d_dbg, h->debug_ablate, h->cur_s0,
+                       h->d_I0, h->d_chG, h->d_chH, h->d_chD, h->d_chy, active_tree(h).d_Minv, h->d_lfK, h->d_lfS, h->d_dbg, h->sw.debug_ablate, h->cur_s0,
                        h->d_pivflag, h->piv_limit, ts, count, (unsigned)h->cur_S);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        return HPF_E_HIP;
-    }
-    return HPF_OK;
+    return launch_status(h);
 }
 
 template <int B>
@@ -1633,10 +1628,5 @@ int launch_back_q(hpf_handle* h, const TreeDev& T, const int* nodes, int count, 
     hipLaunchKernelGGL((k_back_q<B>), dim3((unsigned)count, (unsigned)h->cur_S), dim3(64 * NT), 0, h->cur_stream, h->M, T, nodes,
                        2 * h->Hn, h->N, h->Nc, active, h->d_Z, h->d_w, h->d_x, (double*)nullptr, h->d_H, active_tree(h).d_Minv, h->d_lfK,
                        h->d_lfS, h->cur_s0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        return HPF_E_HIP;
-    }
-    return HPF_OK;
+    return launch_status(h);
 }

@@ -232,9 +232,10 @@ int  hpf_debug_stamps(hpf_handle* h, long long* out, int count);
  * on the handle's own stream (hpf_set_stream), the others on streams of the handle.  The runtime maps streams onto FOUR hardware queues: with a fifth
  * stream busy at the same time (the application's own work during a solve) two groups share a queue and serialise (1.25 instead of 0.90 ms per
  * step at the benchmark shape) -- such an application sets 3.
- * Switches read by hpf_create (diagnostics, A/B runs; from the option string of hpf_create_opts, and from the environment only with
- * HPF_ENV_SWITCHES=1; HPF_HOST_THREADS -- host threads of the tree planner, no effect on results -- is always read from the environment;
- * HPF_TREE_DUMP takes a path: environment only): HPF_DEBUG_ABLATE (timing-only ablation of factor-kernel phases: results INVALID), HPF_GJ_MODE=0
+ * Switches read by hpf_create (diagnostics, A/B runs; from the option string of hpf_create_opts -- the first occurrence of a name counts --, and
+ * from the environment only with HPF_ENV_SWITCHES=1; HPF_HOST_THREADS -- host threads of the tree planner, no effect on results -- is always read
+ * from the environment; HPF_TREE_DUMP takes a path: environment only, ignored in an option string; the one list of them with their defaults is
+ * struct hpf::Switches in csrc/hpf_switches.hpp): HPF_DEBUG_ABLATE (timing-only ablation of factor-kernel phases: results INVALID), HPF_GJ_MODE=0
  * (the pivoted variant for every solve of the handle), HPF_LAZY=0 builds the elimination tree without lazy leaves (every
  * leaf writes its Schur complement; 1: only leaves directly under their dense parent), HPF_SLEAF=0 sends the nonlinear buses
  * whose dense children are all lazy leaves (super-leaves: bordered low-rank inverse) through Gauss-Jordan like every other bus,

@@ -778,3 +778,10 @@ def test_build_switches_come_from_the_option_string_and_the_environment_only_on_
     monkeypatch.setenv("HPF_ENV_SWITCHES", "0")
     assert census() == default                                                    # ... and ignored without the opt-in
     assert census("HPF_LAZY=0 HPF_COMPRESS=0") == by_string                       # (the option string always counts)
+    # HPF_TREE_DUMP takes a path and is read from the environment only: in an option string it is ignored (no file, not even one named after the
+    # rest of the string), and the switches after it still apply
+    dump_dir = tmp_path / "dump"
+    dump_dir.mkdir()
+    monkeypatch.delenv("HPF_TREE_DUMP", raising=False)
+    assert census("HPF_TREE_DUMP=%s HPF_LAZY=0" % (dump_dir / "plan.txt"))["lazy_leaves"] == 0
+    assert os.listdir(dump_dir) == []

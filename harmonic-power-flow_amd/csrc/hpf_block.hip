@@ -902,6 +902,50 @@ int launch_level_back(hpf_handle* h, const TreeDev& T, const int* sl_nodes, int 
     return launch_status(h);
 }
 
+// Back sweep as a tree walk (blocks of 52, Tree::walk_*): one workgroup per (work list, scenario) walks the list's Gauss-Jordan buses in
+// order, with workgroup barriers only -- the trunk launch first, then the branch launch, on the same stream.  While bus i computes, bus
+// i + 1's inverse, w and coupling entries are already on their way (back_q_load); the x of the walked buses stays in an LDS ring, so the
+// barriers between buses order LDS alone and leave those loads in flight.
+template <int B>
+__global__ __launch_bounds__(64 * ((B + 16) / 16)) void k_back_walk(
+    Model M, TreeDev T, const int* __restrict__ recs, const int* __restrict__ slots, const int* __restrict__ list_ptr, int b, int N, int Nc,
+    const int* __restrict__ active, const double* __restrict__ Zall, const double* __restrict__ wall, double* __restrict__ xall,
+    const double* __restrict__ Hall, const double* __restrict__ Minv, const double* __restrict__ lfK, const double* __restrict__ lfS, int s0) {
+    __shared__ double xl[WALK_SLOTS + 2][B];      // ring of the walked buses' x | x_parent, x_c read from HBM
+    const int beg = list_ptr[blockIdx.x], end = list_ptr[blockIdx.x + 1], tid = threadIdx.x;
+    if (beg >= end) return;
+    BackQIn<B> cur, nxt;
+    back_q_load<B>(cur, beg, blockIdx.y, M, T, recs, b, active, Zall, wall, Hall, Minv, s0);
+    if (cur.s < 0) return;                        // frozen / empty slot (block-uniform)
+    const double* xs = xall + (size_t)cur.s * M.n * B;
+    for (int i = beg; i < end; ++i) {
+        const int2 sl = reinterpret_cast<const int2*>(slots)[i];
+        const int par = cur.kp.y, crole = cur.kp.w >> 28;
+        // an x the ring does not hold: written by an earlier launch, or by this very thread (tid < B) at least WALK_SLOTS buses ago
+        if (tid < B) {
+            if (par >= 0 && sl.x < 0) xl[WALK_SLOTS][tid] = xs[(size_t)par * B + tid];
+            if (crole == 1 && sl.y < 0) xl[WALK_SLOTS + 1][tid] = xs[(size_t)T.comp_child[cur.kp.w & 0x0fffffff] * B + tid];
+        }
+        lds_barrier();
+        if (i + 1 < end) back_q_load<B>(nxt, i + 1, blockIdx.y, M, T, recs, b, active, Zall, wall, Hall, Minv, s0);
+        const double x = back_q_compute<B>(cur, M, T, b, N, Nc, xall, (double*)nullptr, lfK, lfS, xl[sl.x < 0 ? WALK_SLOTS : sl.x],
+                                           xl[sl.y < 0 ? WALK_SLOTS + 1 : sl.y]);
+        if (tid < B) xl[(i - beg) % WALK_SLOTS][tid] = x;
+        lds_barrier();
+        cur = nxt;
+    }
+}
+
+// lists list0 .. list0 + count - 1 of the tree's walk
+template <int B>
+int launch_back_walk(hpf_handle* h, const Tree& tr, const TreeDev& T, int list0, int count, const int* active) {
+    constexpr int NT = (B + 16) / 16;
+    hipLaunchKernelGGL((k_back_walk<B>), dim3((unsigned)count, (unsigned)h->cur_S), dim3(64 * NT), 0, h->cur_stream, h->M, T, tr.d_walk_rec,
+                       tr.d_walk_slot, tr.d_walk_ptr + list0, 2 * h->Hn, h->N, h->Nc, active, h->d_Z, h->d_w, h->d_x, h->d_H, tr.d_Minv,
+                       h->d_lfK, h->d_lfS, h->cur_s0);
+    return launch_status(h);
+}
+
 // =============================================================================================================
 // Meshed networks on the block-tree path: "bordered Newton step".
 // The admittance pattern = BFS spanning tree + k loop-closing lines (ties).  With J_t = the Jacobian without the ties' off-
@@ -1025,7 +1069,7 @@ static void tree_free_one(Tree& T) {
                     T.d_child_mid, T.d_lin, T.d_lin_ptr, T.d_lin_post, T.d_all_ptr, T.d_all_post, T.d_fdesc, T.d_child3,
                     T.d_bdesc, T.d_dchild, T.d_chain_ptr, T.d_chain_nodes, T.d_chain_ch, T.d_Minv, T.d_lrec, T.d_crec, T.d_cnode, T.d_arec,
                     T.d_lzrec, T.d_lzimg, T.d_lbimg, T.d_bleaf, T.d_bsleaf, T.d_bsleaf_dep, T.d_sbimg, T.d_lbrec, T.d_lbptr, T.d_lb2rec, T.d_lb2x, T.d_lb2ptr, T.d_lb2cptr, T.d_lb2clist,
-                    T.d_comp_child};
+                    T.d_comp_child, T.d_walk_ptr, T.d_walk_rec, T.d_walk_slot};
     for (void* p : ptrs)
         if (p) hipFree(p);
 }
@@ -1285,11 +1329,25 @@ static int back_batched(hpf_handle* h, const Tree& T, const int* active) {
     return T.n_bleaf > 0 ? launch_leaf_back_batch<BW>(h, T.d_bleaf, T.n_bleaf, active) : HPF_OK;
 }
 
+// the Gauss-Jordan buses of the back sweep in two tree walks (k_back_walk) instead of one launch per depth; its batched workgroups
+// (bordered buses, constant-inverse leaves) follow in back_batched
+static bool back_walks(const hpf_handle* h, const Tree& T, int BW) {
+    return h->sw.back_walk && h->cur_S >= h->sw.back_walk_min && h->cur_S <= h->sw.back_walk_max && h->sw.leafbatch && h->has_ctree && h->gj_mode == 1 && BW == 52 &&
+           T.walk_ptr.size() == (size_t)T.walk_lists + 2;
+}
+
 static int back_sweep(hpf_handle* h, const Tree& T, const TreeDev& td, const int* active, int Bst) {
     ScopedTimer tb(h, T_BACK);
     const int BW = wave_block_size(2 * h->Hn);
-    const bool fused_back = back_is_fused(h, T, BW);
-    for (int dl = 0; dl < T.n_depths; ++dl) {
+    const bool walk = back_walks(h, T, BW);
+    const bool fused_back = !walk && back_is_fused(h, T, BW);
+    if (walk) {
+        int r = launch_back_walk<52>(h, T, td, 0, 1, active);
+        if (!r && T.walk_lists > 0) r = launch_back_walk<52>(h, T, td, 1, T.walk_lists, active);
+        if (r) return r;
+        ++h->n_back_walks;
+    }
+    for (int dl = 0; dl < (walk ? 0 : T.n_depths); ++dl) {
         const int cnt = T.dep_ptr[dl + 1] - T.dep_ptr[dl];
         if (cnt == 0) continue;
         const int* nodes = T.d_dep_nodes + T.dep_ptr[dl];

@@ -31,6 +31,10 @@ struct TimedSpan {
     hipEvent_t e0, e1;
 };
 
+// back-sweep tree walk: at most WALK_LISTS subtree lists (x 32 scenarios: one workgroup per CU), an LDS ring of the x of the last
+// WALK_SLOTS buses a workgroup walked
+constexpr int WALK_LISTS = 8, WALK_SLOTS = 32;
+
 // Feeder-tree description for the BLOCK_TREE solver (host copies + device copies).
 struct Tree {
     int n_levels = 0;                 // elimination levels (by height, leaves first)
@@ -137,6 +141,17 @@ struct Tree {
     int n_comp = 0;
     std::vector<int> comp_v, comp_c;
     int* d_comp_child = nullptr;      // [n_comp] c of compress step i (k_back_q: x_v needs x_c)
+    // back-sweep tree walk (k_back_walk, blocks of 52, leaf batching on): the Gauss-Jordan buses the back sweep's depth launches would take,
+    // as work lists of Tree::d_bdesc records -- list 0 the trunk (the top walk_depth depths, one launch), lists 1..walk_lists the subtrees
+    // below it (one launch), each root-first, with the LDS ring slots of the x of its parent and of its pending child c (-1: from HBM)
+    int walk_lists = 0;               // branch lists (0: no schedule)
+    int walk_depth = 0;               // depths in the trunk
+    std::vector<int> walk_ptr;        // [walk_lists + 2] list l: records walk_ptr[l] .. walk_ptr[l + 1]
+    std::vector<int> walk_rec;        // [][4] the d_bdesc records
+    std::vector<int> walk_slot;       // [][2] ring slot of x_parent, of x_c
+    int* d_walk_ptr = nullptr;
+    int* d_walk_rec = nullptr;
+    int* d_walk_slot = nullptr;
     double plan_ms = 0.0;             // host time of tree_build_into up to the uploads
     double flops_per_solve = 0.0;     // factor sweep + back sweep
     double flops_factor = 0.0;        // factor sweep only (k_tree_factor, all levels)
@@ -247,6 +262,7 @@ struct hpf_handle {
     hpf::Tree tree;                   // elimination tree as the network gives it (single-wave / generic kernels, pf)
     hpf::Tree ctree;                  // the same with pass-through buses contracted (multi-wave kernels, gj_mode 1)
     bool has_ctree = false;
+    long long n_back_walks = 0;       // back sweeps (scenario group x Newton step) whose Gauss-Jordan buses went through k_back_walk (hpf_tree_census[15])
     int auto_repivot = 1;             // hpf_solve repeats scenarios flagged by the static-pivot monitor with partial pivoting
     int* h_act[2] = {nullptr, nullptr};          // pinned copies of d_active (hpf_solve looks at chunk c - 1 while chunk c runs)
     hipEvent_t poll_ev[2] = {nullptr, nullptr};

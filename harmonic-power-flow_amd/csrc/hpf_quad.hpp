@@ -1467,24 +1467,79 @@ __global__ __launch_bounds__(64 * ((B + 16) / 16), (B > 52 ? (LEAF ? HPF_Q100L_O
                            chH, chD, chy, Minv, lfK, lfS, dbg, ablate, s0, pivflag, piv_limit, tstamp);
 }
 
+// barrier of a workgroup that orders its LDS accesses only: the outstanding global loads (the next bus's prefetched tiles in
+// k_back_walk) stay in flight, unlike __syncthreads(), whose release waits for every memory access of the wave
+__device__ __forceinline__ void lds_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
 // root -> leaves: x_k = w_k - D_k^{-1} (A(k,parent) x_parent), inverse in tile layout; wave wv multiplies its tile column,
 // the partial row sums meet in LDS.  Constant-inverse leaves keep no inverse in HBM:  D^-1 t = S^-1 (M t - Mc K (Mr t))  with
 // the per-model M (tile layout, L2 / Infinity Cache), the Woodbury core K and S^-1 left by the factor kernel.
+// Two steps: back_q_load fetches what does not depend on x_parent (k_back_walk issues it one bus ahead), back_q_compute the rest.
 template <int B>
-__device__ __forceinline__ void back_q_body(
-    const int bx_, const int by_, const Model& M, const TreeDev& T, const int* __restrict__ nodes, int b, int N, int Nc, const int* __restrict__ active,
-    const double* __restrict__ Zall, const double* __restrict__ wall, double* __restrict__ xall, double* __restrict__ step,
-    const double* __restrict__ Hall, const double* __restrict__ Minv, const double* __restrict__ lfK,
-    const double* __restrict__ lfS, int s0) {
+struct BackQIn {
+    static constexpr int NT = (B + 16) / 16;
+    int4 kp;                          // Tree::d_bdesc: (bus, parent, leaf slot + 1, 0)
+    int s;                            // scenario (-1: frozen / empty slot)
+    double x;                         // w_k (tid < B)
+    double zr[NT * 4];                // the lane's entries of the stored inverse (or of the leaf's per-model image)
+    double hk0, hk1, h20, h21;        // the lane's entries of A(k,parent) (and of A(k,c), compress role 1)
+};
+
+template <int B>
+__device__ __forceinline__ void back_q_load(
+    BackQIn<B>& in, const int bx_, const int by_, const Model& M, const TreeDev& T, const int* __restrict__ nodes, int b,
+    const int* __restrict__ active, const double* __restrict__ Zall, const double* __restrict__ wall, const double* __restrict__ Hall,
+    const double* __restrict__ Minv, int s0) {
     constexpr int NT = (B + 16) / 16;
     constexpr size_t CT = (size_t)NT * NT * 256;
     const int s = active ? active[by_ + s0] : (int)by_ + s0;   // slot -> scenario (active list; -1: frozen / empty slot)
+    in.s = s;
     if (s < 0) return;
-    const int4 kp = reinterpret_cast<const int4*>(nodes)[bx_];          // Tree::d_bdesc: (bus, parent, leaf slot + 1, 0)
+    const int4 kp = reinterpret_cast<const int4*>(nodes)[bx_];
+    in.kp = kp;
     const int k = kp.x, par = kp.y, cleaf = kp.z;
-    // compress steps (tree_build_into): role 1 = bus eliminated before its pending child c: x_k = w_k - D_k^-1 (A(k,p) x_p + A(k,c) x_c), it
-    // comes AFTER c; role 2 = such a child: its coupling block with the parent p is the dense Hd = A'(k,p) the compress step left
     const int crole = kp.w >> 28, cinfo = kp.w & 0x0fffffff;
+    const int tid = threadIdx.x, lane = tid & 63, lg = lane >> 4, jj = lane & 15;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = M.n, Hn = M.Hn;
+    in.x = 0.0;
+    if (tid < B) in.x = wall[((size_t)s * n + k) * B + tid];
+    if (par >= 0) {
+        if (cleaf) {                                              // per-model image, same tile-image layout
+            TileIO<B>::load(Minv + (size_t)(cleaf - 1) * CT, wv, lg, jj, in.zr);
+        } else {
+            TileIO<B>::load(Zall + ((size_t)s * n + k) * CT, wv, lg, jj, in.zr);
+        }
+        const int col = 16 * wv + jj, p = col >> 1, t1 = col & 1;
+        if (crole != 2 && col < b) {
+            const double* hk = Hall + ((size_t)s * n + k) * Hn * 4 + p * 4 + t1 * 2;
+            in.hk0 = hk[0];
+            in.hk1 = hk[1];
+            if (crole == 1) {
+                const double* h2 = T.cH2 + ((size_t)s * T.n_comp + cinfo) * Hn * 4 + p * 4 + t1 * 2;
+                in.h20 = h2[0];
+                in.h21 = h2[1];
+            }
+        }
+    }
+}
+
+// compress steps (tree_build_into): role 1 = bus eliminated before its pending child c: x_k = w_k - D_k^-1 (A(k,p) x_p + A(k,c) x_c), it
+// comes AFTER c; role 2 = such a child: its coupling block with the parent p is the dense Hd = A'(k,p) the compress step left.
+// xp / xc: the x of the parent / of c -- in HBM (xall), or in LDS where k_back_walk keeps the x of the buses it walked.  Returns x_k (tid < B).
+template <int B>
+__device__ __forceinline__ double back_q_compute(
+    const BackQIn<B>& in, const Model& M, const TreeDev& T, int b, int N, int Nc, double* __restrict__ xall, double* __restrict__ step,
+    const double* __restrict__ lfK, const double* __restrict__ lfS, const double* xp, const double* xc) {
+    constexpr int NT = (B + 16) / 16;
+    constexpr size_t CT = (size_t)NT * NT * 256;
+    const int s = in.s;
+    const int k = in.kp.x, par = in.kp.y, cleaf = in.kp.z;
+    const int crole = in.kp.w >> 28, cinfo = in.kp.w & 0x0fffffff;
     const int tid = threadIdx.x, lane = tid & 63, lg = lane >> 4, jj = lane & 15;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = M.n, c = M.c, Hn = M.Hn;
@@ -1492,46 +1547,33 @@ __device__ __forceinline__ void back_q_body(
     constexpr int RP = 16 * NT > 64 ? 16 * NT : 64;
     __shared__ double part[NT][RP];
     __shared__ double mcl[RP * 2], zl[RP];
-    double x = 0.0;
-    if (tid < B) x = wall[((size_t)s * n + k) * B + tid];
+    double x = in.x;
     if (par >= 0) {
-        double zr[NT * 4];
-        if (cleaf) {                                              // per-model image, same tile-image layout
-            TileIO<B>::load(Minv + (size_t)(cleaf - 1) * CT, wv, lg, jj, zr);
-        } else {
-            TileIO<B>::load(Zall + ((size_t)s * n + k) * CT, wv, lg, jj, zr);
-        }
         const int col = 16 * wv + jj, p = col >> 1, t1 = col & 1;
         double tv = 0.0;
         if (crole == 2) {                                         // t = Hd x_p: a dense product, row sums like the inverse's below
             double hr[NT * 4];
             TileIO<B>::load(T.cF + (((size_t)s * T.n_comp + cinfo) * 3 + 2) * CT, wv, lg, jj, hr);
-            const double xpc = col < b ? xs[(size_t)par * B + col] : 0.0;
+            const double xpc = col < b ? xp[col] : 0.0;
 #pragma unroll
             for (int e = 0; e < NT * 4; ++e)
                 if (16 * (e >> 2) + 4 * (e & 3) < B) {
                     const double r = row_sum16(hr[e] * xpc);
                     if (jj == 0) part[wv][16 * (e >> 2) + lg + 4 * (e & 3)] = r;
                 }
-            __syncthreads();
+            lds_barrier();
             if (tid < B) {
                 double acc = part[0][tid];
 #pragma unroll
                 for (int w2 = 1; w2 < NT; ++w2) acc += part[w2][tid];
                 zl[tid] = acc;
             }
-            __syncthreads();
+            lds_barrier();
             tv = col < b ? zl[col] : 0.0;
-            __syncthreads();                                      // (part / zl are reused below)
+            lds_barrier();                                        // (part / zl are reused below)
         } else if (col < b) {
-            const double* hk = Hall + ((size_t)s * n + k) * Hn * 4 + p * 4 + t1 * 2;
-            const double* xp = xs + (size_t)par * B;
-            tv = fma(hk[1], xp[2 * p + 1], hk[0] * xp[2 * p]);
-            if (crole == 1) {
-                const double* h2 = T.cH2 + ((size_t)s * T.n_comp + cinfo) * Hn * 4 + p * 4 + t1 * 2;
-                const double* xc = xs + (size_t)T.comp_child[cinfo] * B;
-                tv += fma(h2[1], xc[2 * p + 1], h2[0] * xc[2 * p]);
-            }
+            tv = fma(in.hk1, xp[2 * p + 1], in.hk0 * xp[2 * p]);
+            if (crole == 1) tv += fma(in.h21, xc[2 * p + 1], in.h20 * xc[2 * p]);
         }
         if (cleaf && tid < 2) zl[tid] = tv;                        // t[0], t[1]
         const double tvs = (cleaf && col < 2) ? 0.0 : tv;          // leaf image: columns 0, 1 hold the border, not the inverse
@@ -1539,11 +1581,11 @@ __device__ __forceinline__ void back_q_body(
 #pragma unroll
         for (int e = 0; e < NT * 4; ++e)
             if (16 * (e >> 2) + 4 * (e & 3) < B) {
-                const double r = row_sum16(zr[e] * tvs);
+                const double r = row_sum16(in.zr[e] * tvs);
                 if (jj == 0) part[wv][16 * (e >> 2) + lg + 4 * (e & 3)] = r;
-                if (cleaf && wv == 0 && jj < 2) mcl[(16 * (e >> 2) + lg + 4 * (e & 3)) * 2 + jj] = zr[e];      // M[:, 0:2]
+                if (cleaf && wv == 0 && jj < 2) mcl[(16 * (e >> 2) + lg + 4 * (e & 3)) * 2 + jj] = in.zr[e];      // M[:, 0:2]
             }
-        __syncthreads();
+        lds_barrier();
         double acc = 0.0;
         if (tid < B) {
             acc = part[0][tid];
@@ -1557,9 +1599,9 @@ __device__ __forceinline__ void back_q_body(
                 t0 = zl[0];
                 t1v = zl[1];
             }
-            __syncthreads();
+            lds_barrier();
             if (tid < 2) zl[tid] = acc + (tid == 0 ? t0 : t1v);   // [I Lr] t
-            __syncthreads();
+            lds_barrier();
             if (tid < B) {
                 const double* kk = lfK + ((size_t)s * n + k) * 12;
                 const double u0 = fma(kk[1], zl[1], kk[0] * zl[0]), u1 = fma(kk[3], zl[1], kk[2] * zl[0]);     // (c0 + D)^-1 [I Lr] t
@@ -1567,9 +1609,9 @@ __device__ __forceinline__ void back_q_body(
                 const double c1r = tid < 2 ? (tid == 1 ? 1.0 : 0.0) : mcl[tid * 2 + 1];
                 acc = fma(c1r, u1, fma(c0r, u0, tid < 2 ? 0.0 : acc));
             }
-            __syncthreads();
+            lds_barrier();
             if (tid < B) zl[tid] = acc;                           // Drect^-1 t
-            __syncthreads();
+            lds_barrier();
             if (tid < B) {
                 const double* si = lfS + (((size_t)s * n + k) * Hn + (tid >> 1)) * 4 + 2 * (tid & 1);
                 acc = (tid >> 1) < Hn ? fma(si[1], zl[tid | 1], si[0] * zl[tid & ~1]) : acc;                    // S_q^-1 from the left
@@ -1589,6 +1631,24 @@ __device__ __forceinline__ void back_q_body(
             }
         }
     }
+    return x;
+}
+
+// one bus of one scenario, x_parent (and x_c) from HBM
+template <int B>
+__device__ __forceinline__ void back_q_body(
+    const int bx_, const int by_, const Model& M, const TreeDev& T, const int* __restrict__ nodes, int b, int N, int Nc, const int* __restrict__ active,
+    const double* __restrict__ Zall, const double* __restrict__ wall, double* __restrict__ xall, double* __restrict__ step,
+    const double* __restrict__ Hall, const double* __restrict__ Minv, const double* __restrict__ lfK,
+    const double* __restrict__ lfS, int s0) {
+    BackQIn<B> in;
+    back_q_load<B>(in, bx_, by_, M, T, nodes, b, active, Zall, wall, Hall, Minv, s0);
+    if (in.s < 0) return;
+    const double* xs = xall + (size_t)in.s * M.n * B;
+    const int par = in.kp.y, crole = in.kp.w >> 28;
+    const double* xp = par >= 0 ? xs + (size_t)par * B : nullptr;
+    const double* xc = crole == 1 ? xs + (size_t)T.comp_child[in.kp.w & 0x0fffffff] * B : nullptr;
+    back_q_compute<B>(in, M, T, b, N, Nc, xall, step, lfK, lfS, xp, xc);
 }
 
 template <int B>

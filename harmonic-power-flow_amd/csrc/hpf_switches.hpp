@@ -22,6 +22,10 @@ struct Switches {
     bool fuse_levels = true;          // HPF_FUSELEVEL=0: separate launches for the batched and the per-scenario workgroups of a level
     bool fuse_back = true;            // HPF_FUSEBACK=0: the back sweep's batched launches after the last depth instead of inside the depths' launches
     int fuse_back_max = 32;           // HPF_FUSEBACK_MAX: largest scenario group that takes the fused back sweep
+    bool back_walk = true;            // HPF_BACKWALK=0: the Gauss-Jordan buses of the back sweep in one launch per depth instead of two tree walks
+    int back_walk_min = 16;           // HPF_BACKWALK_MIN: smallest scenario group that takes the tree walk (at 1 - 4 its serial per-bus steps lose
+                                      // ~8 % of the step to the few short depth launches; at 16 the two tie)
+    int back_walk_max = 256;          // HPF_BACKWALK_MAX: largest scenario group that takes the tree walk (measured up to 256: a tie above 32)
     int border_slot_cap = 1024;       // HPF_BORDER_SLOTS: cap of the virtual scenario slots of a meshed handle's bordered step
     // the tree planner
     bool lintree = true;              // HPF_LINTREE=0: the 2x2 algebra of the linear subtrees in one launch per height
@@ -75,6 +79,9 @@ inline Switches parse_switches(const char* options, bool env_opt_in) {
     flag("HPF_FUSELEVEL", s.fuse_levels);
     flag("HPF_FUSEBACK", s.fuse_back);
     integer("HPF_FUSEBACK_MAX", s.fuse_back_max);
+    flag("HPF_BACKWALK", s.back_walk);
+    integer("HPF_BACKWALK_MIN", s.back_walk_min);
+    integer("HPF_BACKWALK_MAX", s.back_walk_max);
     integer("HPF_BORDER_SLOTS", s.border_slot_cap);
     flag("HPF_LINTREE", s.lintree);
     flag("HPF_LINBUNDLE", s.linbundle);

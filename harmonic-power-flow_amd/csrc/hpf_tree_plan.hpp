@@ -1225,6 +1225,88 @@ static int tree_build_into(hpf_handle* h, const hpf_desc* d, Tree& T, bool contr
         bdesc[(size_t)pos * 4 + 2] = cleaf_of[kb] + 1;
         bdesc[(size_t)pos * 4 + 3] = comp_role[kb] ? ((comp_role[kb] << 28) | comp_idx[kb]) : 0;
     }
+    // back-sweep tree walk (k_back_walk): the records the depth launches give k_back_q (behind a depth's leaves and batched bordered
+    // buses, which go to back_batched after the walk: nothing of the dense tree hangs below them).  A bus waits for its parent and, in
+    // compress role 1, for its pending child c; both come earlier in depth order.  The trunk holds the top depths, down to the first
+    // depth below which at least WALK_LISTS subtrees hang; the subtrees go into at most WALK_LISTS lists (largest first, to the list
+    // with the fewest buses), every list in depth order.
+    T.walk_lists = T.walk_depth = 0;
+    T.walk_ptr.clear();
+    T.walk_rec.clear();
+    T.walk_slot.clear();
+    if (contract && h->sw.leafbatch && T.n_depths > 0 && (int)T.dep_nleaf.size() >= T.n_depths) {
+        std::vector<int> wpos(n, -1), wdep(n, -1), wpar(n, -1), members;
+        for (int dl = 0; dl < T.n_depths; ++dl)
+            for (int pos = T.dep_ptr[dl] + (dl > 0 ? T.dep_nleaf[dl] : 0); pos < T.dep_ptr[dl + 1]; ++pos) {
+                const int kb = T.dep_nodes[pos];
+                wpos[kb] = pos;
+                wdep[kb] = dl;
+                wpar[kb] = comp_role[kb] == 1 ? comp_child[kb] : pard[kb];
+                members.push_back(kb);
+            }
+        bool ok = true;                               // (every bus the walk waits for is walked itself, and earlier)
+        for (int kb : members) ok = ok && (wpar[kb] < 0 || (wpos[wpar[kb]] >= 0 && wpos[wpar[kb]] < wpos[kb])) && (pard[kb] < 0 || wpos[pard[kb]] >= 0);
+        int cut = T.n_depths, best = -1;              // trunk = depths < cut
+        for (int D = 1; ok && D < T.n_depths; ++D) {
+            int roots = 0;
+            for (int kb : members) roots += wdep[kb] >= D && wpar[kb] >= 0 && wdep[wpar[kb]] < D;
+            if (roots > best) {
+                best = roots;
+                cut = D;
+            }
+            if (roots >= WALK_LISTS) break;
+        }
+        if (ok) {
+            std::vector<int> top(n, -1);              // subtree root of a branch bus
+            std::vector<std::vector<int>> subs;
+            std::vector<int> trunk;
+            for (int kb : members) {                  // (members are in depth order: a bus after the one it waits for)
+                if (wdep[kb] < cut) {
+                    trunk.push_back(kb);
+                    continue;
+                }
+                const int w = wpar[kb];
+                if (w >= 0 && wdep[w] >= cut) {
+                    top[kb] = top[w];
+                } else {
+                    top[kb] = (int)subs.size();
+                    subs.emplace_back();
+                }
+                subs[top[kb]].push_back(kb);
+            }
+            const int L = (int)std::min<size_t>(subs.size(), (size_t)WALK_LISTS);
+            std::vector<int> order(subs.size());
+            for (size_t i = 0; i < subs.size(); ++i) order[i] = (int)i;
+            std::stable_sort(order.begin(), order.end(), [&](int a, int b2) { return subs[a].size() > subs[b2].size(); });
+            std::vector<std::vector<int>> lists(L);
+            for (int si : order) {
+                int lm = 0;
+                for (int l = 1; l < L; ++l)
+                    if (lists[l].size() < lists[lm].size()) lm = l;
+                lists[lm].insert(lists[lm].end(), subs[si].begin(), subs[si].end());
+            }
+            lists.insert(lists.begin(), trunk);
+            T.walk_ptr.assign(1, 0);
+            for (auto& li : lists) {
+                std::sort(li.begin(), li.end(), [&](int a, int b2) { return wpos[a] < wpos[b2]; });
+                for (int q = 0; q < (int)li.size(); ++q) {
+                    const int kb = li[q];
+                    auto ring = [&](int dep) {            // ring slot of the x of a bus this list walked fewer than WALK_SLOTS records before
+                        if (dep < 0) return -1;
+                        for (int q2 = q - 1; q2 >= 0 && q - q2 < WALK_SLOTS; --q2)
+                            if (li[q2] == dep) return q2 % WALK_SLOTS;
+                        return -1;
+                    };
+                    T.walk_rec.insert(T.walk_rec.end(), &bdesc[(size_t)wpos[kb] * 4], &bdesc[(size_t)wpos[kb] * 4] + 4);
+                    T.walk_slot.push_back(ring(pard[kb]));
+                    T.walk_slot.push_back(comp_role[kb] == 1 ? ring(comp_child[kb]) : -1);
+                }
+                T.walk_ptr.push_back((int)T.walk_rec.size() / 4);
+            }
+            T.walk_lists = L;
+            T.walk_depth = cut;
+        }
+    }
     {
         int nc = 0, nb = 0, nn = 0;
         for (int i = 0; i < n; ++i) {
@@ -1336,6 +1418,15 @@ static int tree_build_into(hpf_handle* h, const hpf_desc* d, Tree& T, bool contr
             if (h->n_ties > 0)
                 fprintf(fp, "# meshed: %d loop-closing lines, %d endpoint buses, border %d unknowns, bordered step %s\n", h->n_ties, h->n_tb, h->m_border,
                         h->mesh_sel ? "factor-once" : "virtual sweeps");
+            if (!T.walk_ptr.empty()) {              // the back-sweep walk: trunk (list 0) and branch lists, bus ids in walk order
+                fprintf(fp, "# walk: %d trunk depths, %d branch lists\n", T.walk_depth, T.walk_lists);
+                for (size_t l = 0; l + 1 < T.walk_ptr.size(); ++l) {
+                    fprintf(fp, "# walk_list %d", (int)l);
+                    for (int i = T.walk_ptr[l]; i < T.walk_ptr[l + 1]; ++i) fprintf(fp, " %d", T.walk_rec[(size_t)i * 4]);
+                    fprintf(fp, "\n");
+                }
+                for (int i = 0; i < T.n_comp; ++i) fprintf(fp, "# walk_comp %d %d\n", T.comp_v[i], T.comp_c[i]);
+            }
             for (int pos = 0; pos < T.n_dense; ++pos) {
                 const int k = T.lvl_nodes[pos];
                 const int kind = cleaf_of[k] >= 0 ? 1 : ((sl_off[k] >= 0 && lz_idx[k] >= 0) ? 2 : 0);
@@ -1411,6 +1502,9 @@ static int tree_build_into(hpf_handle* h, const hpf_desc* d, Tree& T, bool contr
     }
     if ((r = upload(h, &T.d_dchild, dchild))) return r;
     if ((r = upload(h, &T.d_comp_child, T.comp_c))) return r;
+    if ((r = upload(h, &T.d_walk_ptr, T.walk_ptr))) return r;
+    if ((r = upload(h, &T.d_walk_rec, T.walk_rec))) return r;
+    if ((r = upload(h, &T.d_walk_slot, T.walk_slot))) return r;
     if ((r = upload(h, &T.d_chain_ptr, T.chain_ptr))) return r;
     if ((r = upload(h, &T.d_chain_nodes, T.chain_nodes))) return r;
     if ((r = upload(h, &T.d_chain_ch, T.chain_ch))) return r;

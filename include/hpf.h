@@ -260,6 +260,9 @@ int  hpf_debug_stamps(hpf_handle* h, long long* out, int count);
  * a 4 x 4 pivot block beyond which such a system goes to the pivoted LU, default 1e3; HPF_BORDER_INFO=1 prints every border solve's residual),
  * HPF_FUSEBACK=0 launches the back sweep's scenario-batched workgroups (bordered buses, leaves) after the last depth instead of inside the
  * depths' launches (k_level_back: groups of up to HPF_FUSEBACK_MAX = 32 scenarios, blocks of 52),
+ * HPF_BACKWALK=0 runs the back sweep's Gauss-Jordan buses in one launch per depth instead of two tree walks (k_back_walk: the trunk,
+ * then up to 8 subtree lists, one workgroup per list and scenario; blocks of 52, groups of HPF_BACKWALK_MIN = 16 to HPF_BACKWALK_MAX = 256
+ * scenarios: groups of 1 - 4 run faster on the depth launches; the batched workgroups follow the walk),
  * HPF_GROUPS=n presets "scenario_groups".  Every switch selects a path with the same Newton steps (tests/test_gpu_robustness.py). */
 int  hpf_set_option(hpf_handle* h, const char* name, int value);
 
@@ -309,7 +312,8 @@ int  hpf_kernel_model(const hpf_handle* h, int which, double* bytes, double* flo
  * [11] border systems of a meshed network that were repeated with the pivoted LU since hpf_create (option "border_pivoting"),
  * [12] border unknowns of a meshed network (2 Hn x distinct endpoint buses of the loop-closing lines), [13] buses on the endpoints' root paths
  * (kept as plain Gauss-Jordan buses by the factor-once bordered step; 0: virtual-sweep form), [14] form of the bordered step: 0 virtual sweeps,
- * 1 factor-once with rocSOLVER's LU of the border system, 2 factor-once with the block Gauss-Jordan solve.
+ * 1 factor-once with rocSOLVER's LU of the border system, 2 factor-once with the block Gauss-Jordan solve, [15] back sweeps (scenario group x
+ * Newton step) since hpf_create whose Gauss-Jordan buses went through the tree walk (HPF_BACKWALK).
  * HPF_E_STATE for DENSE. */
 int  hpf_tree_census(const hpf_handle* h, int* counts, int n_counts);
 /* Wall-clock milliseconds hpf_create spent: ms[0] total, [1] planning the elimination trees on the host (classification of the buses,

@@ -18,9 +18,14 @@ from harmonic_power_flow_amd import _lib, ingest, synth   # noqa: E402
 INPUTS = os.path.join(REPO, "tests", "golden", "inputs")
 
 
-def plan(nb, hmax, seed=0, max_scenarios=1, ties=0):
+def plan(nb, hmax, seed=0, max_scenarios=1, ties=0, lines_out=False, files=None):
+    """rows of the planner's dump (ints); lines_out=True: every line of the dump instead, comments included, in file order.
+    files=(buses.csv, lines.csv): that network instead of the synthetic feeder of nb buses"""
     tmp = tempfile.mkdtemp(prefix="hpf_plan_")
-    fb, fl = synth.gen(nb, seed=seed, outdir=tmp)
+    if files:
+        fb, fl = files
+    else:
+        fb, fl = synth.gen(nb, seed=seed, outdir=tmp)
     if ties:
         synth.add_ties(fl, nb, ties)
     st = hp.Settings(H_MAX=hmax)
@@ -45,6 +50,8 @@ def plan(nb, hmax, seed=0, max_scenarios=1, ties=0):
     path = os.path.join(tmp, "plan.txt")
     rc = _lib.load().hpf_tree_plan(C.byref(d), path.encode())
     assert rc == 0, rc
+    if lines_out:
+        return [ln.rstrip("\n") for ln in open(path)]
     rows = [tuple(int(x) for x in ln.split()) for ln in open(path) if not ln.startswith("#")]
     return rows
 

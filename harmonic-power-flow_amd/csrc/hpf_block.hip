@@ -1027,6 +1027,16 @@ __global__ __launch_bounds__(256) void k_border_finish(int count, int r, int v0,
 
 }  // namespace
 
+namespace hpf {
+
+// frees what tree_upload allocated for the tree
+static void tree_free_one(Tree& T) {
+    for (void* p : T.d_owned) hipFree(p);
+    T.d_owned.clear();
+}
+
+}  // namespace hpf
+
 #include "hpf_tree_plan.hpp"      // the host-side planner: tree_build_into, tree_plan_dump, tree_build
 
 namespace hpf {
@@ -1061,18 +1071,6 @@ bool tree_levels_fused(hpf_handle* h) {
 
 // the tree the Newton step of the current mode runs on
 Tree& active_tree(hpf_handle* h) { return (h->has_ctree && h->gj_mode == 1) ? h->ctree : h->tree; }
-
-static void tree_free_one(Tree& T);
-static void tree_free_one_fwd(Tree& T) { tree_free_one(T); }
-static void tree_free_one(Tree& T) {
-    void* ptrs[] = {T.d_parent, T.d_lvl_nodes, T.d_dep_nodes, T.d_child_ptr, T.d_child, T.d_e_up, T.d_e_dn,
-                    T.d_child_mid, T.d_lin, T.d_lin_ptr, T.d_lin_post, T.d_all_ptr, T.d_all_post, T.d_fdesc, T.d_child3,
-                    T.d_bdesc, T.d_dchild, T.d_chain_ptr, T.d_chain_nodes, T.d_chain_ch, T.d_Minv, T.d_lrec, T.d_crec, T.d_cnode, T.d_arec,
-                    T.d_lzrec, T.d_lzimg, T.d_lbimg, T.d_bleaf, T.d_bsleaf, T.d_bsleaf_dep, T.d_sbimg, T.d_lbrec, T.d_lbptr, T.d_lb2rec, T.d_lb2x, T.d_lb2ptr, T.d_lb2cptr, T.d_lb2clist,
-                    T.d_comp_child, T.d_walk_ptr, T.d_walk_rec, T.d_walk_slot};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-}
 
 void tree_free(hpf_handle* h) {
     tree_free_one(h->tree);

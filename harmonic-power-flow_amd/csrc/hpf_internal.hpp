@@ -152,7 +152,8 @@ struct Tree {
     int* d_walk_ptr = nullptr;
     int* d_walk_rec = nullptr;
     int* d_walk_slot = nullptr;
-    double plan_ms = 0.0;             // host time of tree_build_into up to the uploads
+    std::vector<void*> d_owned;       // every device array above, as tree_upload allocated it: what tree_free_one frees
+    double plan_ms = 0.0;             // host time of tree_build_into up to the uploads (all planning, the back-sweep batch records included)
     double flops_per_solve = 0.0;     // factor sweep + back sweep
     double flops_factor = 0.0;        // factor sweep only (k_tree_factor, all levels)
     double bytes_back = 0.0;          // algorithmic HBM bytes of the dense back sweep, one scenario and step

@@ -239,8 +239,12 @@ def _postprocess(Vm, Va):
 
 
 def hpf(buses, lines, coupled, thresh_h=1e-4, max_iter_h=50, plt_convergence=False, settings=None, ne_dir=None,
-        solver="auto", verbose=True, return_jacobian=True, details=None, extra_iters=0):
+        solver="auto", verbose=True, return_jacobian=True, details=None, extra_iters=0, check_steps=False):
     """HG:511-560 -> (V, err_h, n_iter_h, J).
+
+    `check_steps` (not in the reference, default False): every harmonic Newton step's normwise backward error is evaluated on the device
+    (option "step_residual_check"); a step above the limit repeats the solve with partial pivoting (radial block tree) or retries it on
+    the dense LU (meshed, solver="auto"); `details` then carries step_eta_max and step_flagged.
 
     `J` is the Jacobian of the last iteration as scipy CSR like the reference (HG:537,560), at every size: the device writes
     the CSR arrays directly (hpf_jacobian_csr_last; 1.2 M entries at 1 000 buses x 26 harmonics).  return_jacobian=False skips it;
@@ -269,15 +273,21 @@ def hpf(buses, lines, coupled, thresh_h=1e-4, max_iter_h=50, plt_convergence=Fal
         # (block-tree: hpf_solve itself watches the static pivot order and repeats a flagged scenario with partial pivoting)
         want_J = bool(return_jacobian)
         dm.set_option("keep_previous_state", 1 if want_J else 0)      # (explicit both ways: the handle may be a borrowed one)
+        dm.set_option("step_residual_check", 1 if check_steps else 0)  # (likewise)
         n_iter, err, hist = dm.solve(thresh_h, max_iter_h)                        # HG:530-542
         stats = dm.stats()
+        step_eta_max = float(dm.step_residuals()[1][0]) if check_steps else None
         # a meshed network on the block-tree path has no pivoted repeat of its own (hpf.h): with solver="auto" a scenario the static-pivot monitor
         # flagged, or whose mismatch turned non-finite, is solved again on the dense rocSOLVER path where that fits
         retry_dense = (solver == "auto" and dm.solver == "block_tree" and dm.tree_census()["ties"] > 0 and
-                       bool(stats["flags"][0] & (4 | 8)) and not (stats["flags"][0] & 16) and 8.0 * dm.N * dm.N <= 64e9)
+                       bool(stats["flags"][0] & (4 | 8 | 64)) and not (stats["flags"][0] & 16) and 8.0 * dm.N * dm.N <= 64e9)
         if details is not None:
             details["repeated_with_pivoting"] = bool(stats["flags"][0] & 16)
-        if verbose and (stats["flags"][0] & 16):
+            details["step_eta_max"] = step_eta_max                      # (None: check off; after a repeat: of the repeat)
+            details["step_flagged"] = bool(stats["flags"][0] & 64)
+        if verbose and (stats["flags"][0] & 16) and (stats["flags"][0] & 64):
+            print("Warning! A Newton step missed the residual check; the solve was repeated with partial pivoting.")
+        elif verbose and (stats["flags"][0] & 16):
             print("Warning! Static-pivot block elimination was flagged; the solve was repeated with partial pivoting.")
         if extra_iters > 0 and np.isfinite(err[0]):
             dm.mismatch(want_f=False)
@@ -296,10 +306,13 @@ def hpf(buses, lines, coupled, thresh_h=1e-4, max_iter_h=50, plt_convergence=Fal
                            tree=(dm.tree_census() if dm.solver == "block_tree" else None),
                            stats=stats, Vm_raw=Vm_raw[0].copy(), Va_raw=Va_raw[0].copy(), N=dm.N)
     if retry_dense:
-        if verbose:
+        if verbose and (stats["flags"][0] & 64):
+            print("Warning! A Newton step of the bordered block-tree path missed the residual check; solving again with the dense LU.")
+        elif verbose:
             print("Warning! The bordered block-tree step was flagged (static pivot order / non-finite mismatch); solving again with the dense LU.")
         return hpf(buses, lines, coupled, thresh_h=thresh_h, max_iter_h=max_iter_h, plt_convergence=plt_convergence, settings=settings, ne_dir=ne_dir,
-                   solver="dense", verbose=verbose, return_jacobian=return_jacobian, details=details, extra_iters=extra_iters)
+                   solver="dense", verbose=verbose, return_jacobian=return_jacobian, details=details, extra_iters=extra_iters,
+                   check_steps=check_steps)
     Vm, Va = _postprocess(Vm_raw[0], Va_raw[0])                                   # HG:545-549
     V = _frame(Vm, Va, harmonics, n)
     err_h = float(err[0])
@@ -459,13 +472,14 @@ def get_THD(V):
     return pd.DataFrame({"THD_F": thd_f, "THD_R": thd_r})
 
 
-def solve(filename_buses, filename_lines, coupled=True, settings=None, ne_dir=None, solver="auto", verbose=False, extra_iters=0):
-    """Convenience wrapper (= init_network + hpf + get_THD) -> dict(V, err_h, n_iter_h, THD, details)."""
+def solve(filename_buses, filename_lines, coupled=True, settings=None, ne_dir=None, solver="auto", verbose=False, extra_iters=0,
+          check_steps=False):
+    """Convenience wrapper (= init_network + hpf + get_THD) -> dict(V, err_h, n_iter_h, THD, details).  check_steps: see hpf."""
     st = settings or globals()["settings"]
     buses, lines, m, n, c = init_network(filename_buses, filename_lines, settings=st)
     details = {}
     V, err_h, n_iter_h, J = hpf(buses, lines, coupled, st.thresh_h, st.max_iter_h, settings=st, ne_dir=ne_dir,
-                                solver=solver, verbose=verbose, details=details, extra_iters=extra_iters)
+                                solver=solver, verbose=verbose, details=details, extra_iters=extra_iters, check_steps=check_steps)
     # converged = the stop rule err_h <= thresh_h was met (flags bit 0) -- not "the loop ended": a NaN mismatch ends it too
     return {"V": V, "err_h": err_h, "n_iter_h": n_iter_h, "THD": get_THD(V), "details": details,
             "converged": bool(details["stats"]["flags"][0] & 1)}

@@ -231,14 +231,19 @@ HPF_HD Blk2 jac_current_diag(const Model& M, const cplx* U, const cplx* E, int q
 }
 
 // Coupled Norton cross terms q != p at nonlinear bus i (HG:425-435): entry [q*n+i, p*n+i] = 0 - Y_N[q,p]*...
+// (norton_cross_blk: the same entry from its three operands, Y_N[q,p] and the voltages of column (p, i), wherever the caller keeps them)
+HPF_HD Blk2 norton_cross_blk(cplx yn, cplx u, cplx e) {
+    Blk2 b;
+    b.dV = cneg(cmul_unf(yn, e));
+    b.dA = cneg(cmul_unf(cmulj(yn), u));
+    return b;
+}
+
 HPF_HD Blk2 jac_norton_cross(const Model& M, const cplx* U, const cplx* E, int q, int p, int i) {
     const int d = M.dev[i];
     const cplx yn = M.YN[((size_t)d * M.Hn + q) * M.Hn + p];
     const size_t kc = M.vi(p, i);
-    Blk2 b;
-    b.dV = cneg(cmul_unf(yn, E[kc]));
-    b.dA = cneg(cmul_unf(cmulj(yn), U[kc]));
-    return b;
+    return norton_cross_blk(yn, U[kc], E[kc]);
 }
 
 // Power rows at the fundamental (HG:451-459 for the harmonic NR, HG:207-214 for pf): entry (i, j) of
@@ -360,8 +365,14 @@ HPF_HD bool jcsr_has_entry(const Model& M, const JRow& R, int e, int j) {
     return y.re != 0.0 || y.im != 0.0;
 }
 
+// Y_N[q, p] of device type d: from the transposed copy where the model has one (device: the threads of one bus, q fastest, then read one
+// contiguous run per column p), else from the matrix itself -- the same value
+HPF_HD cplx norton_yn(const Model& M, int d, int q, int p) {
+    return M.YNt ? M.YNt[((size_t)d * M.Hn + p) * M.Hn + q] : M.YN[((size_t)d * M.Hn + q) * M.Hn + p];
+}
+
 HPF_HD bool jcsr_has_cross(const Model& M, const JRow& R, int p) {
-    const cplx y = M.YN[((size_t)M.dev[R.i] * M.Hn + R.q) * M.Hn + p];
+    const cplx y = norton_yn(M, M.dev[R.i], R.q, p);
     return y.re != 0.0 || y.im != 0.0;
 }
 
@@ -424,6 +435,83 @@ HPF_HD void jcsr_fill_row(const Model& M, const cplx* U, const cplx* E, int Nc, 
     const JCount cnt = jcsr_count_row(M, Nc, r);
     JFill fl{M, U, E, jcsr_row(M, Nc, r), Nc, col, val, start, start + cnt.n_theta};
     jcsr_walk(M, fl.R, fl);
+}
+
+// ---- Residual of a Newton step, row by row (the check of option "step_residual_check") --------------------------------------------
+// For complex row k = q*n + i, Re and Im parts together (.re / .im of every member): r = f_k - sum_c J_kc dx_c, a = sum_c |J_kc| |dx_c|
+// and the row sum w = sum_c |J_kc| over the stored entries of hpf_jacobian_csr (jcsr_walk: the same entries, the same entry functions, the
+// same column masking kc < 1 / kc < c) without forming J.  Every product is one fma into its sum: with k stored entries in the real row,
+// |r - (f - J dx)| <= (k + 1) 2^-53 (|J| |dx| + |f|).  The Re part is an equation for k >= 1, the Im part for k >= c: the caller masks.
+// The step is read through an accessor dx(kc, p, j) -> (d theta, d V) of stacked column kc = p*n + j; components that are no unknowns may
+// hold anything (they are never used).
+struct StepStacked {       // the reference's stacked layout (HG:393-398; the dense solver and the generic tree kernels leave the step so)
+    const double* d;
+    int Nc, c;
+    HPF_HD cplx operator()(int kc, int, int) const { return {kc >= 1 ? d[kc - 1] : 0.0, kc >= c ? d[Nc + kc - c] : 0.0}; }
+};
+struct StepBusMajor {      // bus-major image [bus][2p + (theta | V)] with stride Bst (multi-wave block-tree sweep)
+    const double* x;
+    int Bst;
+    HPF_HD cplx operator()(int, int p, int j) const {
+        const double* o = x + (size_t)j * Bst + 2 * p;
+        return {o[0], o[1]};
+    }
+};
+
+struct StepRow {
+    cplx r, a, w;
+};
+
+HPF_HD JRow jcsr_row_qi(const Model& M, int q, int i) {
+    JRow R;
+    R.t = 0;
+    R.q = q;
+    R.i = i;
+    R.k = q * M.n + i;
+    R.power = q == 0 && i < M.m;
+    R.cross = M.coupled && i >= M.m;
+    return R;
+}
+
+template <class DX>
+struct JResid {
+    const Model& M;
+    const cplx *U, *E;
+    JRow R;
+    const DX& dx;
+    StepRow s;
+    // one complex entry b of column kc against the step d of that column
+    HPF_HD void term(int kc, const Blk2& b, cplx d) {
+        if (kc >= 1) {
+            s.r.re = fma(-b.dA.re, d.re, s.r.re);
+            s.r.im = fma(-b.dA.im, d.re, s.r.im);
+            s.a.re = fma(fabs(b.dA.re), fabs(d.re), s.a.re);
+            s.a.im = fma(fabs(b.dA.im), fabs(d.re), s.a.im);
+            s.w.re += fabs(b.dA.re);
+            s.w.im += fabs(b.dA.im);
+        }
+        if (kc >= M.c) {
+            s.r.re = fma(-b.dV.re, d.im, s.r.re);
+            s.r.im = fma(-b.dV.im, d.im, s.r.im);
+            s.a.re = fma(fabs(b.dV.re), fabs(d.im), s.a.re);
+            s.a.im = fma(fabs(b.dV.im), fabs(d.im), s.a.im);
+            s.w.re += fabs(b.dV.re);
+            s.w.im += fabs(b.dV.im);
+        }
+    }
+    HPF_HD void operator()(int kc, int e, int j, int p) {
+        const Blk2 b = e >= 0 ? (R.power ? jac_power_entry<false>(M, U, E, R.i, j, e) : jac_current_entry(M, U, E, R.q, R.i, j, e))
+                              : norton_cross_blk(norton_yn(M, M.dev[R.i], R.q, p), U[M.vi(p, R.i)], E[M.vi(p, R.i)]);   // = jac_norton_cross
+        term(kc, b, dx(kc, p, j));
+    }
+};
+
+// row (q, i), k = q*n + i >= 1, with its mismatch f supplied by the caller (mismatch_row_qi<false>: what the solver was given)
+template <class DX>
+HPF_HD StepRow step_residual_row(const Model& M, const cplx* U, const cplx* E, int q, int i, cplx f, const DX& dx) {
+    JResid<DX> res{M, U, E, jcsr_row_qi(M, q, i), dx, {f, {0.0, 0.0}, {0.0, 0.0}}};
+    jcsr_walk(M, res.R, res);
+    return res.s;
 }
 
 // Real mismatch vector layout f = [Re f_c ; Im f_c[c-1:]] (HG:388).

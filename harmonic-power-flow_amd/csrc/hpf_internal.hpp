@@ -24,7 +24,7 @@ enum LinForm {
     LIN_LEVELS                        // one launch per height (k_lin_level_factor / _back)
 };
 
-enum { T_MISMATCH = 0, T_JACOBIAN = 1, T_SOLVE = 2, T_UPDATE = 3, T_BACK = 4, T_GJ = 5, T_GJ_DEV = 6, T_COUNT = 7 };
+enum { T_MISMATCH = 0, T_JACOBIAN = 1, T_SOLVE = 2, T_UPDATE = 3, T_BACK = 4, T_GJ = 5, T_GJ_DEV = 6, T_RESID = 7, T_COUNT = 8 };
 
 struct TimedSpan {
     int which;
@@ -237,6 +237,11 @@ struct hpf_handle {
     int* d_nactive = nullptr;         // [1]
     int* d_pivflag = nullptr;         // [S] bit0: a static 4x4 pivot block exceeded piv_limit (k_factor_q), bit1: repeated with partial pivoting,
                                       //     bit2: exactly zero pivot met by the pivoted wave Gauss-Jordan (k_factor_w)
+                                      //     bit3: a Newton step missed the residual check (k_step_eta) in the current pass, bit4: ... in the first pass of a repeated scenario
+    int resid_check = 0;              // option "step_residual_check": k_step_residual + k_step_eta between the linear solve and the update
+    double resid_limit = 1e-10;       // option "step_residual_limit_log10": eta above it (or not finite) flags the scenario
+    unsigned long long* d_respart = nullptr;   // [S][4][errpart_stride] partial maxima of |r|, row sums of |J|, |dx|, |f| (one per wavefront of k_step_residual)
+    double* d_eta = nullptr;          // [2][S_alloc] eta of the last step | largest eta of the solve (-1: no step yet)
     int* d_mask = nullptr;            // [S] scenarios of a repeat pass
     double *d_Vm0 = nullptr, *d_Va0 = nullptr;   // [S][Hn*n] state at the entry of hpf_solve (repeat with partial pivoting starts from it)
     double *d_Vmp = nullptr, *d_Vap = nullptr;   // [S][Hn*n] option "keep_previous_state": the state each scenario's LAST Newton step started from
@@ -299,8 +304,8 @@ struct hpf_handle {
     double setup_ms[4] = {0, 0, 0, 0}; // hpf_create: total | tree planning on the host | tree uploads | per-scenario allocation
     int timing = 0;                   // hpf_timing_enable: 1 HIP-event spans + device stamps, 2 device stamps only (no event packets between kernels)
     std::vector<hpf::TimedSpan> spans;
-    double t_ms[hpf::T_COUNT] = {0, 0, 0, 0, 0, 0, 0};
-    int64_t t_n[hpf::T_COUNT] = {0, 0, 0, 0, 0, 0, 0};
+    double t_ms[hpf::T_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t t_n[hpf::T_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
     static constexpr int TS_CAP = 16384;         // launches of the general factor kernel a timing leg can stamp
     unsigned long long* d_tstamp = nullptr;      // [TS_CAP][2] first workgroup start / last workgroup end (wall_clock64) per launch
     int ts_next = 0;

@@ -283,6 +283,114 @@ __global__ __launch_bounds__(TPB, 8) void k_mismatch(Model M, int count, int N, 
     b = wave_max_u64(b);
     if ((tid & 63) == 0) errpart[(size_t)s * pstride + (size_t)bx * (TPB / 64) + (tid >> 6)] = b;
 }
+
+// Residual check of a Newton step (option "step_residual_check"): r = f - J dx row by row without forming J, between the linear solve and
+// the state update.  Shaped like k_mismatch: one thread per complex row (t = i*Hn + q), XCD-aware placement, slot list; a tile with
+// nonlinear buses stages the device type's Y_N^T and the tile's U, E and step (d theta, d V per column) in LDS, so that the Hn cross terms
+// of a nonlinear row -- the only O(Hn^2) part -- and its Norton injection run out of LDS.  Per-entry arithmetic: hpf_assembly.hpp
+// (step_residual_row / JResid: the entries and masks of hpf_jacobian_csr); f is evaluated again exactly as k_mismatch evaluates it (the
+// step overwrote d_f on the stacked paths, the tree sweeps own d_fb).  It never reads a debug switch: the step is judged against the true J.
+// Every wavefront leaves four partial maxima (|r|, row sums of |J|, |dx|, |f|) -> respart[s][4][pstride]; k_step_eta forms eta.
+// BUSX: the step is the bus-major image (stride Bst) of the multi-wave block-tree sweep, else the stacked vector.  stage: the launch has the LDS.
+template <bool BUSX>
+__global__ __launch_bounds__(TPB) void k_step_residual(Model M, int count, int N, int Nc, const int* __restrict__ active, const cplx* __restrict__ U,
+                           const cplx* __restrict__ E, const double* __restrict__ P, const double* __restrict__ Q,
+                           const double* __restrict__ step, int Bst, unsigned long long* __restrict__ respart, int pstride,
+                           int s0, int S_cnt, unsigned hn_magic, int stage_ok) {
+    extern __shared__ cplx rs_lds[];                    // [Hn*Hn] Y_N^T of the tile's first device type | [tile buses][Hn] U | E | step
+    int bx, slot;
+    if (!xcd_map(S_cnt, bx, slot)) return;
+    const int s = active ? active[slot + s0] : slot + s0;
+    if (s < 0) return;
+    const int tid = threadIdx.x;
+    const int t = bx * TPB + tid;
+    const int Hn = M.Hn;
+    const cplx* Us = U + (size_t)s * M.n * Hn;
+    const cplx* Es = E + (size_t)s * M.n * Hn;
+    const double* ds = step + (BUSX ? (size_t)s * M.n * Bst : (size_t)s * N);
+    const StepBusMajor dxb{ds, Bst};
+    const StepStacked dxs{ds, Nc, M.c};
+    const bool live = t < count;
+    const int i = live ? div_by(t, hn_magic) : M.n - 1, q = live ? t - i * Hn : 0;
+    const int i_first = div_by(bx * TPB, hn_magic);
+    int i_last = div_by(bx * TPB + TPB - 1, hn_magic);
+    if (i_last > M.n - 1) i_last = M.n - 1;
+    const int nyn = Hn * Hn, nv = (i_last - i_first + 1) * Hn;          // nv <= (TPB / Hn + 2) Hn: the launch sized the LDS for it
+    const bool stage = stage_ok && M.coupled && M.YNt && i_last >= M.m;   // (uniform over the workgroup)
+    int d0 = -1;
+    cplx *ul = rs_lds + nyn, *el = ul + nv, *xl = el + nv;
+    if (stage) {
+        d0 = M.dev[i_first > M.m ? i_first : M.m];
+        const double2* src = reinterpret_cast<const double2*>(M.YNt + (size_t)d0 * nyn);
+        double2* dst = reinterpret_cast<double2*>(rs_lds);
+        for (int x = tid; x < nyn; x += TPB) dst[x] = src[x];
+        const size_t o = (size_t)i_first * Hn;
+        for (int x = tid; x < nv; x += TPB) {
+            ul[x] = Us[o + x];
+            el[x] = Es[o + x];
+            const int ib = i_first + div_by(x, hn_magic), p = x - (ib - i_first) * Hn;
+            xl[x] = BUSX ? dxb(0, p, ib) : dxs(p * M.n + ib, p, ib);
+        }
+        __syncthreads();
+    }
+    unsigned long long br = 0, bw = 0, bd = 0, bf = 0;
+    const int k = q * M.n + i;
+    if (live && k >= 1) {
+        const bool mine = d0 >= 0 && i >= M.m && M.dev[i] == d0;       // nonlinear bus of the staged device type
+        const int loc = (i - i_first) * Hn;
+        const cplx f = mine ? cadd(row_current(M, Us, q, i), norton_injection_lds(M, d0, rs_lds, ul + loc, q))
+                            : mismatch_row_qi<false>(M, Us, P + (size_t)s * M.n, Q + (size_t)s * M.n, q, i);
+        StepRow rw;
+        if (stage && i >= M.m) {
+            // A nonlinear row of a staged tile: the entries of jcsr_walk with the cross terms' operands out of LDS.  The admittance row comes
+            // FIRST, for all lanes together, then the cross terms in ascending column p != q: inside the column loop (jcsr_walk's order) the lane
+            // with p == q made its whole wavefront wait for the row's dependent fetches at EVERY p (measured: 155 us for one workgroup at Hn = 26,
+            // 6 us per column).  Only the order of the sum differs from the host's row function; the rounding bound does not depend on it.
+            // Y_N^T of another device type than the staged one comes from memory (the lanes of a bus read one contiguous run per column).
+            JResid<StepStacked> res{M, Us, Es, jcsr_row_qi(M, q, i), dxs, {f, {0.0, 0.0}, {0.0, 0.0}}};
+            for (int e = M.rowptr[i]; e < M.rowptr[i + 1]; ++e) {
+                const int j = M.col[e];
+                if (!jcsr_has_entry(M, res.R, e, j)) continue;
+                const Blk2 b = jac_current_entry(M, Us, Es, q, i, j, e);
+                res.term(k - i + j, b, BUSX ? dxb(0, q, j) : dxs(k - i + j, q, j));
+            }
+            const cplx* yq = (mine ? rs_lds : M.YNt + (size_t)M.dev[i] * nyn) + q;
+            for (int p = 0; p < Hn; ++p) {
+                const cplx yn = yq[(size_t)p * Hn];
+                if (p != q && (yn.re != 0.0 || yn.im != 0.0)) res.term(p * M.n + i, norton_cross_blk(yn, ul[loc + p], el[loc + p]), xl[loc + p]);
+            }
+            rw = res.s;
+        } else if (BUSX) {
+            rw = step_residual_row(M, Us, Es, q, i, f, dxb);
+        } else {
+            rw = step_residual_row(M, Us, Es, q, i, f, dxs);
+        }
+        const cplx d = BUSX ? dxb(k, q, i) : dxs(k, q, i);
+        br = abs_bits(rw.r.re);
+        bw = abs_bits(rw.w.re);
+        bd = abs_bits(d.re);
+        bf = abs_bits(f.re);
+        if (k >= M.c) {
+            unsigned long long v;
+            v = abs_bits(rw.r.im); br = v > br ? v : br;
+            v = abs_bits(rw.w.im); bw = v > bw ? v : bw;
+            v = abs_bits(d.im); bd = v > bd ? v : bd;
+            v = abs_bits(f.im); bf = v > bf ? v : bf;
+        }
+    }
+    br = wave_max_u64(br);
+    bw = wave_max_u64(bw);
+    bd = wave_max_u64(bd);
+    bf = wave_max_u64(bf);
+    if ((tid & 63) == 0) {
+        unsigned long long* o = respart + (size_t)s * 4 * pstride + (size_t)bx * (TPB / 64) + (tid >> 6);
+        o[0] = br;
+        o[pstride] = bw;
+        o[2 * (size_t)pstride] = bd;
+        o[3 * (size_t)pstride] = bf;
+    }
+}
+
 // Dense Jacobian, network entries: one thread per (harmonic position, stored admittance entry) of one scenario.
 template <bool FUND>
 __global__ void k_jac_dense(Model M, int total, int N, int Nc, size_t J_stride, const int* __restrict__ active,
@@ -455,6 +563,29 @@ __global__ __launch_bounds__(64) void k_err_reduce(const unsigned long long* __r
     if (threadIdx.x == 0) out[blockIdx.x] = b;
 }
 
+// eta = |f - J dx|_inf / (| |J| |_inf |dx|_inf + |f|_inf) of the step k_step_residual just judged (the normwise backward error of
+// tests/stepcheck.py), one wavefront per slot: eta[s] the last step's, eta[S_alloc + s] the largest of the solve (-1: no step yet; a
+// non-finite eta stays); eta > limit or not finite sets pivflag bit 3.
+__global__ __launch_bounds__(64) void k_step_eta(int S, const int* __restrict__ active, const unsigned long long* __restrict__ respart, int pstride,
+                                                 int np, double limit, double* __restrict__ eta, int eta_stride, int* __restrict__ pivflag, int s0) {
+    const int sl = blockIdx.x;
+    if (sl >= S) return;
+    const int s = active ? active[sl + s0] : sl + s0;
+    if (s < 0) return;
+    const unsigned long long* part = respart + (size_t)s * 4 * pstride;
+    const double r = __longlong_as_double((long long)slot_err_bits(part, np));
+    const double w = __longlong_as_double((long long)slot_err_bits(part + pstride, np));
+    const double d = __longlong_as_double((long long)slot_err_bits(part + 2 * (size_t)pstride, np));
+    const double f = __longlong_as_double((long long)slot_err_bits(part + 3 * (size_t)pstride, np));
+    if (threadIdx.x != 0) return;
+    const double den = w * d + f;
+    const double e = den > 0.0 ? r / den : r;
+    eta[s] = e;
+    const double m = eta[eta_stride + s];
+    if (e != e || e > m) eta[eta_stride + s] = e;
+    if (!(e <= limit)) atomicOr(pivflag + s, 8);
+}
+
 // Stable compaction of the slot list (running scenarios to the front, -1 behind them) and their count -> *count.  One workgroup;
 // runs between two chunks of iterations, so that the next chunk launches grids over the running scenarios only and the
 // 16-scenario tiles of the leaf kernels stay full.
@@ -494,19 +625,31 @@ __global__ void k_set_int(int* p, int count, int v) {
     if (i < count) p[i] = v;
 }
 
-// scenarios that need the repeat pass with partial pivoting: a static pivot block went over the limit (pivflag bit 0) or the
-// mismatch became non-finite.  mask[s] = 1, pivflag[s] |= 2 ("repeated"); k_restore_masked then resets their state.
+// scenarios that need the repeat pass with partial pivoting: a static pivot block went over the limit (pivflag bit 0), a step missed the
+// residual check (bit 3, option "step_residual_check") or the mismatch became non-finite.  mask[s] = 1, pivflag[s] |= 2 ("repeated");
+// k_restore_masked then resets their state.  The residual verdict of the first pass moves to bit 4, so that bit 3 is the repeat's own;
+// eta (nullptr: check off) starts again for the repeated scenarios.
 __global__ void k_mark_repeat(int S, const double* __restrict__ err, int* __restrict__ pivflag, int* __restrict__ mask,
-                              int* __restrict__ count) {
+                              int* __restrict__ count, double* __restrict__ eta, int eta_stride) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= S) return;
     const double e = err[s];
-    const int m = ((pivflag[s] & 1) || e != e || isinf(e)) ? 1 : 0;
+    const int pf = pivflag[s];
+    const int m = ((pf & 1) || (pf & 8) || e != e || isinf(e)) ? 1 : 0;
     mask[s] = m;
     if (m) {
-        pivflag[s] = (pivflag[s] & 1) | 2;      // bit 1: repeated (bit 0 stays: why)
+        pivflag[s] = (pf & 1) | 2 | ((pf & 8) ? 16 : 0);      // bit 1: repeated (bits 0 and 4 stay: why)
+        if (eta) {
+            eta[s] = NAN;
+            eta[eta_stride + s] = -1.0;
+        }
         atomicAdd(count, 1);
     }
+}
+
+// hpf_stat.flags bits 6 and 7 from the pivflag word: a step of the first pass / of the pass whose result is returned missed the residual check
+__device__ __forceinline__ int resid_flag_bits(int pf) {
+    return (((pf & 2) ? (pf & 16) : (pf & 8)) ? 64 : 0) | ((pf & 8) ? 128 : 0);
 }
 
 // option "keep_previous_state": before a Newton step, the running scenarios' voltages -> the "previous state" copy (the reference
@@ -578,7 +721,7 @@ __global__ void k_stats(int n, int Hn, double thresh, int max_iter, const double
         st.err = e;
         const int pf = pivflag ? pivflag[s] : 0;
         st.flags = (e <= thresh ? 1 : 0) | ((niter[s] >= max_iter && !(e <= thresh)) ? 2 : 0) | ((e != e || isinf(e)) ? 4 : 0) |
-                   ((pf & 1) ? 8 : 0) | ((pf & 2) ? 16 : 0) | ((pf & 4) ? 32 : 0);
+                   ((pf & 1) ? 8 : 0) | ((pf & 2) ? 16 : 0) | ((pf & 4) ? 32 : 0) | resid_flag_bits(pf);
         st.thd_max = __longlong_as_double((long long)r);
         out[s] = st;
     }
@@ -665,7 +808,7 @@ __global__ void k_queue_harvest(int n, int Hn, double thresh, int max_iter, cons
         st.err = e;
         const int pf = pivflag[s];
         st.flags = (e <= thresh ? 1 : 0) | ((niter[s] >= max_iter && !(e <= thresh)) ? 2 : 0) | ((e != e || isinf(e)) ? 4 : 0) |
-                   ((pf & 1) ? 8 : 0) | ((pf & 4) ? 32 : 0);
+                   ((pf & 1) ? 8 : 0) | ((pf & 4) ? 32 : 0) | resid_flag_bits(pf);
         st.thd_max = __longlong_as_double((long long)r);
         qstats[g] = st;
     }
@@ -975,6 +1118,42 @@ int launch_update(hpf_handle* h, const int* active) {
     return launch_status(h);
 }
 
+// eta of no step yet, for every slot (hpf_solve entry, hpf_set_state, switching the check on)
+int reset_step_eta(hpf_handle* h) {
+    if (!h->d_eta) return HPF_OK;
+    const size_t S = (size_t)h->S_alloc;
+    hipLaunchKernelGGL(k_fill, dim3((unsigned)((S + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, h->d_eta, S, (double)NAN);
+    hipLaunchKernelGGL(k_fill, dim3((unsigned)((S + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, h->d_eta + S, S, -1.0);
+    return launch_status(h);
+}
+
+// LDS of k_step_residual: Y_N^T of one device type + U, E and the step of the workgroup's tile of buses; 0: nothing to stage (uncoupled, no
+// nonlinear bus) or beyond what a workgroup can have -- the kernel then reads every operand from memory
+static size_t step_residual_lds(const hpf_handle* h) {
+    if (!(h->coupled && h->n > h->m)) return 0;
+    const size_t lds = sizeof(cplx) * ((size_t)h->Hn * h->Hn + 3 * (size_t)(TPB / h->Hn + 2) * h->Hn);
+    return lds > 160 * 1024 ? 0 : lds;
+}
+
+// The residual check of the step newton_step just left (in d_x or d_f, as launch_update will read it), before the update moves the state.
+int launch_step_residual(hpf_handle* h, const int* active) {
+    ScopedTimer t(h, T_RESID);
+    const int count = h->n * h->Hn;
+    if (count <= 1) return HPF_OK;
+    const bool busx = bus_images(h);
+    const int nbx = (count + TPB - 1) / TPB;
+    const size_t lds = step_residual_lds(h);
+    auto kern = busx ? &k_step_residual<true> : &k_step_residual<false>;
+    if (lds > 64 * 1024)        // beyond the default dynamic-LDS limit of a kernel (as launch_mismatch)
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL(kern, xcd_grid(nbx, h->cur_S), dim3(TPB), lds, h->cur_stream, h->M, count, h->N, h->Nc, active, h->d_U, h->d_E,
+                       h->d_P, h->d_Q, busx ? h->d_x : h->d_f, tree_bst(h), h->d_respart, h->errpart_stride, h->cur_s0, h->cur_S,
+                       div_magic(h->Hn), lds > 0 ? 1 : 0);
+    hipLaunchKernelGGL(k_step_eta, dim3((unsigned)h->cur_S), dim3(64), 0, h->cur_stream, h->cur_S, active, h->d_respart, h->errpart_stride,
+                       err_parts<false>(h), h->resid_limit, h->d_eta, h->S_alloc, h->d_pivflag, h->cur_s0);
+    return launch_status(h);
+}
+
 // One Newton step: Jacobian at the current state, step = J^{-1} f into d_f.
 template <bool FUND>
 int newton_step(hpf_handle* h, const int* active) {
@@ -1062,6 +1241,7 @@ int nr_pass(hpf_handle* h, double thresh, int max_iter, const int* mask) {
                     hipLaunchKernelGGL(k_keep_prev, grid2(h->n * h->Hn, h->cur_S), dim3(TPB), 0, h->cur_stream, h->n * h->Hn,
                                        h->d_active, h->d_Vm, h->d_Va, h->d_Vmp, h->d_Vap, h->cur_s0);
                 if ((rr = newton_step<FUND>(h, h->d_active))) return rr;
+                if (!FUND && h->resid_check && (rr = launch_step_residual(h, h->d_active))) return rr;
                 if ((rr = launch_update<FUND>(h, h->d_active))) return rr;
                 if ((rr = launch_mismatch<FUND>(h, h->d_active, false))) return rr;
                 hipLaunchKernelGGL(k_finalize, dim3((unsigned)h->cur_S), dim3(64), 0, h->cur_stream, h->cur_S, 0, thresh,
@@ -1170,6 +1350,7 @@ int nr_loop(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* err
                             h->n_ties == 0;      // (the bordered step of a meshed network runs in the bus-image layout of the static-pivot kernels only)
     const size_t count = (size_t)h->n * h->Hn;
     if (!FUND) HIPCHK(hipMemsetAsync(h->d_pivflag, 0, sizeof(int) * S, h->stream));
+    if (!FUND && h->resid_check && (r = reset_step_eta(h))) return r;
     if (can_repeat) {
         if (!h->d_Vm0) {
             if ((r = dev_alloc(h, &h->d_Vm0, (size_t)h->S_max * count))) return r;
@@ -1184,7 +1365,7 @@ int nr_loop(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* err
         int nrep = 0;
         HIPCHK(hipMemsetAsync(h->d_nactive, 0, sizeof(int), h->stream));
         hipLaunchKernelGGL(k_mark_repeat, dim3((S + 63) / 64), dim3(64), 0, h->stream, S, h->d_err, h->d_pivflag, h->d_mask,
-                           h->d_nactive);
+                           h->d_nactive, h->resid_check ? h->d_eta : (double*)nullptr, h->S_alloc);
         HIPCHK(hipMemcpyAsync(&nrep, h->d_nactive, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         if (nrep > 0) {
@@ -1312,6 +1493,7 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
             int rr;
             for (int j = 0; j < todo; ++j) {
                 if ((rr = newton_step<false>(h, h->d_active))) return rr;
+                if (h->resid_check && (rr = launch_step_residual(h, h->d_active))) return rr;
                 if ((rr = launch_update<false>(h, h->d_active))) return rr;
                 if ((rr = launch_mismatch<false>(h, h->d_active, false))) return rr;
                 hipLaunchKernelGGL(k_finalize, dim3((unsigned)h->cur_S), dim3(64), 0, h->cur_stream, h->cur_S, 0, thresh, max_iter, 1, 0,
@@ -1351,7 +1533,7 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
 void free_all(hpf_handle* h) {
     void* ptrs[] = {h->d_rowrec, h->d_rowptr, h->d_col, h->d_diag, h->d_erow, h->d_dev, h->d_Y, h->d_YN, h->d_YNt, h->d_IN, h->d_P, h->d_Q,
                     h->d_Vm, h->d_Va, h->d_U, h->d_E, h->d_I0, h->d_f, h->d_errbits, h->d_errpart, h->d_err, h->d_niter, h->d_active,
-                    h->d_nactive, h->d_pivflag, h->d_mask, h->d_Vm0, h->d_Va0, h->d_Vmp, h->d_Vap, h->d_swapVm, h->d_swapVa, h->d_tstamp, h->d_hist, h->d_stats, h->d_J, h->d_ipiv, h->d_info, h->d_Z, h->d_w, h->d_x, h->d_linA, h->d_C, h->d_dbg, h->d_H, h->d_chG, h->d_chH, h->d_chD, h->d_chy, h->d_chZ, h->d_lfK, h->d_lfS, h->d_fb, h->d_F, h->d_H2, h->d_jptr, h->d_jcol, h->d_jval};
+                    h->d_nactive, h->d_pivflag, h->d_mask, h->d_Vm0, h->d_Va0, h->d_Vmp, h->d_Vap, h->d_swapVm, h->d_swapVa, h->d_tstamp, h->d_hist, h->d_stats, h->d_J, h->d_ipiv, h->d_info, h->d_Z, h->d_w, h->d_x, h->d_linA, h->d_C, h->d_dbg, h->d_H, h->d_chG, h->d_chH, h->d_chD, h->d_chy, h->d_chZ, h->d_lfK, h->d_lfS, h->d_fb, h->d_F, h->d_H2, h->d_jptr, h->d_jcol, h->d_jval, h->d_respart, h->d_eta};
     for (void* p : ptrs)
         if (p) hipFree(p);
     tree_free(h);
@@ -1587,6 +1769,7 @@ int hpf_set_state(hpf_handle* h, int n_scen, const double* Vm, const double* Va)
         hipLaunchKernelGGL(k_init_voltages, grid2(count, n_scen), dim3(TPB), 0, h->stream, h->Hn, count, h->d_Vm, h->d_Va);
         if (launch_status(h)) return HPF_E_HIP;
     }
+    if (h->resid_check && reset_step_eta(h)) return HPF_E_HIP;       // (a new state: no step taken yet)
     HIPCHK(hipStreamSynchronize(h->stream));
     h->state_set = true;
     h->mismatch_valid = false;
@@ -1797,6 +1980,7 @@ static int iterate_enqueue(hpf_handle* h, int iters) {
             else
                 full_ctx(h);
             if ((r = newton_step<false>(h, nullptr))) break;
+            if (h->resid_check && (r = launch_step_residual(h, nullptr))) break;
             if ((r = launch_update<false>(h, nullptr))) break;
             r = launch_mismatch<false>(h, nullptr, false);
         }
@@ -1832,6 +2016,19 @@ int hpf_get_stats_dev(hpf_handle* h, void* stats_dev) {
     if (!h->state_set || h->S < 1) return HPF_E_STATE;
     HIPCHK(hipMemcpyAsync(stats_dev, h->d_stats, sizeof(hpf_stat) * h->S, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    return HPF_OK;
+}
+
+int hpf_get_step_residuals(hpf_handle* h, double* eta_last, double* eta_max) {
+    if (!h) return HPF_E_ARG;
+    if (!h->resid_check || !h->d_eta || !h->state_set || h->S < 1) return HPF_E_STATE;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (eta_last) HIPCHK(hipMemcpy(eta_last, h->d_eta, sizeof(double) * h->S, hipMemcpyDeviceToHost));
+    if (eta_max) {
+        HIPCHK(hipMemcpy(eta_max, h->d_eta + h->S_alloc, sizeof(double) * h->S, hipMemcpyDeviceToHost));
+        for (int s = 0; s < h->S; ++s)
+            if (eta_max[s] == -1.0) eta_max[s] = NAN;        // no step yet
+    }
     return HPF_OK;
 }
 
@@ -1875,6 +2072,26 @@ int hpf_set_option(hpf_handle* h, const char* name, int value) {
     if (!strcmp(name, "queue_chunk")) {             // hpf_solve_queue: Newton iterations between two harvest / refill rounds
         if (value < 1 || value > 16) return HPF_E_ARG;
         h->queue_chunk = value;
+        return HPF_OK;
+    }
+    if (!strcmp(name, "step_residual_check")) {     // 1: every harmonic Newton step's backward error on the device (k_step_residual), flags bits 6 / 7
+        if (value != 0 && value != 1) return HPF_E_ARG;
+        if (value && !h->d_eta) {
+            int rr;
+            if ((rr = dev_alloc(h, &h->d_respart, (size_t)h->S_alloc * 4 * h->errpart_stride))) return rr;
+            if ((rr = dev_alloc(h, &h->d_eta, 2 * (size_t)h->S_alloc))) return rr;
+        }
+        if (value && !h->resid_check) {
+            int rr;
+            HIPCHK(hipStreamSynchronize(h->stream));
+            if ((rr = reset_step_eta(h))) return rr;
+        }
+        h->resid_check = value;
+        return HPF_OK;
+    }
+    if (!strcmp(name, "step_residual_limit_log10")) {   // a step is flagged when its eta exceeds 10^value (-16..0, default -10)
+        if (value < -16 || value > 0) return HPF_E_ARG;
+        h->resid_limit = pow(10.0, (double)value);
         return HPF_OK;
     }
     if (!strcmp(name, "auto_repivot")) {            // 0: flagged scenarios are only reported (flags bit 3), not repeated
@@ -2014,7 +2231,16 @@ int hpf_kernel_model(const hpf_handle* h, int which, double* bytes, double* flop
     if (!h) return HPF_E_ARG;
     double by = 0.0, fl = 0.0;
     int ln = 0;
-    if (h->solver == HPF_SOLVER_BLOCK_TREE) {
+    if (which == T_RESID) {
+        // k_step_residual + k_step_eta, one scenario and step.  Bytes: Y, the pattern, U, E, the step, P and Q once (the neighbours' gathers and
+        // the mismatch's second walk of the row hit the L2; Y_N is shared by all scenarios).  Flops per stored admittance entry and harmonic: 8
+        // (the mismatch's product and sum) + 12 (two complex products of the entry) + 24 (eight fma into r and a, four sums into w); per cross
+        // term of a coupled nonlinear bus 12 + 2 + 24, and 8 for its share of the Norton injection.
+        const double Hn = h->Hn, nl = h->coupled ? (double)(h->n - h->m) : 0.0;
+        by = 16.0 * Hn * h->nnz + 4.0 * (h->nnz + 9.0 * h->n) + 16.0 * Hn * h->n * 3.0 + 16.0 * h->n;
+        fl = 44.0 * Hn * h->nnz + nl * Hn * ((Hn - 1.0) * 38.0 + Hn * 8.0);
+        ln = 2;
+    } else if (h->solver == HPF_SOLVER_BLOCK_TREE) {
         const Tree& T = active_tree(const_cast<hpf_handle*>(h));
         if (which == T_GJ && tree_levels_fused(const_cast<hpf_handle*>(h))) {      // k_level: every dense bus, one launch per level
             by = T.bytes_factor; fl = T.flops_factor; ln = T.n_levels;

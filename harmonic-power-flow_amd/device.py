@@ -262,6 +262,14 @@ class DeviceModel:
     def stats_to_device(self, data_ptr):
         self._chk(self.lib.hpf_get_stats_dev(self._h, C.c_void_p(int(data_ptr))), "hpf_get_stats_dev")
 
+    def step_residuals(self):
+        """(eta_last [S], eta_max [S]): normwise backward error of every scenario's last Newton step and the largest one of the solve
+        (hpf_get_step_residuals; needs set_option("step_residual_check", 1); NaN where no step was taken)."""
+        S = self._batch("hpf_get_step_residuals")
+        last, big = np.empty(S), np.empty(S)
+        self._chk(self.lib.hpf_get_step_residuals(self._h, _dp(last), _dp(big)), "hpf_get_step_residuals")
+        return last, big
+
     def set_option(self, name, value):
         self._chk(self.lib.hpf_set_option(self._h, name.encode(), int(value)), "hpf_set_option")
 
@@ -277,7 +285,7 @@ class DeviceModel:
 
     def timing_get(self):
         out = {}
-        for which, name in enumerate(("mismatch", "jacobian", "solve", "update", "back", "gj", "gj_dev")):
+        for which, name in enumerate(("mismatch", "jacobian", "solve", "update", "back", "gj", "gj_dev", "step_residual")):
             ms = C.c_double()
             cnt = C.c_int64()
             self._chk(self.lib.hpf_timing_get(self._h, which, C.byref(ms), C.byref(cnt)), "hpf_timing_get")
@@ -314,8 +322,9 @@ class DeviceModel:
 
     def kernel_model(self, which):
         """(algorithmic bytes, flops) of one kernel class per scenario and Newton step, launches per step and scenario group
-        (hpf_kernel_model; which: "gj" = the general factor kernel k_factor_q<B,false>, "solve" = whole factor sweep, "back")."""
+        (hpf_kernel_model; which: "gj" = the general factor kernel k_factor_q<B,false>, "solve" = whole factor sweep, "back",
+        "step_residual" = the residual check of a step)."""
         by, fl, ln = C.c_double(), C.c_double(), C.c_int32()
-        idx = {"solve": 2, "back": 4, "gj": 5}[which]
+        idx = {"solve": 2, "back": 4, "gj": 5, "step_residual": 7}[which]
         self._chk(self.lib.hpf_kernel_model(self._h, idx, C.byref(by), C.byref(fl), C.byref(ln)), "hpf_kernel_model")
         return by.value, fl.value, ln.value

@@ -82,7 +82,9 @@ typedef struct hpf_stat {
     int32_t flags;             /* bit0 converged (err <= thresh), bit1 hit max_iter, bit2 non-finite mismatch,
                                   bit3 BLOCK_TREE: a static 4x4 pivot block amplified beyond the limit during the solve,
                                   bit4 the scenario was repeated with partial pivoting (its result is the repeat's),
-                                  bit5 the pivoted elimination met an exactly zero pivot (hpf_solve returns HPF_E_SINGULAR) */
+                                  bit5 the pivoted elimination met an exactly zero pivot (hpf_solve returns HPF_E_SINGULAR),
+                                  bit6 option "step_residual_check": a Newton step of the first pass missed the residual limit,
+                                  bit7 ... a step of the pass whose result is returned did (= bit6 unless bit4 is set) */
     double  err;               /* final ||f||_inf                                        HG:389 */
     double  thd_max;           /* max over buses of THD_F                                HG:566-568 */
 } hpf_stat;
@@ -166,7 +168,7 @@ int  hpf_solve(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* 
  * solve alone (the arithmetic of a scenario does not depend on its slot).  Other handles (DENSE, meshed networks, pivoted mode) run waves of
  * S_max scenarios.  Outputs (host, may be NULL; Vm and Va together): stats [n_total], raw voltages Vm, Va [n_total][Hn*n] (stacked order,
  * signed / un-wrapped like hpf_get_state).  In the queued mode a scenario flagged by the static-pivot monitor (flags bit 3) or whose mismatch
- * turned non-finite (flags bit 2) is reported, not repeated: solve it again with hpf_solve (which repeats exactly those with partial pivoting).  Afterwards the handle holds no batch: set loads and state before per-batch calls. */
+ * turned non-finite (flags bit 2), or whose step missed the residual check (flags bit 6), is reported, not repeated: solve it again with hpf_solve (which repeats exactly those with partial pivoting).  Afterwards the handle holds no batch: set loads and state before per-batch calls. */
 int  hpf_solve_queue(hpf_handle* h, int n_total, const double* P, const double* Q, double thresh_f, int max_iter_f, double thresh,
                      int max_iter, hpf_stat* stats, double* Vm, double* Va);
 
@@ -208,6 +210,12 @@ int  hpf_sparse_solve(int device, int n, int c, int Hn, const int32_t* indptr, c
 int  hpf_get_stats(hpf_handle* h, hpf_stat* stats /* [S] host */);
 int  hpf_get_stats_dev(hpf_handle* h, void* stats_dev /* [S] hpf_stat, device memory of the caller (RCCL gather) */);
 
+/* Residual check of the Newton steps (option "step_residual_check"): eta_last [S] the normwise backward error
+ * eta = |f - J dx|_inf / (| |J| |_inf |dx|_inf + |f|_inf) of every scenario's last harmonic Newton step, eta_max [S] the largest one since
+ * hpf_solve was entered (since hpf_set_state for hpf_iterate; after a pivoted repeat: of the repeat).  NaN for a scenario that took no step.
+ * Either array may be NULL.  HPF_E_STATE without a batch or with the check off. */
+int  hpf_get_step_residuals(hpf_handle* h, double* eta_last, double* eta_max);
+
 /* Diagnostics: with env HPF_DEBUG_ABLATE & 16 the BLOCK_TREE factor kernel records shader-cycle stamps per (scenario, bus):
  * out[(s*n + k)*8 + 0..5] = assembly, packed sub-phases, packed Gauss-Jordan split, MFMA Gauss-Jordan, packed wave-0 roles,
  * Schur push (tools/stamps.py decodes them; -DHPF_FACTOR_STAMPS build only); [6] dense children,
@@ -228,6 +236,12 @@ int  hpf_debug_stamps(hpf_handle* h, long long* out, int count);
  * the system; a relative residual above 1e-10, a zero pivot or a non-finite entry repeats it with partial pivoting (hpf_tree_census[11]
  * counts those).  1 = always the pivoted LU.
  * "queue_chunk" (1..16, default 4): Newton iterations between two harvest / refill rounds of hpf_solve_queue.
+ * "step_residual_check" (0 / 1, default 0): after the linear solve of every harmonic Newton step -- hpf_solve, hpf_solve_queue, hpf_iterate; every
+ * solver and path -- one more pass over the assembly forms r = f - J dx row by row without storing J (the entries of hpf_jacobian_csr) and the
+ * scenario's normwise backward error eta (hpf_get_step_residuals).  A step with eta above 10^"step_residual_limit_log10" (-16..0, default -10:
+ * healthy steps of every path sit below 1e-12, the evaluation's own rounding below 2e-14) or a non-finite eta sets hpf_stat.flags bit 6; hpf_solve
+ * treats the scenario like one flagged by the static-pivot monitor (repeat with partial pivoting where that exists, "auto_repivot"; the check runs
+ * in the repeat too and bit 7 is the verdict on the pass whose result is returned).  Off: no launch is added, results are bit-identical.
  * "scenario_groups" (1..8, default 4; at least 32 running scenarios per group): independent scenario pipelines on separate HIP streams -- group 0
  * on the handle's own stream (hpf_set_stream), the others on streams of the handle.  The runtime maps streams onto FOUR hardware queues: with a fifth
  * stream busy at the same time (the application's own work during a solve) two groups share a queue and serialise (1.25 instead of 0.90 ms per
@@ -280,6 +294,7 @@ int  hpf_sync(hpf_handle* h);
  * 6 the same launches on the DEVICE clock: last workgroup end - first workgroup start (wall_clock64 stamps written by the kernel
  *   while timing is enabled) -- what rocprofv3 --kernel-trace reports as the kernel's duration; a HIP-event span additionally
  *   holds the event packets and the queue gaps around a ~25 us kernel.
+ * 7 the residual check of the steps (k_step_residual + k_step_eta, option "step_residual_check"; one span per Newton step and scenario group).
  * Returns total milliseconds in *ms and the number of timed spans in *launches. */
 int  hpf_timing_enable(hpf_handle* h, int on);   /* 1: HIP-event spans (classes 0..5) + device stamps (6); 2: device stamps only --
                                                     no event packets between the kernels, the launches run exactly as untimed; 0: off */
@@ -300,7 +315,8 @@ double hpf_back_bytes(const hpf_handle* h);
  * launches of one Newton step for ONE scenario, and the number of launches per step and scenario group.  which == 5: the
  * general multi-wave factor kernel k_factor_q<B,false> alone (Gauss-Jordan buses, non-batched super-leaves; the buses of the
  * scenario-batched kernels k_leaf_batch / k_sleaf_batch and of the leaf-only instantiation are NOT in it); which == 2: the
- * whole factor sweep (= hpf_solve_bytes / hpf_solve_flops); which == 4: the back sweep.  Other classes: HPF_E_ARG. */
+ * whole factor sweep (= hpf_solve_bytes / hpf_solve_flops); which == 4: the back sweep; which == 7 (every solver): the residual check of
+ * a step.  Other classes: HPF_E_ARG. */
 int  hpf_kernel_model(const hpf_handle* h, int which, double* bytes, double* flops, int* launches);
 /* Census of the BLOCK_TREE elimination tree (diagnostic; which kernel takes which bus).  counts[0..8]: buses with a dense b x b
  * block (the rest lives in the 2x2 algebra of the linear subtrees / contracted chains), Gauss-Jordan buses (k_factor_q<B,false>),

@@ -59,6 +59,10 @@ SYMBOLS = {
     "hpf_get_stats": (C.c_int, [_H, C.POINTER(hpf_stat)]),
     "hpf_get_stats_dev": (C.c_int, [_H, C.c_void_p]),
     "hpf_get_step_residuals": (C.c_int, [_H, c_dbl_p, c_dbl_p]),
+    "hpf_distortion_begin": (C.c_int, [_H, c_dbl_p, C.c_double, C.c_double, C.c_int]),
+    "hpf_distortion_add": (C.c_int, [_H, C.c_int]),
+    "hpf_distortion_get": (C.c_int, [_H] + [C.c_void_p] * 12),
+    "hpf_distortion_end": (C.c_int, [_H]),
     "hpf_debug_stamps": (C.c_int, [_H, C.POINTER(C.c_longlong), C.c_int]),
     "hpf_set_option": (C.c_int, [_H, C.c_char_p, C.c_int]),
     "hpf_set_stream": (C.c_int, [_H, C.c_void_p]),

@@ -247,6 +247,18 @@ struct hpf_handle {
     double *d_Vmp = nullptr, *d_Vap = nullptr;   // [S][Hn*n] option "keep_previous_state": the state each scenario's LAST Newton step started from
     double *d_swapVm = nullptr, *d_swapVa = nullptr;   // [S][Hn*n] hpf_jacobian(_csr)_last: the current state while the kept one stands in its place
     int queue_chunk = 4;              // option "queue_chunk": iterations between two harvest / refill rounds of hpf_solve_queue
+    // distortion accumulator (hpf_distortion_*, hpf_distortion.hpp; allocated while open only).  Entries bus-major like the state: t = i*Hn + q for
+    // x of (bus i, harmonic position q), t = n*Hn + i for the THD of bus i
+    bool dist_open = false;
+    bool solve_done = false;          // d_stats / the state belong to a finished hpf_solve of the current batch (hpf_distortion_add)
+    int dist_bins = 0;
+    int dist_id_base = 0;             // option "distortion_id_base": hpf_solve_queue adds scenario g of a call under id base + g
+    double dist_thd_limit = 0.0, dist_hist_max = 0.0, dist_inv_w = 0.0;
+    double* d_dist_f = nullptr;       // [3][n*Hn + n] max | sum | sum of squares
+    int* d_dist_arg = nullptr;        // [n*Hn + n] scenario id of the max (-1: nothing added)
+    uint32_t* d_dist_u = nullptr;     // [n*Hn + n] scenarios over the limit | [n][bins + 1] THD histogram
+    long long* d_dist_cnt = nullptr;  // [3] added, skipped, deferred
+    double* d_dist_limit = nullptr;   // [Hn]
     int keep_prev = 0;
     bool prev_valid = false;          // d_Vmp / d_Vap belong to the last hpf_solve (set_state / set_loads invalidate them)
     double* d_hist = nullptr;         // [S][hist_cap]

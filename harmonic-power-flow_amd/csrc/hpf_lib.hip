@@ -20,6 +20,7 @@
 
 #include <rocsolver/rocsolver.h>
 
+#include "hpf_distortion.hpp"
 #include "hpf_internal.hpp"
 
 using namespace hpf;
@@ -823,6 +824,59 @@ __global__ void k_queue_harvest(int n, int Hn, double thresh, int max_iter, cons
     }
 }
 
+// Distortion accumulator: the finished scenarios of a list are folded into the per-entry statistics (hpf_distortion.hpp).  One thread owns one
+// entry -- t < n*Hn: x of (bus, harmonic position) = t (bus-major like the state: consecutive threads read consecutive doubles and share the
+// bus's fundamental), t < n*Hn + n: the THD of a bus and its histogram row, t = n*Hn + n: the three scenario counters -- and walks the list in
+// order: plain loads and stores, no atomics, max / arg / counters independent of the order in which scenarios arrive.
+// List entry l: storage slots[l] (NULL: l; a negative slot ends the list), scenario number gids[l] (NULL: l) -> record stats[number], id
+// id_base + number.  queue: the caller is hpf_solve_queue (a scenario it only reports is deferred, dist_classify).
+__global__ void k_distortion_add(int n, int Hn, int L, const int* __restrict__ slots, const int* __restrict__ gids, int id_base, int queue,
+                                 const hpf_stat* __restrict__ stats, const double* __restrict__ Vm, const double* __restrict__ limit,
+                                 double thd_limit, double hist_max, double inv_w, int B, double* __restrict__ acc_f, int* __restrict__ acc_arg,
+                                 uint32_t* __restrict__ acc_u, long long* __restrict__ cnt) {
+    const int E = n * Hn, T = E + n;
+    const int t = blockIdx.x * TPB + threadIdx.x;
+    if (t > T) return;
+    if (t == T) {
+        long long c[3] = {0, 0, 0};
+        for (int l = 0; l < L; ++l) {
+            if (slots && slots[l] < 0) break;
+            const hpf_stat st = stats[gids ? gids[l] : l];
+            c[dist_classify(st.flags, st.thd_max, queue != 0)] += 1;
+        }
+        for (int k = 0; k < 3; ++k) cnt[k] = cnt[k] + c[k];
+        return;
+    }
+    const int bus = t < E ? t / Hn : t - E, q = t < E ? t - bus * Hn : 0;
+    const double lim = t < E ? limit[q] : thd_limit;
+    double mx = acc_f[t], sum = acc_f[(size_t)T + t], sumsq = acc_f[2 * (size_t)T + t];
+    int arg = acc_arg[t];
+    uint32_t over = acc_u[t];
+    uint32_t* hist = acc_u + (size_t)T + (size_t)bus * (B + 1);
+    bool any = false;
+    for (int l = 0; l < L; ++l) {
+        const int s = slots ? slots[l] : l;
+        if (s < 0) break;
+        const int g = gids ? gids[l] : l;
+        const hpf_stat st = stats[g];
+        if (dist_classify(st.flags, st.thd_max, queue != 0) != DIST_ADD) continue;
+        const double* Vbus = Vm + (size_t)s * E + (size_t)bus * Hn;
+        const double x = t < E ? dist_x(Vbus, q) : dist_thd(Vbus, Hn);
+        dist_fold(x, id_base + g, lim, mx, arg, sum, sumsq, over);
+        if (t >= E) {
+            const int b = dist_bin(x, hist_max, inv_w, B);
+            hist[b] = hist[b] + 1u;
+        }
+        any = true;
+    }
+    if (!any) return;
+    acc_f[t] = mx;
+    acc_f[(size_t)T + t] = sum;
+    acc_f[2 * (size_t)T + t] = sumsq;
+    acc_arg[t] = arg;
+    acc_u[t] = over;
+}
+
 // a new scenario moves into every storage of the new list: loads, the reference's start (HG:174-184) with the fundamental entries from
 // its power-flow seed, U / E, counters
 __global__ void k_queue_init(int n, int Hn, const int* __restrict__ newlist, const int* __restrict__ slot_scen, const double* __restrict__ qP,
@@ -1325,10 +1379,31 @@ int nr_pass(hpf_handle* h, double thresh, int max_iter, const int* mask) {
     return HPF_OK;
 }
 
+// one k_distortion_add launch on the handle's stream (the open accumulator of h): list, records and id rule as the kernel describes them
+int distortion_launch(hpf_handle* h, int L, const int* slots, const int* gids, int id_base, bool queue, const hpf_stat* stats) {
+    const int T = h->n * h->Hn + h->n;
+    hipLaunchKernelGGL(k_distortion_add, dim3((unsigned)((T + 1 + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, h->n, h->Hn, L, slots, gids, id_base,
+                       queue ? 1 : 0, stats, h->d_Vm, h->d_dist_limit, h->dist_thd_limit, h->dist_hist_max, h->dist_inv_w, h->dist_bins,
+                       h->d_dist_f, h->d_dist_arg, h->d_dist_u, h->d_dist_cnt);
+    return launch_status(h);
+}
+
+void distortion_free(hpf_handle* h) {
+    void* ptrs[] = {h->d_dist_f, h->d_dist_arg, h->d_dist_u, h->d_dist_cnt, h->d_dist_limit};
+    for (void* p : ptrs)
+        if (p) hipFree(p);
+    h->d_dist_f = h->d_dist_limit = nullptr;
+    h->d_dist_arg = nullptr;
+    h->d_dist_u = nullptr;
+    h->d_dist_cnt = nullptr;
+    h->dist_open = false;
+}
+
 template <bool FUND>
 int nr_loop(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* err, double* err_hist) {
     if (!h->loads_set || !h->state_set || h->S < 1) return HPF_E_STATE;
     if (max_iter < 0) return HPF_E_ARG;
+    h->solve_done = false;
     int r;
     const int S = h->S;
     const int cap = max_iter + 1;
@@ -1398,6 +1473,7 @@ int nr_loop(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* err
                 h->last_detail = s;
                 return HPF_E_SINGULAR;
             }
+        h->solve_done = true;
     }
     return HPF_OK;
 }
@@ -1474,6 +1550,7 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
                            hlist, hg, newlist, base);
         hipLaunchKernelGGL(k_queue_harvest, dim3((unsigned)S_max), dim3(TPB), 0, h->stream, n, Hn, thresh, max_iter, hlist, hg, h->d_Vm,
                            h->d_Va, h->d_err, h->d_niter, h->d_pivflag, qst, qVm, qVa);
+        if (h->dist_open && distortion_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;   // (before the storages are refilled)
         hipLaunchKernelGGL(k_queue_init, grid2((int)count, S_max), dim3(TPB), 0, h->stream, n, Hn, newlist, slot_scen, qP, qQ, sVm, sVa,
                            h->d_P, h->d_Q, h->d_Vm, h->d_Va, h->d_U, h->d_E, h->d_niter, h->d_pivflag);
         set_ctx(h, h->stream, 0, S_max);
@@ -1525,7 +1602,7 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
                hipMemcpy(Va, qVa, sizeof(double) * (size_t)n_total * count, hipMemcpyDeviceToHost) != hipSuccess))
         return cleanup(HPF_E_HIP);
     // the handle is left without a defined batch: loads and state have to be set again before the per-batch entry points
-    h->loads_set = h->state_set = false;
+    h->loads_set = h->state_set = h->solve_done = false;
     h->S = 0;
     return cleanup(HPF_OK);
 }
@@ -1536,6 +1613,7 @@ void free_all(hpf_handle* h) {
                     h->d_nactive, h->d_pivflag, h->d_mask, h->d_Vm0, h->d_Va0, h->d_Vmp, h->d_Vap, h->d_swapVm, h->d_swapVa, h->d_tstamp, h->d_hist, h->d_stats, h->d_J, h->d_ipiv, h->d_info, h->d_Z, h->d_w, h->d_x, h->d_linA, h->d_C, h->d_dbg, h->d_H, h->d_chG, h->d_chH, h->d_chD, h->d_chy, h->d_chZ, h->d_lfK, h->d_lfS, h->d_fb, h->d_F, h->d_H2, h->d_jptr, h->d_jcol, h->d_jval, h->d_respart, h->d_eta};
     for (void* p : ptrs)
         if (p) hipFree(p);
+    distortion_free(h);
     tree_free(h);
     for (auto& sp : h->spans) {
         hipEventDestroy(sp.e0);
@@ -1744,6 +1822,7 @@ int hpf_set_loads(hpf_handle* h, int n_scen, const double* P, const double* Q) {
     h->loads_set = true;
     h->mismatch_valid = false;
     h->prev_valid = false;
+    h->solve_done = false;
     return HPF_OK;
 }
 
@@ -1774,6 +1853,7 @@ int hpf_set_state(hpf_handle* h, int n_scen, const double* Vm, const double* Va)
     h->state_set = true;
     h->mismatch_valid = false;
     h->prev_valid = false;
+    h->solve_done = false;
     return HPF_OK;
 }
 
@@ -1955,10 +2035,11 @@ int hpf_solve_queue(hpf_handle* h, int n_total, const double* P, const double* Q
         if ((r = hpf_set_state(h, S, nullptr, nullptr))) return r;
         if ((r = hpf_fund_pf(h, thresh_f, max_iter_f, nullptr, nullptr, nullptr))) return r;
         if ((r = hpf_solve(h, thresh, max_iter, nullptr, nullptr, nullptr))) return r;
+        if (h->dist_open && (r = distortion_launch(h, S, nullptr, nullptr, h->dist_id_base + g0, true, h->d_stats))) return r;
         if (stats && (r = hpf_get_stats(h, stats + g0))) return r;
         if (Vm && (r = hpf_get_state(h, Vm + (size_t)g0 * cnt, Va + (size_t)g0 * cnt))) return r;
     }
-    h->loads_set = h->state_set = false;                 // (as on the queued path: the handle is left without a defined batch)
+    h->loads_set = h->state_set = h->solve_done = false;   // (as on the queued path: the handle is left without a defined batch)
     h->S = 0;
     return HPF_OK;
 }
@@ -1998,6 +2079,7 @@ static int iterate_enqueue(hpf_handle* h, int iters) {
 int hpf_iterate(hpf_handle* h, int iters) {
     if (!h || iters < 0) return HPF_E_ARG;
     if (!h->loads_set || !h->state_set || !h->mismatch_valid) return HPF_E_STATE;
+    h->solve_done = false;
     // (replaying a captured hipGraph of several iterations was measured again in round 2, with 3 / 4 / 6 / 8 scenario groups at
     //  128 and 1 024 scenarios: 0..-6 % -- the step is not bound by the host's launch rate)
     return iterate_enqueue(h, iters);
@@ -2029,6 +2111,87 @@ int hpf_get_step_residuals(hpf_handle* h, double* eta_last, double* eta_max) {
         for (int s = 0; s < h->S; ++s)
             if (eta_max[s] == -1.0) eta_max[s] = NAN;        // no step yet
     }
+    return HPF_OK;
+}
+
+int hpf_distortion_begin(hpf_handle* h, const double* limit, double thd_limit, double hist_max, int hist_bins) {
+    if (!h || hist_bins < 1 || hist_bins > 256 || !(hist_max > 0.0) || isinf(hist_max) || thd_limit != thd_limit) return HPF_E_ARG;
+    std::vector<double> lim((size_t)h->Hn, (double)INFINITY);
+    for (int q = 0; limit && q < h->Hn; ++q) {
+        if (limit[q] != limit[q]) return HPF_E_ARG;
+        lim[q] = limit[q];
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    distortion_free(h);                                  // (an open accumulator is reset; the bin count may differ)
+    const size_t T = (size_t)h->n * h->Hn + h->n, nu = T + (size_t)h->n * (hist_bins + 1);
+    int r;
+    if ((r = dev_alloc(h, &h->d_dist_f, 3 * T)) || (r = dev_alloc(h, &h->d_dist_arg, T)) || (r = dev_alloc(h, &h->d_dist_u, nu)) ||
+        (r = dev_alloc(h, &h->d_dist_cnt, (size_t)3)) || (r = dev_upload(h, &h->d_dist_limit, lim.data(), lim.size()))) {
+        distortion_free(h);
+        return r;
+    }
+    HIPCHK(hipMemsetAsync(h->d_dist_f, 0, sizeof(double) * 3 * T, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_dist_arg, 0xff, sizeof(int) * T, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_dist_u, 0, sizeof(uint32_t) * nu, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_dist_cnt, 0, sizeof(long long) * 3, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->dist_bins = hist_bins;
+    h->dist_thd_limit = thd_limit;
+    h->dist_hist_max = hist_max;
+    h->dist_inv_w = (double)hist_bins / hist_max;
+    h->dist_open = true;
+    return HPF_OK;
+}
+
+int hpf_distortion_add(hpf_handle* h, int first_id) {
+    if (!h || first_id < 0) return HPF_E_ARG;
+    if (!h->dist_open || !h->loads_set || !h->state_set || h->S < 1 || !h->solve_done) return HPF_E_STATE;
+    int r;
+    if ((r = distortion_launch(h, h->S, nullptr, nullptr, first_id, false, h->d_stats))) return r;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return HPF_OK;
+}
+
+int hpf_distortion_get(hpf_handle* h, int64_t* counts, double* x_max, int32_t* x_arg, double* x_sum, double* x_sumsq, uint32_t* x_over,
+                       double* thd_max, int32_t* thd_arg, double* thd_sum, double* thd_sumsq, uint32_t* thd_over, uint32_t* thd_hist) {
+    if (!h) return HPF_E_ARG;
+    if (!h->dist_open) return HPF_E_STATE;
+    const int n = h->n, Hn = h->Hn;
+    const size_t E = (size_t)n * Hn, T = E + n, nu = T + (size_t)n * (h->dist_bins + 1);
+    std::vector<double> f(3 * T);
+    std::vector<int32_t> arg(T);
+    std::vector<uint32_t> u(nu);
+    long long cnt[3];
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(f.data(), h->d_dist_f, sizeof(double) * 3 * T, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(arg.data(), h->d_dist_arg, sizeof(int32_t) * T, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(u.data(), h->d_dist_u, sizeof(uint32_t) * nu, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cnt, h->d_dist_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
+    for (int k = 0; counts && k < 3; ++k) counts[k] = cnt[k];
+    double* xf[3] = {x_max, x_sum, x_sumsq};
+    double* tf[3] = {thd_max, thd_sum, thd_sumsq};
+    for (int a = 0; a < 3; ++a) {
+        if (tf[a]) memcpy(tf[a], f.data() + a * T + E, sizeof(double) * n);
+        if (!xf[a]) continue;
+        for (int q = 0; q < Hn; ++q)                         // device bus-major -> ABI stacked order
+            for (int i = 0; i < n; ++i) xf[a][(size_t)q * n + i] = f[a * T + (size_t)i * Hn + q];
+    }
+    for (int q = 0; q < Hn; ++q)
+        for (int i = 0; i < n; ++i) {
+            if (x_arg) x_arg[(size_t)q * n + i] = arg[(size_t)i * Hn + q];
+            if (x_over) x_over[(size_t)q * n + i] = u[(size_t)i * Hn + q];
+        }
+    if (thd_arg) memcpy(thd_arg, arg.data() + E, sizeof(int32_t) * n);
+    if (thd_over) memcpy(thd_over, u.data() + E, sizeof(uint32_t) * n);
+    if (thd_hist) memcpy(thd_hist, u.data() + T, sizeof(uint32_t) * (size_t)n * (h->dist_bins + 1));
+    return HPF_OK;
+}
+
+int hpf_distortion_end(hpf_handle* h) {
+    if (!h) return HPF_E_ARG;
+    if (!h->dist_open) return HPF_OK;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    distortion_free(h);
     return HPF_OK;
 }
 
@@ -2092,6 +2255,11 @@ int hpf_set_option(hpf_handle* h, const char* name, int value) {
     if (!strcmp(name, "step_residual_limit_log10")) {   // a step is flagged when its eta exceeds 10^value (-16..0, default -10)
         if (value < -16 || value > 0) return HPF_E_ARG;
         h->resid_limit = pow(10.0, (double)value);
+        return HPF_OK;
+    }
+    if (!strcmp(name, "distortion_id_base")) {      // hpf_solve_queue with the distortion accumulator open: scenario g of a call gets id value + g
+        if (value < 0) return HPF_E_ARG;
+        h->dist_id_base = value;
         return HPF_OK;
     }
     if (!strcmp(name, "auto_repivot")) {            // 0: flagged scenarios are only reported (flags bit 3), not repeated

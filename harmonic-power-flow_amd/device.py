@@ -270,6 +270,37 @@ class DeviceModel:
         self._chk(self.lib.hpf_get_step_residuals(self._h, _dp(last), _dp(big)), "hpf_get_step_residuals")
         return last, big
 
+    # -- distortion accumulator (hpf_distortion_*) ----------------------------------------------------------
+    def distortion_begin(self, limit=None, thd_limit=np.inf, hist_max=1.0, bins=64):
+        """Open (or reset) the handle's distortion accumulator: from now on every converged scenario hpf_solve_queue harvests, and every batch
+        handed to distortion_add, is folded into per-bus / per-harmonic statistics on the device.  limit [Hn] (None: no limits): x_over counts
+        the scenarios with x[q][i] > limit[q]; thd_limit likewise for THD; the THD histogram has `bins` (1..256) uniform bins on [0, hist_max)."""
+        lim = None if limit is None else np.ascontiguousarray(limit, dtype=np.float64)
+        assert lim is None or lim.shape == (self.Hn,)
+        self._chk(self.lib.hpf_distortion_begin(self._h, _dp(lim) if lim is not None else None, float(thd_limit), float(hist_max), int(bins)),
+                  "hpf_distortion_begin")
+        self._dist = (lim, float(thd_limit), float(hist_max), int(bins))
+
+    def distortion_add(self, first_id=0):
+        """Fold the current batch (after solve()) into the accumulator, scenario s under id first_id + s."""
+        self._chk(self.lib.hpf_distortion_add(self._h, int(first_id)), "hpf_distortion_add")
+
+    def distortion_get(self):
+        """-> sweep.DistortionStats of everything added since distortion_begin (arrays in the ABI's order [Hn][n]); the accumulator stays open."""
+        from .sweep import DistortionStats
+        dist = getattr(self, "_dist", None)
+        bins = dist[3] if dist else 1
+        a = {name: np.zeros(shape, dtype=dt) for name, dt, shape in zip(
+            DistortionStats.ARRAYS, DistortionStats.DTYPES,
+            ((3,),) + ((self.Hn, self.n),) * 5 + ((self.n,),) * 5 + ((self.n, bins + 1),))}
+        self._chk(self.lib.hpf_distortion_get(self._h, *[a[name].ctypes.data_as(C.c_void_p) for name in DistortionStats.ARRAYS]),
+                  "hpf_distortion_get")
+        return DistortionStats(self.harmonics, dist[0], dist[1], dist[2], **a)
+
+    def distortion_end(self):
+        self._chk(self.lib.hpf_distortion_end(self._h), "hpf_distortion_end")
+        self._dist = None
+
     def set_option(self, name, value):
         self._chk(self.lib.hpf_set_option(self._h, name.encode(), int(value)), "hpf_set_option")
 

@@ -25,7 +25,129 @@ def gather_stats(rec, world):
     return torch.stack(parts, dim=1).reshape(-1, rec.shape[1])
 
 
-def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_iter_h=50, want_voltages=False, refill=True):
+class DistortionStats:
+    """Per-bus / per-harmonic distortion statistics of a sweep, as the device accumulated them (hpf_distortion_*, include/hpf.h) -- a plain
+    container of NumPy arrays.  x [Hn][n]: the fundamental magnitude |V_1| (p.u.) at harmonic position 0, the individual harmonic distortion
+    |V_h| / |V_1| above; thd [n]: THD_F per bus.
+    counts [3] int64: scenarios added, skipped (not converged, or a non-finite THD), deferred (reported by the queue, added by their re-solve);
+    x_max / x_arg, thd_max / thd_arg: largest value and the scenario id it came from (ties: the smallest id; -1: nothing added);
+    x_sum / x_sumsq, thd_sum / thd_sumsq: sums over the added scenarios; x_over / thd_over: scenarios above `limit[q]` / `thd_limit`;
+    thd_hist [n][bins + 1]: `bins` uniform bins on [0, hist_max), the last one counts thd >= hist_max."""
+    ARRAYS = ("counts", "x_max", "x_arg", "x_sum", "x_sumsq", "x_over", "thd_max", "thd_arg", "thd_sum", "thd_sumsq", "thd_over", "thd_hist")
+    DTYPES = (np.int64, np.float64, np.int32, np.float64, np.float64, np.uint32, np.float64, np.int32, np.float64, np.float64, np.uint32,
+              np.uint32)
+
+    def __init__(self, harmonics, limit, thd_limit, hist_max, **arrays):
+        self.harmonics = list(harmonics)
+        self.limit = np.full(len(self.harmonics), np.inf) if limit is None else np.array(limit, dtype=np.float64)
+        self.thd_limit, self.hist_max = float(thd_limit), float(hist_max)
+        for name, dt in zip(self.ARRAYS, self.DTYPES):
+            setattr(self, name, np.ascontiguousarray(arrays[name], dtype=dt))
+        assert self.x_max.ndim == 2 and self.x_max.shape[0] == len(self.harmonics) and self.thd_hist.shape[0] == self.x_max.shape[1]
+
+    @property
+    def added(self):
+        return int(self.counts[0])
+
+    @property
+    def bins(self):
+        return self.thd_hist.shape[1] - 1
+
+    def mean(self):
+        """-> (mean of x [Hn][n], mean of thd [n]) over the added scenarios (NaN when nothing was added)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.x_sum / self.added, self.thd_sum / self.added
+
+    def std(self):
+        """-> (population standard deviation of x [Hn][n], of thd [n]) from sum and sum of squares."""
+        mx, mt = self.mean()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (np.sqrt(np.maximum(self.x_sumsq / self.added - mx * mx, 0.0)),
+                    np.sqrt(np.maximum(self.thd_sumsq / self.added - mt * mt, 0.0)))
+
+    def thd_percentile(self, p):
+        """Per bus [n]: an UPPER BOUND of the p-th percentile of THD over the added scenarios, from the histogram -- the upper edge of the bin
+        that holds the sample np.percentile(..., method="higher") would return (sorted sample number ceil(p/100 (added - 1)) + 1), so it
+        exceeds that sample by at most one bin width hist_max / bins; inf when the sample sits in the overflow bin (thd >= hist_max).
+        Conservative by construction: a limit check against it never passes a bus the exact percentile would fail."""
+        if self.added < 1:
+            return np.full(self.thd_hist.shape[0], np.nan)
+        rank = int(np.ceil((self.added - 1) * (p / 100.0))) + 1
+        b = (np.cumsum(self.thd_hist.astype(np.int64), axis=1) >= rank).argmax(axis=1)
+        edges = np.append((np.arange(self.bins) + 1) * (self.hist_max / self.bins), np.inf)
+        return edges[b]
+
+    def worst(self, k=1):
+        """The k buses with the largest thd_max -> list of (bus, scenario id, value), largest first."""
+        order = np.argsort(-self.thd_max, kind="stable")[:k]
+        return [(int(i), int(self.thd_arg[i]), float(self.thd_max[i])) for i in order]
+
+    def merge(self, other):
+        """Statistics of the union of two disjoint sets of scenarios (another GPU's share, another piece of a sweep): max with the smaller-id
+        tie rule, integer adds, float adds.  Refuses different harmonics / limits / bins / shapes."""
+        if (self.harmonics != other.harmonics or self.x_max.shape != other.x_max.shape or self.thd_hist.shape != other.thd_hist.shape or
+                not np.array_equal(self.limit, other.limit) or self.thd_limit != other.thd_limit or self.hist_max != other.hist_max):
+            raise ValueError("DistortionStats.merge: the two accumulators were opened with different settings or shapes")
+        out = {"counts": self.counts + other.counts, "thd_hist": self.thd_hist + other.thd_hist}
+        for pre in ("x", "thd"):
+            ma, aa, mb, ab = (getattr(o, pre + f) for o in (self, other) for f in ("_max", "_arg"))
+            take = (ab >= 0) & ((aa < 0) | (mb > ma) | ((mb == ma) & (ab < aa)))
+            out[pre + "_max"], out[pre + "_arg"] = np.where(take, mb, ma), np.where(take, ab, aa)
+            for f in ("_sum", "_sumsq", "_over"):
+                out[pre + f] = getattr(self, pre + f) + getattr(other, pre + f)
+        return DistortionStats(self.harmonics, self.limit, self.thd_limit, self.hist_max, **out)
+
+    def with_ids(self, ids):
+        """The same statistics with every scenario id k in x_arg / thd_arg replaced by ids[k] (-1 stays)."""
+        ids = np.asarray(ids)
+        out = {name: getattr(self, name) for name in self.ARRAYS}
+        for f in ("x_arg", "thd_arg"):
+            a = out[f]
+            out[f] = np.where(a >= 0, ids[np.maximum(a, 0)], -1)
+        return DistortionStats(self.harmonics, self.limit, self.thd_limit, self.hist_max, **out)
+
+    def pack(self):
+        """-> one uint8 array holding every array (the payload of gather_distortion)."""
+        return np.concatenate([getattr(self, name).reshape(-1).view(np.uint8) for name in self.ARRAYS])
+
+    def unpack(self, raw):
+        """A DistortionStats with this one's settings and shapes and the arrays of `raw` (what pack() of a peer produced)."""
+        raw = np.ascontiguousarray(raw, dtype=np.uint8)
+        out, o = {}, 0
+        for name in self.ARRAYS:
+            a = getattr(self, name)
+            out[name] = raw[o:o + a.nbytes].view(a.dtype).reshape(a.shape).copy()
+            o += a.nbytes
+        assert o == raw.size
+        return DistortionStats(self.harmonics, self.limit, self.thd_limit, self.hist_max, **out)
+
+
+def gather_distortion(stats, world, ids=None):
+    """Distortion statistics of a multi-GPU sweep.  The device numbers the scenarios of a rank locally (`distortion_id_base` + index in the call,
+    `first_id` + s); `ids[k]` = global id of local scenario k (`scenario_ids(rank, world, per_rank)`) is applied to x_arg / thd_arg on the host
+    first, then ONE all_gather of the packed arrays (a few hundred KB per rank) and a merge in rank order -- every rank returns the same
+    statistics, bit for bit.  world == 1 returns its argument (ids applied), like gather_stats.  Every rank must have opened its accumulator
+    with the same settings."""
+    if ids is not None:
+        stats = stats.with_ids(ids)
+    if world == 1:
+        return stats
+    import torch
+    import torch.distributed as dist
+    mine = torch.from_numpy(stats.pack())
+    backend = dist.get_backend()
+    if backend == "nccl":
+        mine = mine.cuda()
+    parts = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(parts, mine)
+    out = None
+    for p in parts:
+        s = stats.unpack(p.cpu().numpy())
+        out = s if out is None else out.merge(s)
+    return out
+
+
+def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_iter_h=50, want_voltages=False, refill=True, distortion=None):
     """Monte-Carlo / what-if sweep on ONE GPU: every row of P, Q [n_scen][n] (p.u. loads, HG:197,372) is one scenario of the
     network `dm` (a DeviceModel) holds -- the reference's counterpart is one hpf() call per load case (HG:511).  Per scenario:
     reference start (HG:174-184), fundamental pf (HG:244), harmonic NR with the reference's stop rule (HG:536).
@@ -37,7 +159,25 @@ def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_i
     static-pivot kernels (bit 2), or whose step missed the residual check (bit 6, option "step_residual_check"), is solved again on its own through `hpf_solve`, which repeats exactly those with partial pivoting.
     refill=False: fixed waves of up to S_max scenarios (each through fund_pf + solve).
     -> structured array of per-scenario records (n_iter, flags, err, thd_max: the 24-byte record of the multi-GPU gather)
-    [+ raw Vm, Va [n_scen][Hn*n]]; every record and voltage is bit-identical to the scenario solved alone."""
+    [+ raw Vm, Va [n_scen][Hn*n]]; every record and voltage is bit-identical to the scenario solved alone.
+    distortion: None (default), or a dict {"limit": [Hn] or None, "thd_limit": x, "hist_max": x, "bins": 1..256} (missing keys: no limits,
+    hist_max 1.0, 64 bins): the handle's distortion accumulator is opened for the sweep, every converged scenario is folded in on the device
+    under its row number in P (queue pieces through "distortion_id_base", re-solved flagged scenarios and the waves of refill=False through
+    distortion_add), and the DistortionStats are returned as an additional last element; records and voltages are unchanged."""
+    if distortion is not None:
+        dm.distortion_begin(distortion.get("limit"), distortion.get("thd_limit", np.inf), distortion.get("hist_max", 1.0),
+                            distortion.get("bins", 64))
+        try:
+            res = _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, True)
+            stats = dm.distortion_get()
+        finally:
+            dm.set_option("distortion_id_base", 0)
+            dm.distortion_end()
+        return (res + (stats,)) if want_voltages else (res, stats)
+    return _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, False)
+
+
+def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion):
     P = np.ascontiguousarray(np.atleast_2d(P), dtype=np.float64)
     Q = np.ascontiguousarray(np.atleast_2d(Q), dtype=np.float64)
     n_scen = P.shape[0]
@@ -52,6 +192,8 @@ def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_i
         dm.set_state(None, None, n_scen=b - a)
         dm.fund_pf(thresh_f, max_iter_f)
         dm.solve(thresh_h, max_iter_h)
+        if distortion:
+            dm.distortion_add(a)
         st = dm.stats()
         for k in STAT_DTYPE.names:
             out[k][a:b] = st[k]
@@ -66,6 +208,8 @@ def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_i
     per_call = n_scen if not want_voltages else max(dm.S_max, int(8e9 // (16 * dm.n * dm.Hn)))
     for a in range(0, n_scen, per_call):
         b = min(a + per_call, n_scen)
+        if distortion:
+            dm.set_option("distortion_id_base", a)
         res = dm.solve_queue(P[a:b], Q[a:b], thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages=want_voltages)
         if want_voltages:
             rec, Vm[a:b], Va[a:b] = res

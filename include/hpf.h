@@ -216,6 +216,39 @@ int  hpf_get_stats_dev(hpf_handle* h, void* stats_dev /* [S] hpf_stat, device me
  * Either array may be NULL.  HPF_E_STATE without a batch or with the check off. */
 int  hpf_get_step_residuals(hpf_handle* h, double* eta_last, double* eta_max);
 
+/* Distortion accumulator: per-bus / per-harmonic statistics of a sweep, accumulated on the device (the reference's counterpart is a loop of hpf() calls
+ * with get_THD, HG:563-572, and a reduction of all returned voltages on the host).  While the accumulator of a handle is open, every scenario that
+ * finishes CONVERGED is folded into small device arrays, from the raw signed magnitudes Vm the handle holds (q = harmonic position, i = bus):
+ *   x[0][i] = |Vm[0][i]| (fundamental, p.u.),  x[q][i] = |Vm[q][i]| / |Vm[0][i]| for q >= 1 (individual harmonic distortion),
+ *   thd[i] = sqrt(sum_{q>=1} Vm[q][i]^2) / |Vm[0][i]| (the arithmetic of hpf_stat.thd_max: sequential sum over ascending q).
+ * One thread owns one entry and walks the scenarios (k_distortion_add, one launch per harvest round of hpf_solve_queue / per hpf_distortion_add; no
+ * floating-point atomics): max, arg and the integer counters are bit-identical whatever the slot count, queue chunk, scenario groups or number of
+ * GPUs; only the four sum arrays depend on the order in which scenarios finish, by rounding alone.  Closed (the default): nothing is allocated, no
+ * kernel is launched, every output of every entry point is unchanged; open: records and voltages are unchanged too (it only reads the state).
+ * hpf_distortion_begin: allocate, zero, open; on an open accumulator: reset.  limit [Hn] (NULL: +inf) and thd_limit: the `over` arrays count the
+ *   scenarios with x[q][i] > limit[q] / thd[i] > thd_limit (strictly).  The THD histogram has hist_bins (1..256) uniform bins on [0, hist_max) and
+ *   an overflow bin: bin = thd >= hist_max ? hist_bins : (int)(thd * inv_w), inv_w = hist_bins / hist_max formed once in double.  HPF_E_ARG for
+ *   bins outside 1..256, hist_max not in (0, inf), a NaN limit.
+ * hpf_distortion_add: fold the handle's CURRENT BATCH in, scenario s under id first_id + s (first_id >= 0).  HPF_E_STATE without a batch, unless
+ *   hpf_solve was the last call that touched the batch, or with the accumulator closed.  A scenario that did not converge (hpf_stat.flags bit 0
+ *   clear) or has a non-finite thd counts as skipped.
+ * hpf_solve_queue with the accumulator open folds every scenario in by itself, under id base + g (g = its index in the call, base = option
+ *   "distortion_id_base", so that a sweep cut into several calls keeps global ids) -- every solver and path (the waves of DENSE / meshed / pivoted
+ *   handles after each wave).  A scenario whose record has flags bit 2, 3 or 6 (the ones the queue reports for a re-solve through hpf_solve) is NOT
+ *   added but counted as deferred: the caller's re-solve adds it with hpf_distortion_add.
+ * hpf_distortion_get: copies out whichever arrays are non-NULL, in the ABI's stacked order; leaves the accumulator open.  HPF_E_STATE when closed.
+ *   counts [3] int64: scenarios added, skipped, deferred
+ *   x_max [Hn][n] double, x_arg [Hn][n] int32: largest x and the id of the scenario it came from (ties: the smallest id; 0 / -1 before the first add)
+ *   x_sum, x_sumsq [Hn][n] double: sum of x, of x^2 over the added scenarios;  x_over [Hn][n] uint32: scenarios with x > limit[q]
+ *   thd_max [n] double, thd_arg [n] int32, thd_sum, thd_sumsq [n] double, thd_over [n] uint32: the same five for thd[i] against thd_limit
+ *   thd_hist [n][hist_bins + 1] uint32: histogram of thd[i], last bin = overflow
+ * hpf_distortion_end: free (HPF_OK when already closed); hpf_destroy frees an open one.  All four: HPF_E_ARG for a NULL handle, before any HIP call. */
+int  hpf_distortion_begin(hpf_handle* h, const double* limit, double thd_limit, double hist_max, int hist_bins);
+int  hpf_distortion_add(hpf_handle* h, int first_id);
+int  hpf_distortion_get(hpf_handle* h, int64_t* counts, double* x_max, int32_t* x_arg, double* x_sum, double* x_sumsq, uint32_t* x_over,
+                        double* thd_max, int32_t* thd_arg, double* thd_sum, double* thd_sumsq, uint32_t* thd_over, uint32_t* thd_hist);
+int  hpf_distortion_end(hpf_handle* h);
+
 /* Diagnostics: with env HPF_DEBUG_ABLATE & 16 the BLOCK_TREE factor kernel records shader-cycle stamps per (scenario, bus):
  * out[(s*n + k)*8 + 0..5] = assembly, packed sub-phases, packed Gauss-Jordan split, MFMA Gauss-Jordan, packed wave-0 roles,
  * Schur push (tools/stamps.py decodes them; -DHPF_FACTOR_STAMPS build only); [6] dense children,
@@ -242,6 +275,7 @@ int  hpf_debug_stamps(hpf_handle* h, long long* out, int count);
  * healthy steps of every path sit below 1e-12, the evaluation's own rounding below 2e-14) or a non-finite eta sets hpf_stat.flags bit 6; hpf_solve
  * treats the scenario like one flagged by the static-pivot monitor (repeat with partial pivoting where that exists, "auto_repivot"; the check runs
  * in the repeat too and bit 7 is the verdict on the pass whose result is returned).  Off: no launch is added, results are bit-identical.
+ * "distortion_id_base" (>= 0, default 0): with the distortion accumulator open, hpf_solve_queue adds scenario g of a call under id value + g.
  * "scenario_groups" (1..8, default 4; at least 32 running scenarios per group): independent scenario pipelines on separate HIP streams -- group 0
  * on the handle's own stream (hpf_set_stream), the others on streams of the handle.  The runtime maps streams onto FOUR hardware queues: with a fifth
  * stream busy at the same time (the application's own work during a solve) two groups share a queue and serialise (1.25 instead of 0.90 ms per

@@ -63,6 +63,13 @@ SYMBOLS = {
     "hpf_distortion_add": (C.c_int, [_H, C.c_int]),
     "hpf_distortion_get": (C.c_int, [_H] + [C.c_void_p] * 12),
     "hpf_distortion_end": (C.c_int, [_H]),
+    "hpf_num_branches": (C.c_int, [_H]),
+    "hpf_get_branches": (C.c_int, [_H, c_int_p, c_int_p, c_int_p]),
+    "hpf_branch_flows": (C.c_int, [_H] + [c_dbl_p] * 6),
+    "hpf_branch_stats_begin": (C.c_int, [_H, c_dbl_p]),
+    "hpf_branch_stats_add": (C.c_int, [_H, C.c_int]),
+    "hpf_branch_stats_get": (C.c_int, [_H] + [C.c_void_p] * 14),
+    "hpf_branch_stats_end": (C.c_int, [_H]),
     "hpf_debug_stamps": (C.c_int, [_H, C.POINTER(C.c_longlong), C.c_int]),
     "hpf_set_option": (C.c_int, [_H, C.c_char_p, C.c_int]),
     "hpf_set_stream": (C.c_int, [_H, C.c_void_p]),

@@ -472,14 +472,81 @@ def get_THD(V):
     return pd.DataFrame({"THD_F": thd_f, "THD_R": thd_r})
 
 
+def line_branches(lines, br_from, br_to, n):
+    """Map every row of `lines` (fromID, toID: 1-based bus IDs) to its branch -> (branch [L] int, sign [L] float): branch e = the stored pair
+    (min, max) of the line's two buses (parallel lines share one: the matrix holds the last of them, HG:150-155), sign +1 where the line runs
+    from the lower-numbered bus to the higher (the branch's own direction), -1 otherwise.  A line from a bus to itself has no branch: -1, NaN."""
+    f = lines.fromID.to_numpy(dtype=np.int64) - 1
+    t = lines.toID.to_numpy(dtype=np.int64) - 1
+    key = np.minimum(f, t) * n + np.maximum(f, t)
+    bkey = np.asarray(br_from, dtype=np.int64) * n + np.asarray(br_to, dtype=np.int64)      # ascending: CSR order
+    e = np.minimum(np.searchsorted(bkey, key), max(len(bkey) - 1, 0))
+    hit = (f != t) & (bkey[e] == key if len(bkey) else np.zeros(len(key), bool))
+    return np.where(hit, e, -1), np.where(hit, np.where(f < t, 1.0, -1.0), np.nan)
+
+
+def _line_results(V, lines, buses):
+    """Branch flows of the voltage frame V on the GPU (a borrowed assembly-only handle, like harmonic_mismatch), mapped to the rows of `lines`
+    -> harmonics, branch of every line, sign of every line, the flows dict, series admittances y [Hn][nb]."""
+    n = len(buses)
+    harmonics = list(dict.fromkeys(V.index.get_level_values(0)))
+    Y = build_admittance_matrices(buses, lines, harmonics)
+    with _borrow_model(buses, Y, None, False, harmonics, solver="dense", assembly_only=True) as dm:
+        dm.set_state(*_state_arrays(V))
+        fl = dm.branch_flows()
+        br_from, br_to, ypos = dm.branches()
+    e, sign = line_branches(lines, br_from, br_to, n)
+    return harmonics, e, sign, fl, -Y.Yval[:, ypos]
+
+
+def _take(a, e):
+    """a [..., nb] at the branches e [L] (-1: NaN)"""
+    out = np.full(a.shape[:-1] + (len(e),), np.nan, dtype=a.dtype)
+    ok = e >= 0
+    out[..., ok] = a[..., e[ok]]
+    return out
+
+
+def line_flows(V, lines, buses, settings=None):
+    """Harmonic current and series loss of every line for the voltages in DataFrame `V` (not in the reference: its current_balance, HG:326-357,
+    forms bus injections only) -> DataFrame indexed (harmonic, line) with fromID, toID, I_m, I_a (p.u. / rad, positive from the line's fromID to
+    its toID) and loss (p.u., R |I|^2 with R = Re(1 / y) of the branch).  The currents are evaluated on the GPU (hpf_branch_flows); every row of
+    `lines` is mapped to the branch of the admittance matrix that holds its bus pair, so parallel lines report the one line the matrix contains
+    (HG:150-155)."""
+    harmonics, e, sign, fl, y = _line_results(V, lines, buses)
+    Ib = fl["I"][0]                                                     # [Hn][nb]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        lb = np.where(np.abs(y) > 0, y.real / (y.real * y.real + y.imag * y.imag) * (Ib.real * Ib.real + Ib.imag * Ib.imag), 0.0)
+    I = _take(Ib, e) * sign
+    Hn = len(harmonics)
+    idx = pd.MultiIndex.from_product([harmonics, lines.index.values], names=["harmonic", "line"])
+    return pd.DataFrame({"fromID": np.tile(lines.fromID.to_numpy(), Hn), "toID": np.tile(lines.toID.to_numpy(), Hn),
+                         "I_m": np.abs(I).reshape(-1), "I_a": np.angle(I).reshape(-1), "loss": _take(lb, e).reshape(-1)}, index=idx)
+
+
+def line_summary(V, lines, buses, settings=None):
+    """Per line of `lines` (same index) for the voltages in `V`: I_rms (RMS current over all harmonics, p.u.: the thermal loading), THD_I
+    (harmonic over fundamental current; inf / NaN on a line without fundamental current), loss and loss_harm (series loss over all harmonics / over
+    the harmonics above the fundamental, p.u.) -- the device's sums over ascending harmonics (hpf_branch_flows)."""
+    harmonics, e, sign, fl, y = _line_results(V, lines, buses)
+    return pd.DataFrame({"fromID": lines.fromID.to_numpy(), "toID": lines.toID.to_numpy(), "I_rms": _take(fl["irms"][0], e),
+                         "THD_I": _take(fl["thd_i"][0], e), "loss": _take(fl["loss"][0], e), "loss_harm": _take(fl["loss_harm"][0], e)},
+                        index=lines.index)
+
+
 def solve(filename_buses, filename_lines, coupled=True, settings=None, ne_dir=None, solver="auto", verbose=False, extra_iters=0,
-          check_steps=False):
-    """Convenience wrapper (= init_network + hpf + get_THD) -> dict(V, err_h, n_iter_h, THD, details).  check_steps: see hpf."""
+          check_steps=False, line_flows=False):
+    """Convenience wrapper (= init_network + hpf + get_THD) -> dict(V, err_h, n_iter_h, THD, details).  check_steps: see hpf.
+    line_flows=True adds the keys "line_flows" and "line_summary" (the two functions of that name on the result)."""
     st = settings or globals()["settings"]
     buses, lines, m, n, c = init_network(filename_buses, filename_lines, settings=st)
     details = {}
     V, err_h, n_iter_h, J = hpf(buses, lines, coupled, st.thresh_h, st.max_iter_h, settings=st, ne_dir=ne_dir,
                                 solver=solver, verbose=verbose, details=details, extra_iters=extra_iters, check_steps=check_steps)
     # converged = the stop rule err_h <= thresh_h was met (flags bit 0) -- not "the loop ended": a NaN mismatch ends it too
-    return {"V": V, "err_h": err_h, "n_iter_h": n_iter_h, "THD": get_THD(V), "details": details,
-            "converged": bool(details["stats"]["flags"][0] & 1)}
+    out = {"V": V, "err_h": err_h, "n_iter_h": n_iter_h, "THD": get_THD(V), "details": details,
+           "converged": bool(details["stats"]["flags"][0] & 1)}
+    if line_flows:
+        out["line_flows"] = globals()["line_flows"](V, lines, buses, st)
+        out["line_summary"] = line_summary(V, lines, buses, st)
+    return out

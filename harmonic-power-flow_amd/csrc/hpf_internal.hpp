@@ -259,6 +259,21 @@ struct hpf_handle {
     uint32_t* d_dist_u = nullptr;     // [n*Hn + n] scenarios over the limit | [n][bins + 1] THD histogram
     long long* d_dist_cnt = nullptr;  // [3] added, skipped, deferred
     double* d_dist_limit = nullptr;   // [Hn]
+    // branch table (hpf_branch.hpp; built by the first call that needs it, absent otherwise): branch e = stored pair (i, j), i < j, numbered in
+    // CSR order of its upper-triangle entry
+    bool br_built = false;
+    int nb = 0;
+    std::vector<int> br_from, br_to, br_ypos;   // [nb] host copies (hpf_get_branches); ypos = position of (i, j) in col
+    int *d_br_from = nullptr, *d_br_to = nullptr;
+    hpf::cplx* d_br_y = nullptr;      // [nb][Hn] series admittances y = -Y, branch-major
+    double* d_br_part = nullptr;      // [S_max][tiles][Hn] per-tile sums of loss[q][e] (k_branch_flows -> k_branch_loss_h)
+    // branch statistics accumulator (hpf_branch_stats_*; allocated while open only)
+    bool bstat_open = false;
+    double* d_bs_f = nullptr;         // [9][nb] irms max | sum | sumsq, loss the same three, harmonic loss the same three
+    int* d_bs_arg = nullptr;          // [3][nb] scenario id of the three maxima (-1: nothing added)
+    uint32_t* d_bs_over = nullptr;    // [nb] scenarios with irms above the rating
+    long long* d_bs_cnt = nullptr;    // [3] added, skipped, deferred
+    double* d_bs_rating = nullptr;    // [nb]
     int keep_prev = 0;
     bool prev_valid = false;          // d_Vmp / d_Vap belong to the last hpf_solve (set_state / set_loads invalidate them)
     double* d_hist = nullptr;         // [S][hist_cap]

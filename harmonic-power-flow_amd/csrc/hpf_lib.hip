@@ -20,6 +20,7 @@
 
 #include <rocsolver/rocsolver.h>
 
+#include "hpf_branch.hpp"
 #include "hpf_distortion.hpp"
 #include "hpf_internal.hpp"
 
@@ -877,6 +878,132 @@ __global__ void k_distortion_add(int n, int Hn, int L, const int* __restrict__ s
     acc_u[t] = over;
 }
 
+// U alone from (Vm, Va): hpf_branch_flows evaluates at the handle's current state, and hpf_set_state uploads Vm / Va only (E is left as the
+// last solver kernel wrote it -- fund_pf and the harmonic NR normalise it differently)
+__global__ void k_branch_refresh_u(int count, const double* __restrict__ Vm, const double* __restrict__ Va, cplx* __restrict__ U) {
+    const int k = blockIdx.x * TPB + threadIdx.x;
+    if (k >= count) return;
+    const size_t o = (size_t)blockIdx.y * count + k;
+    cplx u, e;
+    polar<false>(Vm[o], Va[o], u, e);
+    U[o] = u;
+}
+
+// Branch flows of every scenario of the batch (hpf_branch.hpp).  Workgroup (tile, scenario): BRANCH_TILE consecutive branches.  Lanes run over q
+// within a branch (item t = e_local * Hn + q), so the runs U[i][0..Hn), U[j][0..Hn) and yb[e][0..Hn) are read as whole lines; I, |I|^2 and the
+// loss go to LDS; then ONE lane per branch forms the ascending-q sums, one lane per q the tile's share of loss_h (ascending e), and I leaves
+// transposed through LDS in the ABI's stacked order [Hn][nb] (e fastest: runs of BRANCH_TILE x 16 bytes).  Any output pointer may be NULL.
+__global__ void k_branch_flows(int nb, int Hn, int n, int tiles, const int* __restrict__ from, const int* __restrict__ to,
+                               const cplx* __restrict__ yb, const cplx* __restrict__ U, cplx* __restrict__ I, double* __restrict__ irms,
+                               double* __restrict__ thd_i, double* __restrict__ loss, double* __restrict__ loss_harm, double* __restrict__ part) {
+    extern __shared__ __align__(16) unsigned char br_lds[];
+    cplx* sI = reinterpret_cast<cplx*>(br_lds);
+    double* si2 = reinterpret_cast<double*>(sI + (size_t)BRANCH_TILE * Hn);
+    double* sl = si2 + (size_t)BRANCH_TILE * Hn;
+    const int tile = blockIdx.x, s = blockIdx.y, e0 = tile * BRANCH_TILE;
+    const int ne = nb - e0 < BRANCH_TILE ? nb - e0 : BRANCH_TILE;
+    const cplx* Us = U + (size_t)s * n * Hn;
+    for (int t = threadIdx.x; t < ne * Hn; t += TPB) {
+        const int el = t / Hn, q = t - el * Hn, e = e0 + el;
+        const cplx y = yb[(size_t)e * Hn + q], ui = Us[(size_t)from[e] * Hn + q], uj = Us[(size_t)to[e] * Hn + q];
+        const cplx c = branch_current(y, ui, uj);
+        sI[t] = c;
+        si2[t] = branch_abs2(c);
+        sl[t] = branch_loss(y, ui, uj);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < ne) {
+        const int el = threadIdx.x;
+        BranchSums a;
+        branch_sums_start(a);
+        for (int q = 0; q < Hn; ++q) branch_sums_step(a, q, si2[el * Hn + q], sl[el * Hn + q]);
+        const size_t o = (size_t)s * nb + e0 + el;
+        if (irms) irms[o] = branch_irms(a);
+        if (thd_i) thd_i[o] = branch_thd_i(a);
+        if (loss) loss[o] = a.loss_all;
+        if (loss_harm) loss_harm[o] = a.loss_harm;
+    }
+    if (part)
+        for (int q = threadIdx.x; q < Hn; q += TPB) {
+            double a = 0.0;
+            for (int el = 0; el < ne; ++el) a = a + sl[el * Hn + q];
+            part[((size_t)s * tiles + tile) * Hn + q] = a;
+        }
+    if (I)
+        for (int t = threadIdx.x; t < ne * Hn; t += TPB) {
+            const int q = t / ne, el = t - q * ne;
+            I[((size_t)s * Hn + q) * nb + e0 + el] = sI[el * Hn + q];
+        }
+}
+
+// loss_h[s][q] = the tile sums of k_branch_flows in ascending tile order (one thread per (scenario, q): the fixed order of hpf_branch.hpp)
+__global__ void k_branch_loss_h(int Hn, int tiles, const double* __restrict__ part, double* __restrict__ loss_h) {
+    const int s = blockIdx.y, q = blockIdx.x * TPB + threadIdx.x;
+    if (q >= Hn) return;
+    double a = 0.0;
+    for (int t = 0; t < tiles; ++t) a = a + part[((size_t)s * tiles + t) * Hn + q];
+    loss_h[(size_t)s * Hn + q] = a;
+}
+
+// Branch statistics accumulator: the finished scenarios of a list (the list, id and classification rules of k_distortion_add) are folded into the
+// per-branch statistics of irms, loss and harmonic loss.  One thread owns branch t (t = nb: the three scenario counters), walks the list in order
+// and forms each scenario's ascending-q sums itself (branch_fold): plain loads and stores, no atomics, so max / arg / over / counters do not
+// depend on the order in which scenarios arrive.  Workgroups of 64: the nb owners spread over nb / 64 compute units.
+constexpr int BR_TPB = 64;
+__global__ __launch_bounds__(BR_TPB) void k_branch_add(int nb, int Hn, int n, int L, const int* __restrict__ slots, const int* __restrict__ gids,
+                                                       int id_base, int queue, const hpf_stat* __restrict__ stats, const cplx* __restrict__ U,
+                                                       const int* __restrict__ from, const int* __restrict__ to, const cplx* __restrict__ yb,
+                                                       const double* __restrict__ rating, double* __restrict__ acc_f, int* __restrict__ acc_arg,
+                                                       uint32_t* __restrict__ acc_over, long long* __restrict__ cnt) {
+    const int t = blockIdx.x * BR_TPB + threadIdx.x;
+    if (t > nb) return;
+    if (t == nb) {
+        long long c[3] = {0, 0, 0};
+        for (int l = 0; l < L; ++l) {
+            if (slots && slots[l] < 0) break;
+            const hpf_stat st = stats[gids ? gids[l] : l];
+            c[dist_classify(st.flags, st.thd_max, queue != 0)] += 1;
+        }
+        for (int k = 0; k < 3; ++k) cnt[k] = cnt[k] + c[k];
+        return;
+    }
+    double mx[3], sum[3], sumsq[3];
+    int arg[3];
+    for (int k = 0; k < 3; ++k) {
+        mx[k] = acc_f[(size_t)(3 * k) * nb + t];
+        sum[k] = acc_f[(size_t)(3 * k + 1) * nb + t];
+        sumsq[k] = acc_f[(size_t)(3 * k + 2) * nb + t];
+        arg[k] = acc_arg[(size_t)k * nb + t];
+    }
+    uint32_t over = acc_over[t];
+    const double lim = rating[t];
+    const cplx* y = yb + (size_t)t * Hn;
+    const size_t oi = (size_t)from[t] * Hn, oj = (size_t)to[t] * Hn;
+    bool any = false;
+    for (int l = 0; l < L; ++l) {
+        const int s = slots ? slots[l] : l;
+        if (s < 0) break;
+        const int g = gids ? gids[l] : l;
+        const hpf_stat st = stats[g];
+        if (dist_classify(st.flags, st.thd_max, queue != 0) != DIST_ADD) continue;
+        const cplx* Us = U + (size_t)s * n * Hn;
+        double irms, thd_i, loss_e, loss_harm;
+        branch_fold(y, Us + oi, Us + oj, Hn, irms, thd_i, loss_e, loss_harm);
+        dist_fold(irms, id_base + g, lim, mx[0], arg[0], sum[0], sumsq[0], over);
+        branch_stat_fold(loss_e, id_base + g, mx[1], arg[1], sum[1], sumsq[1]);
+        branch_stat_fold(loss_harm, id_base + g, mx[2], arg[2], sum[2], sumsq[2]);
+        any = true;
+    }
+    if (!any) return;
+    for (int k = 0; k < 3; ++k) {
+        acc_f[(size_t)(3 * k) * nb + t] = mx[k];
+        acc_f[(size_t)(3 * k + 1) * nb + t] = sum[k];
+        acc_f[(size_t)(3 * k + 2) * nb + t] = sumsq[k];
+        acc_arg[(size_t)k * nb + t] = arg[k];
+    }
+    acc_over[t] = over;
+}
+
 // a new scenario moves into every storage of the new list: loads, the reference's start (HG:174-184) with the fundamental entries from
 // its power-flow seed, U / E, counters
 __global__ void k_queue_init(int n, int Hn, const int* __restrict__ newlist, const int* __restrict__ slot_scen, const double* __restrict__ qP,
@@ -1399,6 +1526,65 @@ void distortion_free(hpf_handle* h) {
     h->dist_open = false;
 }
 
+void branch_stats_free(hpf_handle* h) {
+    void* ptrs[] = {h->d_bs_f, h->d_bs_arg, h->d_bs_over, h->d_bs_cnt, h->d_bs_rating};
+    for (void* p : ptrs)
+        if (p) hipFree(p);
+    h->d_bs_f = h->d_bs_rating = nullptr;
+    h->d_bs_arg = nullptr;
+    h->d_bs_over = nullptr;
+    h->d_bs_cnt = nullptr;
+    h->bstat_open = false;
+}
+
+void branch_free(hpf_handle* h) {
+    branch_stats_free(h);
+    void* ptrs[] = {h->d_br_from, h->d_br_to, h->d_br_y, h->d_br_part};
+    for (void* p : ptrs)
+        if (p) hipFree(p);
+    h->d_br_from = h->d_br_to = nullptr;
+    h->d_br_y = nullptr;
+    h->d_br_part = nullptr;
+    h->br_built = false;
+}
+
+// ---- branch table, branch flows, branch statistics (hpf_branch.hpp) ----------------------------------------------------------------------
+// the table of a handle, built once by the first call that needs it: from / to / position in col of every stored pair (i, j), i < j, in CSR order
+// (row-major, columns ascending), and the branch-major copy of the series admittances y = -Y
+int branch_build(hpf_handle* h) {
+    if (h->br_built) return HPF_OK;
+    const int n = h->n, Hn = h->Hn, nnz = h->nnz;
+    std::vector<int> rowptr((size_t)n + 1), col((size_t)nnz);
+    std::vector<cplx> Y((size_t)nnz * Hn);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(rowptr.data(), h->d_rowptr, sizeof(int) * rowptr.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(col.data(), h->d_col, sizeof(int) * col.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(Y.data(), h->d_Y, sizeof(cplx) * Y.size(), hipMemcpyDeviceToHost));     // entry-major [nnz][Hn]
+    branch_table(n, rowptr.data(), col.data(), h->br_from, h->br_to, h->br_ypos);
+    const int nb = (int)h->br_from.size();
+    if (nb != h->nb) return HPF_E_STATE;                 // (hpf_create counted the same pattern)
+    std::vector<cplx> yb((size_t)nb * Hn);
+    for (int e = 0; e < nb; ++e)
+        for (int q = 0; q < Hn; ++q) yb[(size_t)e * Hn + q] = cneg(Y[(size_t)h->br_ypos[e] * Hn + q]);
+    const int tiles = (nb + BRANCH_TILE - 1) / BRANCH_TILE;
+    int r;
+    if ((r = dev_upload(h, &h->d_br_from, h->br_from.data(), (size_t)nb)) || (r = dev_upload(h, &h->d_br_to, h->br_to.data(), (size_t)nb)) ||
+        (r = dev_upload(h, &h->d_br_y, yb.data(), yb.size())) || (r = dev_alloc(h, &h->d_br_part, (size_t)h->S_max * tiles * Hn))) {
+        branch_free(h);
+        return r;
+    }
+    h->br_built = true;
+    return HPF_OK;
+}
+
+// one k_branch_add launch on the handle's stream (the open accumulator of h): list, records and id rule as k_distortion_add
+int branch_add_launch(hpf_handle* h, int L, const int* slots, const int* gids, int id_base, bool queue, const hpf_stat* stats) {
+    hipLaunchKernelGGL(k_branch_add, dim3((unsigned)((h->nb + 1 + BR_TPB - 1) / BR_TPB)), dim3(BR_TPB), 0, h->stream, h->nb, h->Hn, h->n, L, slots,
+                       gids, id_base, queue ? 1 : 0, stats, h->d_U, h->d_br_from, h->d_br_to, h->d_br_y, h->d_bs_rating, h->d_bs_f, h->d_bs_arg,
+                       h->d_bs_over, h->d_bs_cnt);
+    return launch_status(h);
+}
+
 template <bool FUND>
 int nr_loop(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* err, double* err_hist) {
     if (!h->loads_set || !h->state_set || h->S < 1) return HPF_E_STATE;
@@ -1551,6 +1737,7 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
         hipLaunchKernelGGL(k_queue_harvest, dim3((unsigned)S_max), dim3(TPB), 0, h->stream, n, Hn, thresh, max_iter, hlist, hg, h->d_Vm,
                            h->d_Va, h->d_err, h->d_niter, h->d_pivflag, qst, qVm, qVa);
         if (h->dist_open && distortion_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;   // (before the storages are refilled)
+        if (h->bstat_open && branch_add_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;
         hipLaunchKernelGGL(k_queue_init, grid2((int)count, S_max), dim3(TPB), 0, h->stream, n, Hn, newlist, slot_scen, qP, qQ, sVm, sVa,
                            h->d_P, h->d_Q, h->d_Vm, h->d_Va, h->d_U, h->d_E, h->d_niter, h->d_pivflag);
         set_ctx(h, h->stream, 0, S_max);
@@ -1614,6 +1801,7 @@ void free_all(hpf_handle* h) {
     for (void* p : ptrs)
         if (p) hipFree(p);
     distortion_free(h);
+    branch_free(h);
     tree_free(h);
     for (auto& sp : h->spans) {
         hipEventDestroy(sp.e0);
@@ -1672,6 +1860,7 @@ int hpf_create_opts(hpf_handle** out, const hpf_desc* d, const char* options) {
     if (((long long)d->n * d->Hn + 256) * d->Hn >= (1ll << 32) || (long long)d->n * d->Hn >= (1ll << 29)) return HPF_E_ARG;
     // host-side validation of the pattern: sorted columns, diagonal present, indices in range
     std::vector<int> diag(d->n, -1), erow(d->nnz);
+    int n_upper = 0;                                     // stored pairs (i, j), i < j: the branches (hpf_num_branches)
     if (d->rowptr[0] != 0 || d->rowptr[d->n] != d->nnz) return HPF_E_ARG;
     for (int i = 0; i < d->n; ++i) {
         if (d->rowptr[i + 1] < d->rowptr[i]) return HPF_E_ARG;
@@ -1680,6 +1869,7 @@ int hpf_create_opts(hpf_handle** out, const hpf_desc* d, const char* options) {
             if (j < 0 || j >= d->n) return HPF_E_ARG;
             if (e > d->rowptr[i] && d->col[e - 1] >= j) return HPF_E_ARG;
             if (j == i) diag[i] = e;
+            if (j > i) ++n_upper;
             erow[e] = i;
         }
         if (diag[i] < 0) return HPF_E_ARG;
@@ -1697,6 +1887,7 @@ int hpf_create_opts(hpf_handle** out, const hpf_desc* d, const char* options) {
     };
     h->n = d->n; h->m = d->m; h->c = d->c; h->Hn = d->Hn; h->nnz = d->nnz; h->n_dev = d->n_dev;
     h->coupled = d->coupled ? 1 : 0; h->solver = d->solver; h->device = d->device; h->S_max = d->max_scenarios;
+    h->nb = n_upper;
     h->Nc = d->n * d->Hn - 1;
     h->N = 2 * h->Nc - (d->c - 1);
     h->Nf = 2 * d->n - 1 - d->c;
@@ -2036,6 +2227,7 @@ int hpf_solve_queue(hpf_handle* h, int n_total, const double* P, const double* Q
         if ((r = hpf_fund_pf(h, thresh_f, max_iter_f, nullptr, nullptr, nullptr))) return r;
         if ((r = hpf_solve(h, thresh, max_iter, nullptr, nullptr, nullptr))) return r;
         if (h->dist_open && (r = distortion_launch(h, S, nullptr, nullptr, h->dist_id_base + g0, true, h->d_stats))) return r;
+        if (h->bstat_open && (r = branch_add_launch(h, S, nullptr, nullptr, h->dist_id_base + g0, true, h->d_stats))) return r;
         if (stats && (r = hpf_get_stats(h, stats + g0))) return r;
         if (Vm && (r = hpf_get_state(h, Vm + (size_t)g0 * cnt, Va + (size_t)g0 * cnt))) return r;
     }
@@ -2195,6 +2387,122 @@ int hpf_distortion_end(hpf_handle* h) {
     return HPF_OK;
 }
 
+int hpf_num_branches(const hpf_handle* h) { return h ? h->nb : HPF_E_ARG; }
+
+int hpf_get_branches(hpf_handle* h, int32_t* from, int32_t* to, int32_t* ypos) {
+    if (!h) return HPF_E_ARG;
+    int r;
+    if ((r = branch_build(h))) return r;
+    if (from) memcpy(from, h->br_from.data(), sizeof(int32_t) * (size_t)h->nb);
+    if (to) memcpy(to, h->br_to.data(), sizeof(int32_t) * (size_t)h->nb);
+    if (ypos) memcpy(ypos, h->br_ypos.data(), sizeof(int32_t) * (size_t)h->nb);
+    return HPF_OK;
+}
+
+int hpf_branch_flows(hpf_handle* h, double* I, double* irms, double* thd_i, double* loss, double* loss_harm, double* loss_h) {
+    if (!h) return HPF_E_ARG;
+    if (!h->state_set || h->S < 1) return HPF_E_STATE;
+    const size_t lds = (size_t)BRANCH_TILE * h->Hn * (sizeof(cplx) + 2 * sizeof(double));
+    if (lds > 160 * 1024) return HPF_E_ARG;              // (Hn > 160)
+    int r;
+    if ((r = branch_build(h))) return r;
+    const int S = h->S, nb = h->nb, Hn = h->Hn, tiles = (nb + BRANCH_TILE - 1) / BRANCH_TILE;
+    const size_t count = (size_t)h->n * Hn;
+    cplx* dI = nullptr;
+    double* dv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // irms, thd_i, loss, loss_harm, loss_h
+    double* host[5] = {irms, thd_i, loss, loss_harm, loss_h};
+    auto cleanup = [&](int code) {
+        hipStreamSynchronize(h->stream);
+        if (dI) hipFree(dI);
+        for (double* p : dv)
+            if (p) hipFree(p);
+        return code;
+    };
+    if (I && (r = dev_alloc(h, &dI, (size_t)S * Hn * nb))) return cleanup(r);
+    for (int k = 0; k < 5; ++k)
+        if (host[k] && (r = dev_alloc(h, &dv[k], (size_t)S * (k == 4 ? Hn : nb)))) return cleanup(r);
+    hipLaunchKernelGGL(k_branch_refresh_u, grid2((int)count, S), dim3(TPB), 0, h->stream, (int)count, h->d_Vm, h->d_Va, h->d_U);
+    if (nb > 0) {
+        if (lds > 64 * 1024 &&
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_branch_flows), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
+            return cleanup(HPF_E_HIP);
+        hipLaunchKernelGGL(k_branch_flows, dim3((unsigned)tiles, (unsigned)S), dim3(TPB), lds, h->stream, nb, Hn, h->n, tiles, h->d_br_from,
+                           h->d_br_to, h->d_br_y, h->d_U, dI, dv[0], dv[1], dv[2], dv[3], loss_h ? h->d_br_part : (double*)nullptr);
+    }
+    if (loss_h)
+        hipLaunchKernelGGL(k_branch_loss_h, grid2(Hn, S), dim3(TPB), 0, h->stream, Hn, nb > 0 ? tiles : 0, h->d_br_part, dv[4]);
+    if (launch_status(h)) return cleanup(HPF_E_HIP);
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return cleanup(HPF_E_HIP);
+    if (I && hipMemcpy(I, dI, sizeof(cplx) * (size_t)S * Hn * nb, hipMemcpyDeviceToHost) != hipSuccess) return cleanup(HPF_E_HIP);
+    for (int k = 0; k < 5; ++k)
+        if (host[k] && hipMemcpy(host[k], dv[k], sizeof(double) * (size_t)S * (k == 4 ? Hn : nb), hipMemcpyDeviceToHost) != hipSuccess)
+            return cleanup(HPF_E_HIP);
+    return cleanup(HPF_OK);
+}
+
+int hpf_branch_stats_begin(hpf_handle* h, const double* rating) {
+    if (!h) return HPF_E_ARG;
+    std::vector<double> lim((size_t)h->nb, (double)INFINITY);
+    for (int e = 0; rating && e < h->nb; ++e) {
+        if (rating[e] != rating[e]) return HPF_E_ARG;
+        lim[e] = rating[e];
+    }
+    int r;
+    if ((r = branch_build(h))) return r;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    branch_stats_free(h);                                // (an open accumulator is reset)
+    const size_t nb = (size_t)h->nb;
+    if ((r = dev_alloc(h, &h->d_bs_f, 9 * nb)) || (r = dev_alloc(h, &h->d_bs_arg, 3 * nb)) || (r = dev_alloc(h, &h->d_bs_over, nb)) ||
+        (r = dev_alloc(h, &h->d_bs_cnt, (size_t)3)) || (r = dev_upload(h, &h->d_bs_rating, lim.data(), lim.size()))) {
+        branch_stats_free(h);
+        return r;
+    }
+    HIPCHK(hipMemsetAsync(h->d_bs_f, 0, sizeof(double) * (9 * nb ? 9 * nb : 1), h->stream));
+    HIPCHK(hipMemsetAsync(h->d_bs_arg, 0xff, sizeof(int) * (3 * nb ? 3 * nb : 1), h->stream));
+    HIPCHK(hipMemsetAsync(h->d_bs_over, 0, sizeof(uint32_t) * (nb ? nb : 1), h->stream));
+    HIPCHK(hipMemsetAsync(h->d_bs_cnt, 0, sizeof(long long) * 3, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->bstat_open = true;
+    return HPF_OK;
+}
+
+int hpf_branch_stats_add(hpf_handle* h, int first_id) {
+    if (!h || first_id < 0) return HPF_E_ARG;
+    if (!h->bstat_open || !h->loads_set || !h->state_set || h->S < 1 || !h->solve_done) return HPF_E_STATE;
+    int r;
+    if ((r = branch_add_launch(h, h->S, nullptr, nullptr, first_id, false, h->d_stats))) return r;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return HPF_OK;
+}
+
+int hpf_branch_stats_get(hpf_handle* h, int64_t* counts, double* irms_max, int32_t* irms_arg, double* irms_sum, double* irms_sumsq,
+                         uint32_t* irms_over, double* loss_max, int32_t* loss_arg, double* loss_sum, double* loss_sumsq, double* lossh_max,
+                         int32_t* lossh_arg, double* lossh_sum, double* lossh_sumsq) {
+    if (!h) return HPF_E_ARG;
+    if (!h->bstat_open) return HPF_E_STATE;
+    const size_t nb = (size_t)h->nb;
+    long long cnt[3];
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(cnt, h->d_bs_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
+    for (int k = 0; counts && k < 3; ++k) counts[k] = cnt[k];
+    double* f[9] = {irms_max, irms_sum, irms_sumsq, loss_max, loss_sum, loss_sumsq, lossh_max, lossh_sum, lossh_sumsq};
+    int32_t* a[3] = {irms_arg, loss_arg, lossh_arg};
+    for (int k = 0; k < 9; ++k)
+        if (f[k] && nb) HIPCHK(hipMemcpy(f[k], h->d_bs_f + k * nb, sizeof(double) * nb, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; ++k)
+        if (a[k] && nb) HIPCHK(hipMemcpy(a[k], h->d_bs_arg + k * nb, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
+    if (irms_over && nb) HIPCHK(hipMemcpy(irms_over, h->d_bs_over, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));
+    return HPF_OK;
+}
+
+int hpf_branch_stats_end(hpf_handle* h) {
+    if (!h) return HPF_E_ARG;
+    if (!h->bstat_open) return HPF_OK;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    branch_stats_free(h);
+    return HPF_OK;
+}
+
 int hpf_debug_stamps(hpf_handle* h, long long* out, int count) {
     if (!h || !out || !h->d_dbg || count > h->S_max * h->n * 8) return HPF_E_ARG;
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -2257,7 +2565,7 @@ int hpf_set_option(hpf_handle* h, const char* name, int value) {
         h->resid_limit = pow(10.0, (double)value);
         return HPF_OK;
     }
-    if (!strcmp(name, "distortion_id_base")) {      // hpf_solve_queue with the distortion accumulator open: scenario g of a call gets id value + g
+    if (!strcmp(name, "distortion_id_base")) {      // hpf_solve_queue with the distortion or the branch accumulator open: scenario g of a call gets id value + g
         if (value < 0) return HPF_E_ARG;
         h->dist_id_base = value;
         return HPF_OK;

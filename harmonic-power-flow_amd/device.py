@@ -301,6 +301,57 @@ class DeviceModel:
         self._chk(self.lib.hpf_distortion_end(self._h), "hpf_distortion_end")
         self._dist = None
 
+    # -- branch flows and branch statistics (hpf_branch_*) ---------------------------------------------------
+    @property
+    def nb(self):
+        """Branches of the handle: stored pairs (i, j), i < j, of the admittance pattern (hpf_num_branches)."""
+        return int(self.lib.hpf_num_branches(self._h))
+
+    def branches(self):
+        """-> (from [nb], to [nb], ypos [nb]) int32: the two buses of every branch (from < to) and the position of (from, to) in `col`."""
+        out = [np.empty(self.nb, dtype=np.int32) for _ in range(3)]
+        self._chk(self.lib.hpf_get_branches(self._h, *[_ip(a) for a in out]), "hpf_get_branches")
+        return tuple(out)
+
+    def branch_flows(self, want_I=True):
+        """Series currents and losses of every branch at the handle's current state (after solve(), or after set_state() alone) -> dict:
+        I [S][Hn][nb] complex (p.u., positive from the lower-numbered bus to the higher; None with want_I=False), irms, thd_i, loss, loss_harm
+        [S][nb], loss_h [S][Hn] (include/hpf.h, hpf_branch_flows)."""
+        S, nb = self._batch("hpf_branch_flows"), self.nb
+        out = {"I": np.empty((S, self.Hn, nb), dtype=np.complex128) if want_I else None}
+        for k in ("irms", "thd_i", "loss", "loss_harm"):
+            out[k] = np.empty((S, nb))
+        out["loss_h"] = np.empty((S, self.Hn))
+        self._chk(self.lib.hpf_branch_flows(self._h, out["I"].view(np.float64).ctypes.data_as(_lib.c_dbl_p) if want_I else None,
+                                            *[_dp(out[k]) for k in ("irms", "thd_i", "loss", "loss_harm", "loss_h")]), "hpf_branch_flows")
+        return out
+
+    def branch_stats_begin(self, rating=None):
+        """Open (or reset) the handle's branch statistics: from now on every converged scenario hpf_solve_queue harvests, and every batch handed to
+        branch_stats_add, is folded into per-branch statistics of irms, loss and harmonic loss on the device.  rating [nb] in p.u. (None: no
+        ratings): irms_over counts the scenarios with irms[e] > rating[e]."""
+        r = None if rating is None else np.ascontiguousarray(rating, dtype=np.float64)
+        assert r is None or r.shape == (self.nb,)
+        self._chk(self.lib.hpf_branch_stats_begin(self._h, _dp(r) if r is not None else None), "hpf_branch_stats_begin")
+        self._brating = r
+
+    def branch_stats_add(self, first_id=0):
+        """Fold the current batch (after solve()) into the branch statistics, scenario s under id first_id + s."""
+        self._chk(self.lib.hpf_branch_stats_add(self._h, int(first_id)), "hpf_branch_stats_add")
+
+    def branch_stats_get(self):
+        """-> sweep.BranchStats of everything added since branch_stats_begin; the accumulator stays open."""
+        from .sweep import BranchStats
+        nb = self.nb
+        a = {name: np.zeros((3,) if name == "counts" else (nb,), dtype=dt) for name, dt in zip(BranchStats.ARRAYS, BranchStats.DTYPES)}
+        self._chk(self.lib.hpf_branch_stats_get(self._h, *[a[name].ctypes.data_as(C.c_void_p) for name in BranchStats.ARRAYS]),
+                  "hpf_branch_stats_get")
+        return BranchStats(getattr(self, "_brating", None), **a)
+
+    def branch_stats_end(self):
+        self._chk(self.lib.hpf_branch_stats_end(self._h), "hpf_branch_stats_end")
+        self._brating = None
+
     def set_option(self, name, value):
         self._chk(self.lib.hpf_set_option(self._h, name.encode(), int(value)), "hpf_set_option")
 

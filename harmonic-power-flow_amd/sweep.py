@@ -128,6 +128,11 @@ def gather_distortion(stats, world, ids=None):
     first, then ONE all_gather of the packed arrays (a few hundred KB per rank) and a merge in rank order -- every rank returns the same
     statistics, bit for bit.  world == 1 returns its argument (ids applied), like gather_stats.  Every rank must have opened its accumulator
     with the same settings."""
+    return _gather_merge(stats, world, ids)
+
+
+def _gather_merge(stats, world, ids):
+    """ids applied on the host, one all_gather of stats.pack(), unpack + merge in rank order (DistortionStats and BranchStats alike)."""
     if ids is not None:
         stats = stats.with_ids(ids)
     if world == 1:
@@ -147,7 +152,99 @@ def gather_distortion(stats, world, ids=None):
     return out
 
 
-def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_iter_h=50, want_voltages=False, refill=True, distortion=None):
+class BranchStats:
+    """Per-branch statistics of a sweep, as the device accumulated them (hpf_branch_stats_*, include/hpf.h) -- a plain container of NumPy arrays
+    [nb] over the branches of the handle (DeviceModel.branches()).  Three quantities per scenario and branch: irms (RMS current over all harmonics,
+    p.u.: the thermal loading), loss (series loss over all harmonics) and lossh (the harmonics' share, q >= 1).
+    counts [3] int64: scenarios added, skipped, deferred (the rules of DistortionStats); x_max / x_arg: largest value and the scenario id it came
+    from (ties: the smallest id; -1: nothing added); x_sum / x_sumsq: sums over the added scenarios; irms_over: scenarios with irms above
+    `rating[e]` (strictly)."""
+    ARRAYS = ("counts", "irms_max", "irms_arg", "irms_sum", "irms_sumsq", "irms_over", "loss_max", "loss_arg", "loss_sum", "loss_sumsq",
+              "lossh_max", "lossh_arg", "lossh_sum", "lossh_sumsq")
+    DTYPES = (np.int64, np.float64, np.int32, np.float64, np.float64, np.uint32, np.float64, np.int32, np.float64, np.float64,
+              np.float64, np.int32, np.float64, np.float64)
+    QUANTITIES = ("irms", "loss", "lossh")
+
+    def __init__(self, rating, **arrays):
+        for name, dt in zip(self.ARRAYS, self.DTYPES):
+            setattr(self, name, np.ascontiguousarray(arrays[name], dtype=dt))
+        nb = self.irms_max.shape[0]
+        self.rating = np.full(nb, np.inf) if rating is None else np.array(rating, dtype=np.float64)
+        assert self.counts.shape == (3,) and self.rating.shape == (nb,) and all(getattr(self, a).shape == (nb,) for a in self.ARRAYS[1:])
+
+    @property
+    def added(self):
+        return int(self.counts[0])
+
+    def mean(self, what="irms"):
+        """-> mean [nb] of irms / loss / lossh over the added scenarios (NaN when nothing was added)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return getattr(self, what + "_sum") / self.added
+
+    def std(self, what="irms"):
+        """-> population standard deviation [nb] from sum and sum of squares."""
+        m = self.mean(what)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.sqrt(np.maximum(getattr(self, what + "_sumsq") / self.added - m * m, 0.0))
+
+    def worst(self, k=1, what="irms", relative=False):
+        """The k branches with the largest maximum of `what` (relative=True: of irms_max / rating) -> list of (branch, scenario id, value),
+        largest first."""
+        v = getattr(self, what + "_max")
+        if relative:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                v = np.where(np.isfinite(self.rating), v / self.rating, 0.0)
+        order = np.argsort(-v, kind="stable")[:k]
+        return [(int(e), int(getattr(self, what + "_arg")[e]), float(v[e])) for e in order]
+
+    def merge(self, other):
+        """Statistics of the union of two disjoint sets of scenarios: max with the smaller-id tie rule, integer adds, float adds.  Refuses
+        different ratings / shapes."""
+        if self.irms_max.shape != other.irms_max.shape or not np.array_equal(self.rating, other.rating):
+            raise ValueError("BranchStats.merge: the two accumulators were opened with different ratings or shapes")
+        out = {"counts": self.counts + other.counts, "irms_over": self.irms_over + other.irms_over}
+        for pre in self.QUANTITIES:
+            ma, aa, mb, ab = (getattr(o, pre + f) for o in (self, other) for f in ("_max", "_arg"))
+            take = (ab >= 0) & ((aa < 0) | (mb > ma) | ((mb == ma) & (ab < aa)))
+            out[pre + "_max"], out[pre + "_arg"] = np.where(take, mb, ma), np.where(take, ab, aa)
+            for f in ("_sum", "_sumsq"):
+                out[pre + f] = getattr(self, pre + f) + getattr(other, pre + f)
+        return BranchStats(self.rating, **out)
+
+    def with_ids(self, ids):
+        """The same statistics with every scenario id k in the arg arrays replaced by ids[k] (-1 stays)."""
+        ids = np.asarray(ids)
+        out = {name: getattr(self, name) for name in self.ARRAYS}
+        for pre in self.QUANTITIES:
+            a = out[pre + "_arg"]
+            out[pre + "_arg"] = np.where(a >= 0, ids[np.maximum(a, 0)], -1)
+        return BranchStats(self.rating, **out)
+
+    def pack(self):
+        """-> one uint8 array holding every array (the payload of gather_branch_stats)."""
+        return np.concatenate([getattr(self, name).reshape(-1).view(np.uint8) for name in self.ARRAYS])
+
+    def unpack(self, raw):
+        """A BranchStats with this one's rating and shapes and the arrays of `raw` (what pack() of a peer produced)."""
+        raw = np.ascontiguousarray(raw, dtype=np.uint8)
+        out, o = {}, 0
+        for name in self.ARRAYS:
+            a = getattr(self, name)
+            out[name] = raw[o:o + a.nbytes].view(a.dtype).reshape(a.shape).copy()
+            o += a.nbytes
+        assert o == raw.size
+        return BranchStats(self.rating, **out)
+
+
+def gather_branch_stats(stats, world, ids=None):
+    """Branch statistics of a multi-GPU sweep, like gather_distortion: `ids[k]` = global id of local scenario k is applied to the arg arrays on the
+    host, then ONE all_gather of the packed arrays (108 bytes per branch and rank) and a merge in rank order -- every rank returns the same
+    statistics, bit for bit.  world == 1 returns its argument (ids applied).  Every rank must have opened its accumulator with the same ratings."""
+    return _gather_merge(stats, world, ids)
+
+
+def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_iter_h=50, want_voltages=False, refill=True, distortion=None,
+                    branches=None):
     """Monte-Carlo / what-if sweep on ONE GPU: every row of P, Q [n_scen][n] (p.u. loads, HG:197,372) is one scenario of the
     network `dm` (a DeviceModel) holds -- the reference's counterpart is one hpf() call per load case (HG:511).  Per scenario:
     reference start (HG:174-184), fundamental pf (HG:244), harmonic NR with the reference's stop rule (HG:536).
@@ -163,21 +260,31 @@ def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_i
     distortion: None (default), or a dict {"limit": [Hn] or None, "thd_limit": x, "hist_max": x, "bins": 1..256} (missing keys: no limits,
     hist_max 1.0, 64 bins): the handle's distortion accumulator is opened for the sweep, every converged scenario is folded in on the device
     under its row number in P (queue pieces through "distortion_id_base", re-solved flagged scenarios and the waves of refill=False through
-    distortion_add), and the DistortionStats are returned as an additional last element; records and voltages are unchanged."""
+    distortion_add), and the DistortionStats are returned as an additional last element; records and voltages are unchanged.
+    branches: None (default), or a dict {"rating": [nb] or None}: likewise for the handle's branch statistics (hpf_branch_stats_*: per line
+    the RMS current over all harmonics against its rating, series loss, harmonic loss); the BranchStats are returned as a further last element,
+    after the DistortionStats when both are asked for."""
+    if distortion is None and branches is None:
+        return _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, False, False)
     if distortion is not None:
         dm.distortion_begin(distortion.get("limit"), distortion.get("thd_limit", np.inf), distortion.get("hist_max", 1.0),
                             distortion.get("bins", 64))
-        try:
-            res = _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, True)
-            stats = dm.distortion_get()
-        finally:
-            dm.set_option("distortion_id_base", 0)
+    try:
+        if branches is not None:
+            dm.branch_stats_begin(branches.get("rating"))
+        res = _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion is not None,
+                               branches is not None)
+        extra = (() if distortion is None else (dm.distortion_get(),)) + (() if branches is None else (dm.branch_stats_get(),))
+    finally:
+        dm.set_option("distortion_id_base", 0)
+        if distortion is not None:
             dm.distortion_end()
-        return (res + (stats,)) if want_voltages else (res, stats)
-    return _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, False)
+        if branches is not None:
+            dm.branch_stats_end()
+    return (res if want_voltages else (res,)) + extra
 
 
-def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion):
+def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion, branches):
     P = np.ascontiguousarray(np.atleast_2d(P), dtype=np.float64)
     Q = np.ascontiguousarray(np.atleast_2d(Q), dtype=np.float64)
     n_scen = P.shape[0]
@@ -194,6 +301,8 @@ def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_
         dm.solve(thresh_h, max_iter_h)
         if distortion:
             dm.distortion_add(a)
+        if branches:
+            dm.branch_stats_add(a)
         st = dm.stats()
         for k in STAT_DTYPE.names:
             out[k][a:b] = st[k]
@@ -208,7 +317,7 @@ def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_
     per_call = n_scen if not want_voltages else max(dm.S_max, int(8e9 // (16 * dm.n * dm.Hn)))
     for a in range(0, n_scen, per_call):
         b = min(a + per_call, n_scen)
-        if distortion:
+        if distortion or branches:
             dm.set_option("distortion_id_base", a)
         res = dm.solve_queue(P[a:b], Q[a:b], thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages=want_voltages)
         if want_voltages:

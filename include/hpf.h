@@ -249,6 +249,53 @@ int  hpf_distortion_get(hpf_handle* h, int64_t* counts, double* x_max, int32_t* 
                         double* thd_max, int32_t* thd_arg, double* thd_sum, double* thd_sumsq, uint32_t* thd_over, uint32_t* thd_hist);
 int  hpf_distortion_end(hpf_handle* h);
 
+/* Branch flows: harmonic currents, RMS loading and series losses of the lines, on the device.  The reference has no counterpart (its
+ * current_balance, HG:326-357, forms bus injections only).
+ * A BRANCH is one stored off-diagonal pair (i, j), i < j, of the shared admittance pattern.  Branches are numbered in CSR order of their
+ * upper-triangle entry (row-major, columns ascending): a function of the pattern alone, radial lines and loop-closing lines alike.  The reference
+ * writes Y[from,to] = -1/(R + j h X) and lets a later parallel line overwrite an earlier one (HG:150-155), so a branch is the line the matrix actually
+ * contains; its series admittance at harmonic position q is y[q][e] = -Y[q][pos(i,j)].  Shunt parts (HG:157-168) stay out: only the series element
+ * carries the conductor current.  Per scenario, with U the rectangular voltages (p.u.):
+ *   I[q][e]    = y[q][e] (U[i][q] - U[j][q])          complex, p.u., positive from the lower-numbered bus to the higher
+ *   loss[q][e] = Re(y[q][e]) |U[i][q] - U[j][q]|^2    (= R |I|^2, never negative)
+ *   irms[e] = sqrt(sum_q |I[q][e]|^2),  thd_i[e] = sqrt(sum_{q>=1} |I[q][e]|^2) / |I[0][e]|  (inf / NaN where the fundamental current is zero),
+ *   loss_e[e] = sum_q loss[q][e],  loss_harm[e] = sum_{q>=1} loss[q][e],  loss_h[q] = sum_e loss[q][e].
+ * Every product and sum is rounded on its own; every sum over q runs sequentially over ascending q in one thread (|I[0]| = sqrt(|I[0]|^2)); the sum
+ * over e of loss_h runs in tiles of 32 consecutive branches -- ascending e inside a tile from 0.0, then the tile sums in ascending tile order from
+ * 0.0 -- an order that depends on the number of branches alone.  No atomics.
+ * hpf_num_branches: nb (counted by hpf_create; no device call).  hpf_get_branches: from [nb], to [nb] (bus indices, from < to), ypos [nb] (position
+ *   of (from, to) in `col`); any pointer may be NULL.  The first of hpf_get_branches / hpf_branch_flows / hpf_branch_stats_begin builds the handle's
+ *   branch table (from, to, ypos and a branch-major copy [nb][Hn] of y) on the device; a handle that never calls them holds none.
+ * hpf_branch_flows: evaluates at the handle's CURRENT STATE -- after hpf_solve, or after hpf_set_state alone (the rectangular voltages are refreshed
+ *   from the state first); every solver, handles used for assembly only included.  Outputs for the hpf_num_scenarios scenarios of the batch, any
+ *   pointer may be NULL: I [S][Hn][nb] complex (interleaved re, im), irms / thd_i / loss / loss_harm [S][nb], loss_h [S][Hn].  HPF_E_STATE without a
+ *   batch (no state set, or after hpf_solve_queue); HPF_E_ARG for more than 160 harmonics.
+ * Branch statistics of a sweep (the twin of the distortion accumulator above: same state rules, same scenario lists, same rule for who is added --
+ *   converged scenarios with a finite THD; a scenario hpf_solve_queue only reports, flags bit 2 / 3 / 6, is deferred to the caller's re-solve --
+ *   same ids: hpf_solve_queue numbers scenarios through "distortion_id_base", which serves both accumulators).  One thread owns one branch and
+ *   walks the finished scenarios (k_branch_add, launched where k_distortion_add is): max, arg, over and counts do not depend on slot count, queue
+ *   chunk, scenario groups or number of GPUs; the sums do by rounding alone.  Closed (the default): nothing is allocated or launched.
+ * hpf_branch_stats_begin: allocate, zero, open (on an open one: reset).  rating [nb] in p.u. (NULL: +inf); HPF_E_ARG for a NaN rating.
+ * hpf_branch_stats_add: fold the current batch in, scenario s under id first_id + s (first_id >= 0); HPF_E_STATE unless hpf_solve was the last call
+ *   that touched the batch, or with the accumulator closed.
+ * hpf_branch_stats_get: copies out whichever arrays are non-NULL; leaves the accumulator open.  HPF_E_STATE when closed.
+ *   counts [3] int64: scenarios added, skipped, deferred
+ *   irms_max [nb] double, irms_arg [nb] int32 (ties: the smallest id; 0 / -1 before the first add), irms_sum, irms_sumsq [nb] double,
+ *   irms_over [nb] uint32: scenarios with irms[e] > rating[e] (strictly)
+ *   loss_max, loss_arg, loss_sum, loss_sumsq: the same four for loss_e;  lossh_max, lossh_arg, lossh_sum, lossh_sumsq: for loss_harm
+ *   (thd_i is not accumulated: where a branch carries no fundamental current its samples are inf, NaN or rounding noise)
+ * hpf_branch_stats_end: free (HPF_OK when already closed); hpf_destroy frees an open one and the branch table.
+ * All of them: HPF_E_ARG for a NULL handle, before any HIP call. */
+int  hpf_num_branches(const hpf_handle* h);
+int  hpf_get_branches(hpf_handle* h, int32_t* from, int32_t* to, int32_t* ypos);
+int  hpf_branch_flows(hpf_handle* h, double* I, double* irms, double* thd_i, double* loss, double* loss_harm, double* loss_h);
+int  hpf_branch_stats_begin(hpf_handle* h, const double* rating);
+int  hpf_branch_stats_add(hpf_handle* h, int first_id);
+int  hpf_branch_stats_get(hpf_handle* h, int64_t* counts, double* irms_max, int32_t* irms_arg, double* irms_sum, double* irms_sumsq,
+                          uint32_t* irms_over, double* loss_max, int32_t* loss_arg, double* loss_sum, double* loss_sumsq, double* lossh_max,
+                          int32_t* lossh_arg, double* lossh_sum, double* lossh_sumsq);
+int  hpf_branch_stats_end(hpf_handle* h);
+
 /* Diagnostics: with env HPF_DEBUG_ABLATE & 16 the BLOCK_TREE factor kernel records shader-cycle stamps per (scenario, bus):
  * out[(s*n + k)*8 + 0..5] = assembly, packed sub-phases, packed Gauss-Jordan split, MFMA Gauss-Jordan, packed wave-0 roles,
  * Schur push (tools/stamps.py decodes them; -DHPF_FACTOR_STAMPS build only); [6] dense children,
@@ -275,7 +322,8 @@ int  hpf_debug_stamps(hpf_handle* h, long long* out, int count);
  * healthy steps of every path sit below 1e-12, the evaluation's own rounding below 2e-14) or a non-finite eta sets hpf_stat.flags bit 6; hpf_solve
  * treats the scenario like one flagged by the static-pivot monitor (repeat with partial pivoting where that exists, "auto_repivot"; the check runs
  * in the repeat too and bit 7 is the verdict on the pass whose result is returned).  Off: no launch is added, results are bit-identical.
- * "distortion_id_base" (>= 0, default 0): with the distortion accumulator open, hpf_solve_queue adds scenario g of a call under id value + g.
+ * "distortion_id_base" (>= 0, default 0): with the distortion accumulator or the branch statistics open (it serves both), hpf_solve_queue adds
+ * scenario g of a call under id value + g.
  * "scenario_groups" (1..8, default 4; at least 32 running scenarios per group): independent scenario pipelines on separate HIP streams -- group 0
  * on the handle's own stream (hpf_set_stream), the others on streams of the handle.  The runtime maps streams onto FOUR hardware queues: with a fifth
  * stream busy at the same time (the application's own work during a solve) two groups share a queue and serialise (1.25 instead of 0.90 ms per

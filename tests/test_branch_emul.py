@@ -1,0 +1,294 @@
+"""Branch flows and branch statistics without a GPU: the functions of csrc/hpf_branch.hpp executed serially on the host (tests/branch_emul.py)
+against the NumPy restatement tests/branch_ref.py; the definition itself against the energy identity; the host side (sweep.BranchStats,
+sweep.gather_branch_stats, api.line_branches) and the argument checks of the entry points.
+
+On the host sqrt and / are correctly rounded on both sides and both sides round every real product and sum on its own, in the same order, so
+every array of the flows must be EQUAL; of the statistics max, arg, over and the counts must be equal, and the sums may differ by the order of
+summation only (added x 2^-52 x sum, either side)."""
+import itertools
+import os
+import socket
+
+import numpy as np
+import pandas as pd
+import pytest
+
+import branch_emul as be
+import branch_ref as ref
+
+from harmonic_power_flow_amd import api, sweep
+
+GOLDEN = ["net1_H51_c", "net2_H51_c", "net3_H51_c", "lin4_H11_c", "syn1000_H51_c"]
+
+
+def _same(a, b):
+    return np.array_equal(a, b, equal_nan=True)
+
+
+@pytest.mark.parametrize("name", GOLDEN)
+def test_emulated_flows_equal_numpy_on_the_golden_voltages(name):
+    net = be.network(name)
+    Vm, Va, ids, flags = be.scenario_set(net, 3)
+    U = ref.rect(np.vstack([net["Vm"][None], Vm]), np.vstack([net["Va"][None], Va]), net["n"], net["Hn"])
+    want = ref.flows(net["fr"], net["to"], net["y"], U)
+    got = be.flows(net["fr"], net["to"], net["y"], U)
+    for k in ("I", "irms", "thd_i", "loss", "loss_harm", "loss_h"):
+        assert _same(got[k], want[k]), k
+    assert (want["loss_q"] >= 0).all() and (want["irms"] >= 0).all() and np.isfinite(want["irms"]).all()
+    assert want["loss_h"][0, 0] > 0 and (want["loss_harm"] <= want["loss"]).all()
+    if name == "syn1000_H51_c":
+        assert len(net["fr"]) == 999 == len(net["lines"])
+        assert (np.abs(want["I"][0]) == 0).mean() > 0.3 and (want["irms"][0] == 0).sum() < 100      # no-load subtrees sit at one potential
+
+
+@pytest.mark.parametrize("name", GOLDEN)
+def test_branch_numbering_is_the_upper_triangle_in_csr_order(name):
+    net = be.network(name)
+    fr, to, ypos = be.table(net["n"], net["rowptr"], net["col"])
+    assert np.array_equal(fr, net["fr"]) and np.array_equal(to, net["to"]) and np.array_equal(ypos, net["ypos"])
+    assert (fr < to).all() and np.array_equal(net["col"][ypos], to)
+    key = fr.astype(np.int64) * net["n"] + to
+    assert (np.diff(key) > 0).all()                               # row-major, columns ascending
+    lines = net["lines"]
+    pairs = {(min(a, b) - 1, max(a, b) - 1) for a, b in zip(lines.fromID, lines.toID) if a != b}
+    assert pairs == set(zip(fr.tolist(), to.tolist()))            # the branches are the lines the matrix contains
+    e, sign = api.line_branches(lines, fr, to, net["n"])
+    assert (e >= 0).all() and np.array_equal(fr[e], np.minimum(lines.fromID, lines.toID) - 1)
+    assert np.array_equal(sign, np.where(lines.fromID < lines.toID, 1.0, -1.0))
+
+
+def test_parallel_and_reversed_lines_share_one_branch():
+    net = be.network("net2_H51_c")
+    lines = net["lines"]
+    first = lines.iloc[[0]].copy()
+    rev = lines.iloc[[1]].copy()
+    rev[["fromID", "toID"]] = rev[["toID", "fromID"]].to_numpy()
+    loop = lines.iloc[[0]].copy()
+    loop["toID"] = loop["fromID"]
+    more = pd.concat([lines, first, rev, loop], ignore_index=True)
+    e, sign = api.line_branches(more, net["fr"], net["to"], net["n"])
+    L = len(lines)
+    assert e[L] == e[0] and sign[L] == sign[0]                    # the duplicated line: the same branch, the same direction
+    assert e[L + 1] == e[1] and sign[L + 1] == -sign[1]           # the reversed one: the same branch, the other sign
+    assert e[L + 2] == -1 and np.isnan(sign[L + 2])               # a line from a bus to itself has no branch
+    # the admittance pattern of the table with the duplicate is the pattern without it: the numbering is a function of the pattern alone
+    import harmonic_power_flow_amd as hp
+    Y2 = hp.build_admittance_matrices(net["buses"], more.iloc[:L + 2], net["harmonics"])
+    f2, t2, _ = ref.branches(Y2.rowptr, Y2.col)
+    assert np.array_equal(f2, net["fr"]) and np.array_equal(t2, net["to"])
+
+
+@pytest.mark.parametrize("name", GOLDEN)
+def test_energy_identity_pins_the_definition(name):
+    """Per harmonic Re(U^H Y U) = sum_e loss[q][e] + sum_i Re(rowsum_i(Y_q)) |U_i|^2 for a symmetric Y: independent of both implementations.
+    Both sides are evaluated in float64 by NumPy, so the residual is the rounding of sums whose terms have the size M[q] = sum_ij |Y_ij| |U_i| |U_j|:
+    every term carries a few roundings of 2^-53 relative and so does every partial sum, hence |residual| <= 16 x 2^-53 x M[q] (asserted for
+    every network).  Where the network is loaded the result itself is of the terms' size, and the residual is asserted at 1e-12 of the
+    fundamental term Re(U_1^H Y_1 U_1) (headline golden: 1.6e-11 of 351 p.u.); lin4 is all but unloaded -- 2.8e-4 p.u. left of terms of 1e2 p.u.
+    after cancellation -- so only the first bound can hold there (observed 1.2e-14)."""
+    import scipy.sparse as sp
+    net = be.network(name)
+    n, Hn = net["n"], net["Hn"]
+    U = ref.rect(net["Vm"][None], net["Va"][None], n, Hn)
+    fl = be.flows(net["fr"], net["to"], net["y"], U)
+    loss_q = ref.flows(net["fr"], net["to"], net["y"], U)["loss_q"][0]
+    lhs, rhs, mag = np.zeros(Hn), np.zeros(Hn), np.zeros(Hn)
+    for q in range(Hn):
+        Yq = sp.csr_matrix((net["Yval"][q], net["col"], net["rowptr"]), shape=(n, n))
+        assert abs(Yq - Yq.T).max() == 0
+        u = U[0, q]
+        lhs[q] = (np.conj(u) @ (Yq @ u)).real
+        rhs[q] = loss_q[q].sum() + (np.asarray(Yq.sum(axis=1)).ravel().real * np.abs(u) ** 2).sum()
+        mag[q] = np.abs(u) @ (abs(Yq) @ np.abs(u))
+    scale = abs(lhs[0])
+    res = np.abs(lhs - rhs)
+    print("\nENERGY %s: fundamental term %.6g p.u., fundamental loss %.6g p.u., largest residual %.3g, largest residual / (2^-53 M) %.3g"
+          % (name, scale, loss_q[0].sum(), res.max(), (res / np.maximum(2.0 ** -53 * mag, 1e-300)).max()))
+    assert scale > 0 and (res <= 16 * 2.0 ** -53 * mag).all()
+    if not name.startswith("lin4"):
+        assert (res <= 1e-12 * scale).all()
+    assert (np.abs(fl["loss_h"][0] - loss_q.sum(axis=1)) <= 1e-13 * np.abs(loss_q).sum(axis=1)).all()      # (the tiled order: rounding only)
+
+
+def _case(name="net3_H51_c", S=20):
+    net = be.network(name)
+    Vm, Va, ids, flags = be.scenario_set(net, S)
+    Vm[13], Va[13] = Vm[4], Va[4]                                 # tied maxima
+    U = ref.rect(Vm, Va, net["n"], net["Hn"])
+    ok = ref.thd_ok(Vm, net["n"], net["Hn"])
+    fl = ref.flows(net["fr"], net["to"], net["y"], U)
+    good = ((flags & 1) != 0) & ok
+    rating = np.array([be.midpoint_limit(fl["irms"][good, e]) for e in range(len(net["fr"]))])
+    return net, U, ids, flags, np.where(ok, 0.05, np.nan), fl, rating
+
+
+def _check(got, want):
+    for f in ref.EXACT:
+        assert np.array_equal(got[f], want[f]), f
+    added = int(want["counts"][0])
+    for pre in ref.QUANT:
+        x = want[pre]
+        for f, s in ((pre + "_sum", x.sum(0)), (pre + "_sumsq", (x * x).sum(0))):
+            assert (np.abs(got[f] - want[f]) <= ref.sum_bound(s, added)).all(), f
+
+
+@pytest.mark.parametrize("name", ["net1_H51_c", "net3_H51_c", "lin4_H11_c"])
+def test_emulated_statistics_equal_numpy(name):
+    net, U, ids, flags, thd, fl, rating = _case(name)
+    got = be.accumulate(net["fr"], net["to"], net["y"], U, ids, flags, thd, rating)
+    want = ref.accumulate(fl, ids, flags, np.isfinite(thd), rating)
+    assert want["counts"].tolist() == [19, 1, 0]
+    assert 0 < want["irms_over"].sum() < 19 * len(rating)          # the ratings do cut the samples
+    _check(got, want)
+    for a in ("irms_arg", "loss_arg", "lossh_arg"):
+        assert (got[a] != 7).all() and (got[a] != 13).all()        # the diverged scenario never; of the tied pair the smaller id
+
+
+def test_statistics_do_not_depend_on_order_or_splitting_and_the_queue_defers():
+    net, U, ids, flags, thd, fl, rating = _case()
+    a = (net["fr"], net["to"], net["y"])
+    one = be.accumulate(*a, U, ids, flags, thd, rating)
+    rng = np.random.default_rng(5)
+    for trial in range(4):
+        p = rng.permutation(len(ids))
+        cut = int(rng.integers(1, len(ids) - 1))
+        two = be.accumulate(*a, U[p[:cut]], ids[p[:cut]], flags[p[:cut]], thd[p[:cut]], rating)
+        two = be.accumulate(*a, U[p[cut:]], ids[p[cut:]], flags[p[cut:]], thd[p[cut:]], rating, into=two)
+        for f in ref.EXACT:
+            assert np.array_equal(one[f], two[f]), f
+        for f in ref.SUMS:
+            assert np.allclose(one[f], two[f], rtol=20 * 2.0 ** -52, atol=0)
+    same = be.accumulate(*a, U[:5], ids[:5], flags[:5], thd[:5], rating)
+    same = be.accumulate(*a, U[5:], ids[5:], flags[5:], thd[5:], rating, into=same)
+    for f in be.NAMES:
+        assert np.array_equal(one[f], same[f]), f                  # (the same order of arrival: the sums too)
+    fl2 = flags.copy()
+    fl2[0] |= 8
+    fl2[1] |= 64
+    fl2[7] |= 4
+    thd2 = thd.copy()
+    thd2[11] = np.nan
+    q = be.accumulate(*a, U, ids, fl2, thd2, rating, queue=True)
+    dfr = np.zeros(len(ids), bool)
+    dfr[[0, 1, 7]] = True
+    ok = np.isfinite(thd2)
+    want = ref.accumulate(fl, ids, fl2, ok, rating, deferred=dfr)
+    assert want["counts"].tolist() == [16, 1, 3]
+    _check(q, want)
+    _check(be.accumulate(*a, U, ids, fl2, thd2, rating, queue=False), ref.accumulate(fl, ids, fl2, ok, rating))
+    none = be.accumulate(*a, U, ids, np.zeros_like(flags), thd, rating)
+    assert none["counts"].tolist() == [0, 20, 0] and (none["irms_arg"] == -1).all() and not none["irms_max"].any() and not none["irms_over"].any()
+
+
+def _stats(arrays, rating):
+    return sweep.BranchStats(rating, **{k: arrays[k] for k in sweep.BranchStats.ARRAYS})
+
+
+def _check_whole(got, want):
+    _check({f: getattr(got, f) for f in sweep.BranchStats.ARRAYS}, want)
+
+
+def test_merge_of_parts_in_any_order_gives_the_whole():
+    net, U, ids, flags, thd, fl, rating = _case()
+    a = (net["fr"], net["to"], net["y"])
+    want = ref.accumulate(fl, ids, flags, np.isfinite(thd), rating)
+    for cuts in ((0, 9, 20), (0, 6, 13, 20)):
+        parts = [_stats(be.accumulate(*a, U[lo:hi], ids[lo:hi], flags[lo:hi], thd[lo:hi], rating), rating) for lo, hi in zip(cuts[:-1], cuts[1:])]
+        for order in itertools.permutations(range(len(parts))):
+            m = parts[order[0]]
+            for k in order[1:]:
+                m = m.merge(parts[k])
+            _check_whole(m, want)
+    empty = _stats(be.empty(len(rating)), rating)
+    _check_whole(empty.merge(parts[0]).merge(parts[1]).merge(empty).merge(parts[2]), want)
+    with pytest.raises(ValueError):
+        parts[0].merge(_stats(be.empty(len(rating)), rating * 2))
+    with pytest.raises(ValueError):
+        parts[0].merge(_stats(be.empty(len(rating) + 1), None))
+
+
+def test_mean_std_worst_pack_and_ids():
+    net, U, ids, flags, thd, fl, rating = _case()
+    st = _stats(be.accumulate(net["fr"], net["to"], net["y"], U, np.arange(20), flags, thd, rating), rating)
+    want = ref.accumulate(fl, np.arange(20), flags, np.isfinite(thd), rating)
+    added = st.added
+    assert added == 19
+    for pre in ref.QUANT:
+        v = want[pre]
+        m = v.mean(axis=0)
+        assert (np.abs(st.mean(pre) - m) <= (added + 2) * 2.0 ** -52 * np.abs(m)).all()
+        assert (np.abs(st.std(pre) ** 2 - v.var(axis=0)) <= 4 * (added + 4) * 2.0 ** -52 * (v * v).mean(axis=0)).all()
+        top = st.worst(3, pre)
+        order = np.argsort(-want[pre + "_max"], kind="stable")[:3]
+        assert [t[0] for t in top] == order.tolist() and [t[1] for t in top] == want[pre + "_arg"][order].tolist()
+        assert [t[2] for t in top] == want[pre + "_max"][order].tolist()
+    rel = st.worst(1, relative=True)[0]
+    assert rel[2] == (want["irms_max"] / rating).max()
+    back = st.unpack(st.pack())
+    for f in sweep.BranchStats.ARRAYS:
+        assert np.array_equal(getattr(back, f), getattr(st, f)) and getattr(back, f).dtype == getattr(st, f).dtype
+    gids = sweep.scenario_ids(3, 8, 20)
+    g = sweep.gather_branch_stats(st, 1, ids=gids)
+    _check_whole(g, ref.accumulate(fl, gids, flags, np.isfinite(thd), rating))
+    assert sweep.gather_branch_stats(st, 1) is st
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _worker(rank, world, port, q):
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    for p in (here, os.path.dirname(here)):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import torch.distributed as dist
+    import branch_emul as be_
+    from harmonic_power_flow_amd import sweep as sw
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    net, U, ids, flags, thd, fl, rating = _case()
+    mine = sw.scenario_ids(rank, world, len(ids) // world)
+    local = be_.accumulate(net["fr"], net["to"], net["y"], U[mine], np.arange(len(mine)), flags[mine], thd[mine], rating)   # local numbering
+    out = sw.gather_branch_stats(_stats(local, rating), world, ids=mine)
+    q.put((rank, {f: getattr(out, f) for f in sw.BranchStats.ARRAYS}))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_two_rank_gather_merges_strided_shares_under_global_ids():
+    import torch.multiprocessing as mp
+    world = 2
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = dict(q.get(timeout=180) for _ in range(world))
+    for p in procs:
+        p.join(timeout=120)
+        assert p.exitcode == 0
+    net, U, ids, flags, thd, fl, rating = _case()
+    want = ref.accumulate(fl, ids, flags, np.isfinite(thd), rating)
+    _check_whole(_stats(res[0], rating), want)
+    assert (want["irms_arg"] % 2 == 1).any() and (want["irms_arg"] % 2 == 0).any()          # maxima from both ranks
+    for f in sweep.BranchStats.ARRAYS:
+        assert np.array_equal(res[0][f], res[1][f]), f                                      # every rank holds the same statistics, sums included
+
+
+def test_entry_points_refuse_a_null_handle_before_any_device_call():
+    from harmonic_power_flow_amd import _lib
+    lib = _lib.load()
+    assert lib.hpf_num_branches(None) == -1
+    assert lib.hpf_get_branches(None, None, None, None) == -1
+    assert lib.hpf_branch_flows(None, *([None] * 6)) == -1
+    assert lib.hpf_branch_stats_begin(None, None) == -1
+    assert lib.hpf_branch_stats_add(None, 0) == -1
+    assert lib.hpf_branch_stats_get(None, *([None] * 14)) == -1
+    assert lib.hpf_branch_stats_end(None) == -1

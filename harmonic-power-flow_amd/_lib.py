@@ -70,6 +70,11 @@ SYMBOLS = {
     "hpf_branch_stats_add": (C.c_int, [_H, C.c_int]),
     "hpf_branch_stats_get": (C.c_int, [_H] + [C.c_void_p] * 14),
     "hpf_branch_stats_end": (C.c_int, [_H]),
+    "hpf_start_set": (C.c_int, [_H, c_dbl_p, c_dbl_p]),
+    "hpf_start_capture": (C.c_int, [_H, C.c_int]),
+    "hpf_start_get": (C.c_int, [_H, c_dbl_p, c_dbl_p]),
+    "hpf_start_clear": (C.c_int, [_H]),
+    "hpf_start_apply": (C.c_int, [_H, C.c_int]),
     "hpf_debug_stamps": (C.c_int, [_H, C.POINTER(C.c_longlong), C.c_int]),
     "hpf_set_option": (C.c_int, [_H, C.c_char_p, C.c_int]),
     "hpf_set_stream": (C.c_int, [_H, C.c_void_p]),

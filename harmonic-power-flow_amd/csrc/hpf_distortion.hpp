@@ -26,6 +26,14 @@ HPF_DIST_HD int dist_classify(int flags, double thd_max, bool queue) {
     return DIST_ADD;
 }
 
+// ... and with a start state (hpf_start_*): a scenario that was started from the handle's start state (flags bit 8) and did not converge is
+// solved again by the caller from the reference's start, which adds it -> deferred, not skipped (whoever looks: the queue or an explicit add);
+// every other record is classified as above.
+HPF_DIST_HD int dist_classify_start(int flags, double thd_max, bool queue) {
+    if ((flags & 256) && !(flags & 1)) return DIST_DEFER;
+    return dist_classify(flags, thd_max, queue);
+}
+
 // x of entry (bus, q) from the bus's Hn raw signed magnitudes: |V_1| for q = 0, the individual harmonic distortion |V_h| / |V_1| above
 HPF_DIST_HD double dist_x(const double* Vbus, int q) {
     const double v0 = fabs(Vbus[0]);

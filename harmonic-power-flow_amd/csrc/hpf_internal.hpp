@@ -274,6 +274,11 @@ struct hpf_handle {
     uint32_t* d_bs_over = nullptr;    // [nb] scenarios with irms above the rating
     long long* d_bs_cnt = nullptr;    // [3] added, skipped, deferred
     double* d_bs_rating = nullptr;    // [nb]
+    // start state (hpf_start_*; allocated while set only): one scenario's Vm, Va, U, E [n*Hn], bus-major like the state
+    bool start_set = false;
+    bool from_start = false;          // the current batch came from hpf_start_apply (until the next hpf_set_state): hpf_stat.flags bit 8
+    double *d_sVm = nullptr, *d_sVa = nullptr;
+    hpf::cplx *d_sU = nullptr, *d_sE = nullptr;
     int keep_prev = 0;
     bool prev_valid = false;          // d_Vmp / d_Vap belong to the last hpf_solve (set_state / set_loads invalidate them)
     double* d_hist = nullptr;         // [S][hist_cap]

@@ -694,10 +694,57 @@ __global__ void k_init_voltages(int Hn, int count, double* Vm, double* Va) {
     Va[o] = 0.0;
 }
 
-// get_THD (HG:563-572) THD_F per bus, max over buses, plus the result flags; one block per scenario.
+// ---- start state of the handle (hpf_start_*): sVm, sVa, sU, sE [n*Hn] bus-major like one scenario of the state.  One thread per (bus, harmonic)
+// entry k = i*Hn + q, consecutive threads on consecutive doubles of the bus-major side.
+// hpf_start_set: the caller's arrays in the ABI's stacked order q*n + i (uploaded as they are) -> bus-major, with U and E from polar<false>
+__global__ void k_start_set(int n, int Hn, const double* __restrict__ Vm0, const double* __restrict__ Va0, double* __restrict__ sVm,
+                            double* __restrict__ sVa, cplx* __restrict__ sU, cplx* __restrict__ sE) {
+    const int k = blockIdx.x * TPB + threadIdx.x;
+    if (k >= n * Hn) return;
+    const int i = k / Hn, q = k - i * Hn;
+    const double vm = Vm0[(size_t)q * n + i], va = Va0[(size_t)q * n + i];
+    cplx u, e;
+    polar<false>(vm, va, u, e);
+    sVm[k] = vm;
+    sVa[k] = va;
+    sU[k] = u;
+    sE[k] = e;
+}
+
+// hpf_start_capture: scenario `scen` of the batch -> the start state (U and E formed here, not copied: the batch's own are whatever the last
+// solver kernel left).  *bad (zeroed by the caller) becomes 1 if an entry is one hpf_start_set refuses: non-finite, or a zero magnitude
+__global__ void k_start_capture(int count, int scen, const double* __restrict__ Vm, const double* __restrict__ Va, double* __restrict__ sVm,
+                                double* __restrict__ sVa, cplx* __restrict__ sU, cplx* __restrict__ sE, int* __restrict__ bad) {
+    const int k = blockIdx.x * TPB + threadIdx.x;
+    if (k >= count) return;
+    const double vm = Vm[(size_t)scen * count + k], va = Va[(size_t)scen * count + k];
+    if (!isfinite(vm) || !isfinite(va) || vm == 0.0) *bad = 1;
+    cplx u, e;
+    polar<false>(vm, va, u, e);
+    sVm[k] = vm;
+    sVa[k] = va;
+    sU[k] = u;
+    sE[k] = e;
+}
+
+// hpf_start_apply: the start state -> every scenario of the batch (blockIdx.y)
+__global__ void k_start_apply(int count, const double* __restrict__ sVm, const double* __restrict__ sVa, const cplx* __restrict__ sU,
+                              const cplx* __restrict__ sE, double* __restrict__ Vm, double* __restrict__ Va, cplx* __restrict__ U,
+                              cplx* __restrict__ E) {
+    const int k = blockIdx.x * TPB + threadIdx.x;
+    if (k >= count) return;
+    const size_t o = (size_t)blockIdx.y * count + k;
+    Vm[o] = sVm[k];
+    Va[o] = sVa[k];
+    U[o] = sU[k];
+    E[o] = sE[k];
+}
+
+// get_THD (HG:563-572) THD_F per bus, max over buses, plus the result flags; one block per scenario.  start_bit: 256 when the batch was started
+// from the handle's start state (hpf_start_apply; k_queue_harvest: the queue ran with a start state set), else 0.
 __global__ void k_stats(int n, int Hn, double thresh, int max_iter, const double* __restrict__ Vm,
                         const double* __restrict__ err, const int* __restrict__ niter, const int* __restrict__ pivflag,
-                        hpf_stat* __restrict__ out) {
+                        int start_bit, hpf_stat* __restrict__ out) {
     const int s = blockIdx.x;
     const double* V = Vm + (size_t)s * n * Hn;
     double best = 0.0;
@@ -723,7 +770,7 @@ __global__ void k_stats(int n, int Hn, double thresh, int max_iter, const double
         st.err = e;
         const int pf = pivflag ? pivflag[s] : 0;
         st.flags = (e <= thresh ? 1 : 0) | ((niter[s] >= max_iter && !(e <= thresh)) ? 2 : 0) | ((e != e || isinf(e)) ? 4 : 0) |
-                   ((pf & 1) ? 8 : 0) | ((pf & 2) ? 16 : 0) | ((pf & 4) ? 32 : 0) | resid_flag_bits(pf);
+                   ((pf & 1) ? 8 : 0) | ((pf & 2) ? 16 : 0) | ((pf & 4) ? 32 : 0) | resid_flag_bits(pf) | start_bit;
         st.thd_max = __longlong_as_double((long long)r);
         out[s] = st;
     }
@@ -780,7 +827,7 @@ __global__ __launch_bounds__(1024) void k_queue_refill(int S_max, int n_total, i
 // per-scenario outputs of the sweep
 __global__ void k_queue_harvest(int n, int Hn, double thresh, int max_iter, const int* __restrict__ hlist, const int* __restrict__ hg,
                                 const double* __restrict__ Vm, const double* __restrict__ Va, const double* __restrict__ err,
-                                const int* __restrict__ niter, const int* __restrict__ pivflag, hpf_stat* __restrict__ qstats,
+                                const int* __restrict__ niter, const int* __restrict__ pivflag, int start_bit, hpf_stat* __restrict__ qstats,
                                 double* __restrict__ qVm, double* __restrict__ qVa) {
     const int s = hlist[blockIdx.x];
     if (s < 0) return;
@@ -810,7 +857,7 @@ __global__ void k_queue_harvest(int n, int Hn, double thresh, int max_iter, cons
         st.err = e;
         const int pf = pivflag[s];
         st.flags = (e <= thresh ? 1 : 0) | ((niter[s] >= max_iter && !(e <= thresh)) ? 2 : 0) | ((e != e || isinf(e)) ? 4 : 0) |
-                   ((pf & 1) ? 8 : 0) | ((pf & 4) ? 32 : 0) | resid_flag_bits(pf);
+                   ((pf & 1) ? 8 : 0) | ((pf & 4) ? 32 : 0) | resid_flag_bits(pf) | start_bit;
         st.thd_max = __longlong_as_double((long long)r);
         qstats[g] = st;
     }
@@ -843,7 +890,7 @@ __global__ void k_distortion_add(int n, int Hn, int L, const int* __restrict__ s
         for (int l = 0; l < L; ++l) {
             if (slots && slots[l] < 0) break;
             const hpf_stat st = stats[gids ? gids[l] : l];
-            c[dist_classify(st.flags, st.thd_max, queue != 0)] += 1;
+            c[dist_classify_start(st.flags, st.thd_max, queue != 0)] += 1;
         }
         for (int k = 0; k < 3; ++k) cnt[k] = cnt[k] + c[k];
         return;
@@ -860,7 +907,7 @@ __global__ void k_distortion_add(int n, int Hn, int L, const int* __restrict__ s
         if (s < 0) break;
         const int g = gids ? gids[l] : l;
         const hpf_stat st = stats[g];
-        if (dist_classify(st.flags, st.thd_max, queue != 0) != DIST_ADD) continue;
+        if (dist_classify_start(st.flags, st.thd_max, queue != 0) != DIST_ADD) continue;
         const double* Vbus = Vm + (size_t)s * E + (size_t)bus * Hn;
         const double x = t < E ? dist_x(Vbus, q) : dist_thd(Vbus, Hn);
         dist_fold(x, id_base + g, lim, mx, arg, sum, sumsq, over);
@@ -962,7 +1009,7 @@ __global__ __launch_bounds__(BR_TPB) void k_branch_add(int nb, int Hn, int n, in
         for (int l = 0; l < L; ++l) {
             if (slots && slots[l] < 0) break;
             const hpf_stat st = stats[gids ? gids[l] : l];
-            c[dist_classify(st.flags, st.thd_max, queue != 0)] += 1;
+            c[dist_classify_start(st.flags, st.thd_max, queue != 0)] += 1;
         }
         for (int k = 0; k < 3; ++k) cnt[k] = cnt[k] + c[k];
         return;
@@ -985,7 +1032,7 @@ __global__ __launch_bounds__(BR_TPB) void k_branch_add(int nb, int Hn, int n, in
         if (s < 0) break;
         const int g = gids ? gids[l] : l;
         const hpf_stat st = stats[g];
-        if (dist_classify(st.flags, st.thd_max, queue != 0) != DIST_ADD) continue;
+        if (dist_classify_start(st.flags, st.thd_max, queue != 0) != DIST_ADD) continue;
         const cplx* Us = U + (size_t)s * n * Hn;
         double irms, thd_i, loss_e, loss_harm;
         branch_fold(y, Us + oi, Us + oj, Hn, irms, thd_i, loss_e, loss_harm);
@@ -1024,6 +1071,33 @@ __global__ void k_queue_init(int n, int Hn, const int* __restrict__ newlist, con
     polar<false>(vm, va, u, e);
     U[o] = u;
     E[o] = e;
+    if (q == 0) {
+        P[(size_t)s * n + i] = qP[(size_t)g * n + i];
+        Q[(size_t)s * n + i] = qQ[(size_t)g * n + i];
+    }
+    if (k == 0) {
+        niter[s] = 0;
+        pivflag[s] = 0;
+    }
+}
+
+// ... with a start state set: the same move-in with Vm, Va, U, E copied from the start state (no power-flow seed)
+__global__ void k_queue_init_start(int n, int Hn, const int* __restrict__ newlist, const int* __restrict__ slot_scen, const double* __restrict__ qP,
+                                   const double* __restrict__ qQ, const double* __restrict__ sVm, const double* __restrict__ sVa,
+                                   const cplx* __restrict__ sU, const cplx* __restrict__ sE, double* __restrict__ P, double* __restrict__ Q,
+                                   double* __restrict__ Vm, double* __restrict__ Va, cplx* __restrict__ U, cplx* __restrict__ E,
+                                   int* __restrict__ niter, int* __restrict__ pivflag) {
+    const int s = newlist[blockIdx.y];
+    if (s < 0) return;
+    const int g = slot_scen[s];
+    const int k = blockIdx.x * TPB + threadIdx.x;
+    if (k >= n * Hn) return;
+    const int i = k / Hn, q = k - i * Hn;
+    const size_t o = (size_t)s * n * Hn + k;
+    Vm[o] = sVm[k];
+    Va[o] = sVa[k];
+    U[o] = sU[k];
+    E[o] = sE[k];
     if (q == 0) {
         P[(size_t)s * n + i] = qP[(size_t)g * n + i];
         Q[(size_t)s * n + i] = qQ[(size_t)g * n + i];
@@ -1526,6 +1600,28 @@ void distortion_free(hpf_handle* h) {
     h->dist_open = false;
 }
 
+void start_free(hpf_handle* h) {
+    void* ptrs[] = {h->d_sVm, h->d_sVa, h->d_sU, h->d_sE};
+    for (void* p : ptrs)
+        if (p) hipFree(p);
+    h->d_sVm = h->d_sVa = nullptr;
+    h->d_sU = h->d_sE = nullptr;
+    h->start_set = false;
+}
+
+// the four start arrays of a handle that has none yet
+int start_alloc(hpf_handle* h) {
+    if (h->d_sVm) return HPF_OK;
+    const size_t count = (size_t)h->n * h->Hn;
+    int r;
+    if ((r = dev_alloc(h, &h->d_sVm, count)) || (r = dev_alloc(h, &h->d_sVa, count)) || (r = dev_alloc(h, &h->d_sU, count)) ||
+        (r = dev_alloc(h, &h->d_sE, count))) {
+        start_free(h);
+        return r;
+    }
+    return HPF_OK;
+}
+
 void branch_stats_free(hpf_handle* h) {
     void* ptrs[] = {h->d_bs_f, h->d_bs_arg, h->d_bs_over, h->d_bs_cnt, h->d_bs_rating};
     for (void* p : ptrs)
@@ -1650,7 +1746,7 @@ int nr_loop(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* err
     }
     if (!FUND) {
         hipLaunchKernelGGL(k_stats, dim3(S), dim3(TPB), 0, h->stream, h->n, h->Hn, thresh, max_iter, h->d_Vm, h->d_err,
-                           h->d_niter, h->d_pivflag, h->d_stats);
+                           h->d_niter, h->d_pivflag, h->from_start ? 256 : 0, h->d_stats);
         std::vector<int> pf(S);
         HIPCHK(hipMemcpyAsync(pf.data(), h->d_pivflag, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -1685,8 +1781,9 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
             if (q) hipFree(q);
         return code;
     };
+    const bool warm = h->start_set;                      // every scenario begins at the handle's start state: no pf, no seed arrays
     if ((r = dev_alloc(h, &qP, (size_t)n_total * n)) || (r = dev_alloc(h, &qQ, (size_t)n_total * n)) ||
-        (r = dev_alloc(h, &sVm, (size_t)n_total * n)) || (r = dev_alloc(h, &sVa, (size_t)n_total * n)) ||
+        (!warm && ((r = dev_alloc(h, &sVm, (size_t)n_total * n)) || (r = dev_alloc(h, &sVa, (size_t)n_total * n)))) ||
         (r = dev_alloc(h, &qst, (size_t)n_total)) || (r = dev_alloc(h, &qi, (size_t)4 * S_max + 2)))
         return cleanup(r);
     if (Vm && ((r = dev_alloc(h, &qVm, (size_t)n_total * count)) || (r = dev_alloc(h, &qVa, (size_t)n_total * count)))) return cleanup(r);
@@ -1695,9 +1792,11 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
         hipMemcpyAsync(qQ, Q, sizeof(double) * (size_t)n_total * n, hipMemcpyHostToDevice, h->stream) != hipSuccess)
         return cleanup(HPF_E_HIP);
     // ---- fundamental power flow (HG:244-275) of every scenario from the reference's start, in waves of S_max; only the fundamental
-    //      entries are kept (the harmonic rows of the seed are the constants of HG:181-183)
-    for (int g0 = 0; g0 < n_total; g0 += S_max) {
-        const int S = n_total - g0 < S_max ? n_total - g0 : S_max;
+    //      entries are kept (the harmonic rows of the seed are the constants of HG:181-183).  With a start state set there is no pf
+    //      phase: no scenario goes through these waves
+    const int n_pf = warm ? 0 : n_total;
+    for (int g0 = 0; g0 < n_pf; g0 += S_max) {
+        const int S = n_pf - g0 < S_max ? n_pf - g0 : S_max;
         h->S = S;
         hipMemcpyAsync(h->d_P, qP + (size_t)g0 * n, sizeof(double) * (size_t)S * n, hipMemcpyDeviceToDevice, h->stream);
         hipMemcpyAsync(h->d_Q, qQ + (size_t)g0 * n, sizeof(double) * (size_t)S * n, hipMemcpyDeviceToDevice, h->stream);
@@ -1735,11 +1834,15 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
         hipLaunchKernelGGL(k_queue_refill, dim3(1), dim3(1024), q_lds, h->stream, S_max, n_total, h->d_active, h->d_nactive, slot_scen, next,
                            hlist, hg, newlist, base);
         hipLaunchKernelGGL(k_queue_harvest, dim3((unsigned)S_max), dim3(TPB), 0, h->stream, n, Hn, thresh, max_iter, hlist, hg, h->d_Vm,
-                           h->d_Va, h->d_err, h->d_niter, h->d_pivflag, qst, qVm, qVa);
+                           h->d_Va, h->d_err, h->d_niter, h->d_pivflag, warm ? 256 : 0, qst, qVm, qVa);
         if (h->dist_open && distortion_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;   // (before the storages are refilled)
         if (h->bstat_open && branch_add_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;
-        hipLaunchKernelGGL(k_queue_init, grid2((int)count, S_max), dim3(TPB), 0, h->stream, n, Hn, newlist, slot_scen, qP, qQ, sVm, sVa,
-                           h->d_P, h->d_Q, h->d_Vm, h->d_Va, h->d_U, h->d_E, h->d_niter, h->d_pivflag);
+        if (warm)
+            hipLaunchKernelGGL(k_queue_init_start, grid2((int)count, S_max), dim3(TPB), 0, h->stream, n, Hn, newlist, slot_scen, qP, qQ, h->d_sVm,
+                               h->d_sVa, h->d_sU, h->d_sE, h->d_P, h->d_Q, h->d_Vm, h->d_Va, h->d_U, h->d_E, h->d_niter, h->d_pivflag);
+        else
+            hipLaunchKernelGGL(k_queue_init, grid2((int)count, S_max), dim3(TPB), 0, h->stream, n, Hn, newlist, slot_scen, qP, qQ, sVm, sVa,
+                               h->d_P, h->d_Q, h->d_Vm, h->d_Va, h->d_U, h->d_E, h->d_niter, h->d_pivflag);
         set_ctx(h, h->stream, 0, S_max);
         int rr = launch_mismatch<false>(h, newlist, false);
         full_ctx(h);
@@ -1789,7 +1892,7 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
                hipMemcpy(Va, qVa, sizeof(double) * (size_t)n_total * count, hipMemcpyDeviceToHost) != hipSuccess))
         return cleanup(HPF_E_HIP);
     // the handle is left without a defined batch: loads and state have to be set again before the per-batch entry points
-    h->loads_set = h->state_set = h->solve_done = false;
+    h->loads_set = h->state_set = h->solve_done = h->from_start = false;
     h->S = 0;
     return cleanup(HPF_OK);
 }
@@ -1802,6 +1905,7 @@ void free_all(hpf_handle* h) {
         if (p) hipFree(p);
     distortion_free(h);
     branch_free(h);
+    start_free(h);
     tree_free(h);
     for (auto& sp : h->spans) {
         hipEventDestroy(sp.e0);
@@ -2041,6 +2145,7 @@ int hpf_set_state(hpf_handle* h, int n_scen, const double* Vm, const double* Va)
     }
     if (h->resid_check && reset_step_eta(h)) return HPF_E_HIP;       // (a new state: no step taken yet)
     HIPCHK(hipStreamSynchronize(h->stream));
+    h->from_start = false;
     h->state_set = true;
     h->mismatch_valid = false;
     h->prev_valid = false;
@@ -2062,6 +2167,101 @@ int hpf_get_state(hpf_handle* h, double* Vm, double* Va) {
                 Vm[(size_t)sc * count + (size_t)q * h->n + i] = tm[(size_t)sc * count + (size_t)i * h->Hn + q];
                 Va[(size_t)sc * count + (size_t)q * h->n + i] = ta[(size_t)sc * count + (size_t)i * h->Hn + q];
             }
+    return HPF_OK;
+}
+
+int hpf_start_set(hpf_handle* h, const double* Vm0, const double* Va0) {
+    if (!h || !Vm0 || !Va0) return HPF_E_ARG;
+    const size_t count = (size_t)h->n * h->Hn;
+    for (size_t k = 0; k < count; ++k)
+        if (!isfinite(Vm0[k]) || !isfinite(Va0[k]) || Vm0[k] == 0.0) return HPF_E_ARG;      // (E = U / Vm)
+    int r;
+    double* tmp = nullptr;                               // the caller's arrays as they are (stacked); the kernel transposes
+    if ((r = start_alloc(h)) || (r = dev_alloc(h, &tmp, 2 * count))) return r;
+    hipError_t e = hipMemcpyAsync(tmp, Vm0, sizeof(double) * count, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(tmp + count, Va0, sizeof(double) * count, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_start_set, dim3((unsigned)((count + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, h->n, h->Hn, tmp, tmp + count, h->d_sVm,
+                           h->d_sVa, h->d_sU, h->d_sE);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    hipFree(tmp);
+    if (e != hipSuccess) {
+        h->last_detail = (int)e;
+        start_free(h);
+        return HPF_E_HIP;
+    }
+    h->start_set = true;
+    return HPF_OK;
+}
+
+int hpf_start_capture(hpf_handle* h, int scen) {
+    if (!h) return HPF_E_ARG;
+    if (!h->state_set || h->S < 1) return HPF_E_STATE;
+    if (scen < 0 || scen >= h->S) return HPF_E_ARG;
+    const int count = h->n * h->Hn;
+    int r, bad = 0;
+    if ((r = start_alloc(h))) return r;
+    // (d_nactive: the solvers' counter word, free between two calls, takes the validity verdict)
+    hipError_t e = hipMemsetAsync(h->d_nactive, 0, sizeof(int), h->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_start_capture, dim3((unsigned)((count + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, count, scen, h->d_Vm, h->d_Va,
+                           h->d_sVm, h->d_sVa, h->d_sU, h->d_sE, h->d_nactive);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, h->d_nactive, sizeof(int), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess || bad) {                        // the buffers may be partly overwritten: no start state is left
+        start_free(h);
+        if (e == hipSuccess) return HPF_E_STATE;
+        h->last_detail = (int)e;
+        return HPF_E_HIP;
+    }
+    h->start_set = true;
+    return HPF_OK;
+}
+
+int hpf_start_get(hpf_handle* h, double* Vm0, double* Va0) {
+    if (!h || !Vm0 || !Va0) return HPF_E_ARG;
+    if (!h->start_set) return HPF_E_STATE;
+    const size_t count = (size_t)h->n * h->Hn;
+    std::vector<double> tm(count), ta(count);
+    HIPCHK(hipMemcpyAsync(tm.data(), h->d_sVm, sizeof(double) * count, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(ta.data(), h->d_sVa, sizeof(double) * count, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int q = 0; q < h->Hn; ++q)                                         // device bus-major -> ABI stacked order
+        for (int i = 0; i < h->n; ++i) {
+            Vm0[(size_t)q * h->n + i] = tm[(size_t)i * h->Hn + q];
+            Va0[(size_t)q * h->n + i] = ta[(size_t)i * h->Hn + q];
+        }
+    return HPF_OK;
+}
+
+int hpf_start_clear(hpf_handle* h) {
+    if (!h) return HPF_E_ARG;
+    if (!h->d_sVm) return HPF_OK;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    start_free(h);
+    return HPF_OK;
+}
+
+int hpf_start_apply(hpf_handle* h, int n_scen) {
+    if (!h || n_scen < 1 || n_scen > h->S_max) return HPF_E_ARG;
+    if (!h->start_set) return HPF_E_STATE;
+    if (h->loads_set && n_scen != h->S) return HPF_E_ARG;                   // (the rules of hpf_set_state)
+    h->S = n_scen;
+    const int count = h->n * h->Hn;
+    hipLaunchKernelGGL(k_start_apply, grid2(count, n_scen), dim3(TPB), 0, h->stream, count, h->d_sVm, h->d_sVa, h->d_sU, h->d_sE, h->d_Vm, h->d_Va,
+                       h->d_U, h->d_E);
+    if (launch_status(h)) return HPF_E_HIP;
+    if (h->resid_check && reset_step_eta(h)) return HPF_E_HIP;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->from_start = true;
+    h->state_set = true;
+    h->mismatch_valid = false;
+    h->prev_valid = false;
+    h->solve_done = false;
     return HPF_OK;
 }
 
@@ -2223,15 +2423,19 @@ int hpf_solve_queue(hpf_handle* h, int n_total, const double* P, const double* Q
         const int S = n_total - g0 < h->S_max ? n_total - g0 : h->S_max;
         int r;
         if ((r = hpf_set_loads(h, S, P + (size_t)g0 * h->n, Q + (size_t)g0 * h->n))) return r;
-        if ((r = hpf_set_state(h, S, nullptr, nullptr))) return r;
-        if ((r = hpf_fund_pf(h, thresh_f, max_iter_f, nullptr, nullptr, nullptr))) return r;
+        if (h->start_set) {                              // every scenario from the handle's start state, no pf
+            if ((r = hpf_start_apply(h, S))) return r;
+        } else {
+            if ((r = hpf_set_state(h, S, nullptr, nullptr))) return r;
+            if ((r = hpf_fund_pf(h, thresh_f, max_iter_f, nullptr, nullptr, nullptr))) return r;
+        }
         if ((r = hpf_solve(h, thresh, max_iter, nullptr, nullptr, nullptr))) return r;
         if (h->dist_open && (r = distortion_launch(h, S, nullptr, nullptr, h->dist_id_base + g0, true, h->d_stats))) return r;
         if (h->bstat_open && (r = branch_add_launch(h, S, nullptr, nullptr, h->dist_id_base + g0, true, h->d_stats))) return r;
         if (stats && (r = hpf_get_stats(h, stats + g0))) return r;
         if (Vm && (r = hpf_get_state(h, Vm + (size_t)g0 * cnt, Va + (size_t)g0 * cnt))) return r;
     }
-    h->loads_set = h->state_set = h->solve_done = false;   // (as on the queued path: the handle is left without a defined batch)
+    h->loads_set = h->state_set = h->solve_done = h->from_start = false;   // (as on the queued path: the handle is left without a defined batch)
     h->S = 0;
     return HPF_OK;
 }

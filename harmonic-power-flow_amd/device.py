@@ -156,6 +156,43 @@ class DeviceModel:
         self._chk(self.lib.hpf_get_state(self._h, _dp(Vm), _dp(Va)), "hpf_get_state")
         return Vm, Va
 
+    # -- start state (hpf_start_*) ---------------------------------------------------------------------------
+    def set_start(self, Vm, Va):
+        """The handle's start state from host arrays [Hn*n] (stacked order, raw as get_state returns them): while it is set, every scenario of
+        solve_queue begins there instead of at the reference's flat start + pf (include/hpf.h, "Start state")."""
+        Vm = np.ascontiguousarray(Vm, dtype=np.float64).reshape(-1)
+        Va = np.ascontiguousarray(Va, dtype=np.float64).reshape(-1)
+        assert Vm.shape == Va.shape == (self.n * self.Hn,)
+        self._chk(self.lib.hpf_start_set(self._h, _dp(Vm), _dp(Va)), "hpf_start_set")
+
+    def capture_start(self, scen=0):
+        """The start state from scenario `scen` of the current batch (after solve()), device to device."""
+        self._chk(self.lib.hpf_start_capture(self._h, int(scen)), "hpf_start_capture")
+
+    def get_start(self):
+        """-> (Vm, Va) [Hn*n] of the start state; HPF_E_STATE when none is set."""
+        Vm = np.empty(self.n * self.Hn)
+        Va = np.empty_like(Vm)
+        self._chk(self.lib.hpf_start_get(self._h, _dp(Vm), _dp(Va)), "hpf_start_get")
+        return Vm, Va
+
+    def has_start(self):
+        """True while the handle holds a start state (hpf_start_get answers HPF_E_STATE without one, before any device call)."""
+        try:
+            self.get_start()
+        except _lib.HpfError as e:
+            if e.code != -2:
+                raise
+            return False
+        return True
+
+    def clear_start(self):
+        self._chk(self.lib.hpf_start_clear(self._h), "hpf_start_clear")
+
+    def apply_start(self, n_scen):
+        """set_state of the start state tiled to n_scen scenarios, on the device; solve() then marks the records with flags bit 8."""
+        self._chk(self.lib.hpf_start_apply(self._h, int(n_scen)), "hpf_start_apply")
+
     # -- kernels -------------------------------------------------------------------------------------------
     def mismatch(self, fund=False, want_f=True):
         N = self.Nf if fund else self.N
@@ -230,7 +267,8 @@ class DeviceModel:
         return n_iter, err, hist
 
     def solve_queue(self, P, Q, thresh_f=1e-6, max_iter_f=30, thresh=1e-4, max_iter=50, want_voltages=False):
-        """hpf_solve_queue: every row of P, Q [n_scen][n] is one scenario (reference start, pf, harmonic NR); the handle's S_max slots are
+        """hpf_solve_queue: every row of P, Q [n_scen][n] is one scenario (reference start, pf, harmonic NR -- with a start state set: the start
+        state, no pf, thresh_f / max_iter_f ignored, records with flags bit 8); the handle's S_max slots are
         refilled with pending scenarios as running ones meet the stop rule.  -> records (n_iter, flags, err, thd_max) [n_scen]
         [, raw Vm, Va [n_scen][Hn*n]].  Leaves the handle without a batch (set_loads / set_state before the per-batch calls)."""
         P = np.ascontiguousarray(np.atleast_2d(P), dtype=np.float64)

@@ -244,7 +244,7 @@ def gather_branch_stats(stats, world, ids=None):
 
 
 def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_iter_h=50, want_voltages=False, refill=True, distortion=None,
-                    branches=None):
+                    branches=None, start=None):
     """Monte-Carlo / what-if sweep on ONE GPU: every row of P, Q [n_scen][n] (p.u. loads, HG:197,372) is one scenario of the
     network `dm` (a DeviceModel) holds -- the reference's counterpart is one hpf() call per load case (HG:511).  Per scenario:
     reference start (HG:174-184), fundamental pf (HG:244), harmonic NR with the reference's stop rule (HG:536).
@@ -253,7 +253,9 @@ def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_i
     than slots runs at the lock-step rate of a full handle instead of paying every wave's convergence tail (size the model for as
     many live scenarios as fit: 72 MB of solver state per scenario of the 1 000-bus x 25-harmonic feeder; larger batches amortise the
     latency-bound upper tree levels).  A scenario the static-pivot monitor flags (flags bit 3), whose mismatch turned non-finite in the
-    static-pivot kernels (bit 2), or whose step missed the residual check (bit 6, option "step_residual_check"), is solved again on its own through `hpf_solve`, which repeats exactly those with partial pivoting.
+    static-pivot kernels (bit 2), or whose step missed the residual check (bit 6, option "step_residual_check"), is solved again on its own through
+    `hpf_solve`, which repeats exactly those with partial pivoting on a radial block-tree handle; a meshed handle has no pivoted repeat (its re-solve
+    runs the same static-pivot step again), a dense handle pivots in every solve.
     refill=False: fixed waves of up to S_max scenarios (each through fund_pf + solve).
     -> structured array of per-scenario records (n_iter, flags, err, thd_max: the 24-byte record of the multi-GPU gather)
     [+ raw Vm, Va [n_scen][Hn*n]]; every record and voltage is bit-identical to the scenario solved alone.
@@ -263,28 +265,71 @@ def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_i
     distortion_add), and the DistortionStats are returned as an additional last element; records and voltages are unchanged.
     branches: None (default), or a dict {"rating": [nb] or None}: likewise for the handle's branch statistics (hpf_branch_stats_*: per line
     the RMS current over all harmonics against its rating, series loss, harmonic loss); the BranchStats are returned as a further last element,
-    after the DistortionStats when both are asked for."""
-    if distortion is None and branches is None:
-        return _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, False, False)
-    if distortion is not None:
-        dm.distortion_begin(distortion.get("limit"), distortion.get("thd_limit", np.inf), distortion.get("hist_max", 1.0),
-                            distortion.get("bins", 64))
+    after the DistortionStats when both are asked for.
+    start: None (default): the reference's flat start + pf for every scenario, today's behaviour bit for bit (a handle on which the caller
+    has set a start state of its own is refused with ValueError: clear it, or pass it as `start`).  Otherwise a WARM START -- every
+    scenario begins at one solved state of the feeder (the handle's start state, hpf_start_*), the pf phase is skipped (thresh_f / max_iter_f
+    then only serve cold re-solves), and the harmonic NR of a Monte-Carlo sweep around a base case needs 2 - 3 iterations instead of 20 - 30
+    (DESIGN.md 6.3).  A pair (Vm0, Va0) [Hn*n] (raw, as get_state returns them): used as given.  A dict {"P": P0, "Q": Q0} [n]: the base case
+    with these loads is solved cold on the handle first (one scenario, reference start, pf, harmonic NR to min(thresh_h, 1e-9)) and captured on
+    the device; RuntimeError if it does not converge.  "mean": shorthand for the column means of this call's P, Q -- which DEPENDS on the
+    scenarios this call holds: a multi-GPU sweep whose results must not depend on the number of GPUs passes the same {"P", "Q"} on every rank.
+    Records of warm scenarios carry flags bit 8, and each is bit-identical to apply_start(1) + set_loads + solve of the scenario alone.  A warm
+    scenario that does not converge (bit 8 without bit 0) is solved again cold, exactly as with start=None (its final record has no bit 8); the
+    flagged ones (bits 2, 3, 6) are repeated from the start state through apply_start + solve first and go the cold way if that leaves them
+    not converged.  The accumulators count a scenario that is solved again as deferred and add it once, from the solve whose record is returned.
+    The start state is taken off the handle for the cold re-solves and put back after them, and cleared when the call returns."""
+    if start is None:
+        if dm.has_start():
+            raise ValueError("solve_scenarios(start=None) on a handle that holds a start state: clear_start() first, or pass start=dm.get_start()")
+    else:
+        _set_start(dm, P, Q, start, thresh_f, max_iter_f, thresh_h, max_iter_h)
     try:
-        if branches is not None:
-            dm.branch_stats_begin(branches.get("rating"))
-        res = _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion is not None,
-                               branches is not None)
-        extra = (() if distortion is None else (dm.distortion_get(),)) + (() if branches is None else (dm.branch_stats_get(),))
-    finally:
-        dm.set_option("distortion_id_base", 0)
+        if distortion is None and branches is None:
+            return _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, False, False, start is not None)
         if distortion is not None:
-            dm.distortion_end()
-        if branches is not None:
-            dm.branch_stats_end()
-    return (res if want_voltages else (res,)) + extra
+            dm.distortion_begin(distortion.get("limit"), distortion.get("thd_limit", np.inf), distortion.get("hist_max", 1.0),
+                                distortion.get("bins", 64))
+        try:
+            if branches is not None:
+                dm.branch_stats_begin(branches.get("rating"))
+            res = _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion is not None,
+                                   branches is not None, start is not None)
+            extra = (() if distortion is None else (dm.distortion_get(),)) + (() if branches is None else (dm.branch_stats_get(),))
+        finally:
+            dm.set_option("distortion_id_base", 0)
+            if distortion is not None:
+                dm.distortion_end()
+            if branches is not None:
+                dm.branch_stats_end()
+        return (res if want_voltages else (res,)) + extra
+    finally:
+        if start is not None:
+            dm.clear_start()
 
 
-def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion, branches):
+def _set_start(dm, P, Q, start, thresh_f, max_iter_f, thresh_h, max_iter_h):
+    """the handle's start state from the `start` argument of solve_scenarios"""
+    if isinstance(start, (tuple, list)) and len(start) == 2:
+        dm.set_start(*start)
+        return
+    if isinstance(start, str) and start == "mean":
+        P2, Q2 = np.atleast_2d(np.asarray(P, dtype=np.float64)), np.atleast_2d(np.asarray(Q, dtype=np.float64))
+        start = {"P": P2.mean(axis=0), "Q": Q2.mean(axis=0)}
+    if not (isinstance(start, dict) and "P" in start and "Q" in start):
+        raise ValueError("solve_scenarios: start=%r (None, a pair (Vm0, Va0), {'P': .., 'Q': ..} or 'mean')" % (start,))
+    dm.set_loads(np.asarray(start["P"], dtype=np.float64).reshape(1, -1), np.asarray(start["Q"], dtype=np.float64).reshape(1, -1))
+    dm.set_state(None, None, n_scen=1)
+    dm.fund_pf(thresh_f, max_iter_f)
+    dm.solve(min(thresh_h, 1e-9), max_iter_h)
+    st = dm.stats()[0]
+    if not (st["flags"] & 1):
+        raise RuntimeError("solve_scenarios: the base case of the warm start did not converge (n_iter %d, flags %d, err %.3e)"
+                           % (st["n_iter"], st["flags"], st["err"]))
+    dm.capture_start(0)
+
+
+def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion, branches, warm=False):
     P = np.ascontiguousarray(np.atleast_2d(P), dtype=np.float64)
     Q = np.ascontiguousarray(np.atleast_2d(Q), dtype=np.float64)
     n_scen = P.shape[0]
@@ -294,24 +339,48 @@ def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_
         Vm = np.empty((n_scen, dm.n * dm.Hn))
         Va = np.empty_like(Vm)
 
-    def wave(a, b):
+    def wave(a, b, from_start=False, keep_unconverged=True):
+        """scenarios a..b-1 as one batch: cold (reference start + pf) or from the start state.  keep_unconverged=False (one scenario): a result that did not converge is dropped, neither
+        stored nor added -- the caller solves the scenario again -> False"""
         dm.set_loads(P[a:b], Q[a:b])
-        dm.set_state(None, None, n_scen=b - a)
-        dm.fund_pf(thresh_f, max_iter_f)
+        if from_start:
+            dm.apply_start(b - a)
+        else:
+            dm.set_state(None, None, n_scen=b - a)
+            dm.fund_pf(thresh_f, max_iter_f)
         dm.solve(thresh_h, max_iter_h)
+        st = dm.stats()
+        if not keep_unconverged and not (st["flags"] & 1).all():
+            return False
         if distortion:
             dm.distortion_add(a)
         if branches:
             dm.branch_stats_add(a)
-        st = dm.stats()
         for k in STAT_DTYPE.names:
             out[k][a:b] = st[k]
         if want_voltages:
             Vm[a:b], Va[a:b] = dm.get_state()
+        return True
+
+    def cold_resolves(more=()):
+        # started from the start state (bit 8) and not converged, and the scenarios of `more`: each alone from the reference's start, as a sweep
+        # without a start solves it -- with the start state off the handle meanwhile, so that nothing of that solve can read it
+        todo = sorted(set(np.nonzero(((out["flags"] & 256) != 0) & ((out["flags"] & 1) == 0))[0].tolist()) | set(more))
+        if not todo:
+            return
+        kept = dm.get_start()
+        dm.clear_start()
+        try:
+            for s in todo:
+                wave(s, s + 1)
+        finally:
+            dm.set_start(*kept)
 
     if not refill:
         for a in range(0, n_scen, dm.S_max):
-            wave(a, min(a + dm.S_max, n_scen))
+            wave(a, min(a + dm.S_max, n_scen), from_start=warm)
+        if warm:
+            cold_resolves()
         return (out, Vm, Va) if want_voltages else out
     # the device keeps the voltages of a whole call: bound a call by ~8 GB of result buffers when they are asked for
     per_call = n_scen if not want_voltages else max(dm.S_max, int(8e9 // (16 * dm.n * dm.Hn)))
@@ -327,9 +396,16 @@ def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_
         for k in STAT_DTYPE.names:
             out[k][a:b] = rec[k]
     # static pivot order flagged (bit 3), non-finite mismatch (bit 2) or a step over the residual limit (bit 6) -- the conditions hpf_solve's
-    # repeat pass looks at (k_mark_repeat): the scenario alone, hpf_solve repeats it pivoted
+    # repeat pass looks at (k_mark_repeat): the scenario alone, hpf_solve repeats it pivoted on a radial block-tree handle (a meshed handle has
+    # no pivoted repeat: the re-solve runs the same static-pivot step again)
+    failed = []                                          # repeated from the start state without converging: the cold way below
     for s in np.nonzero((out["flags"] & (8 | 4 | 64)) != 0)[0]:
-        wave(int(s), int(s) + 1)
+        if not warm:
+            wave(int(s), int(s) + 1)
+        elif not wave(int(s), int(s) + 1, from_start=True, keep_unconverged=False):
+            failed.append(int(s))
+    if warm:
+        cold_resolves(failed)
     return (out, Vm, Va) if want_voltages else out
 
 

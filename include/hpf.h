@@ -84,7 +84,8 @@ typedef struct hpf_stat {
                                   bit4 the scenario was repeated with partial pivoting (its result is the repeat's),
                                   bit5 the pivoted elimination met an exactly zero pivot (hpf_solve returns HPF_E_SINGULAR),
                                   bit6 option "step_residual_check": a Newton step of the first pass missed the residual limit,
-                                  bit7 ... a step of the pass whose result is returned did (= bit6 unless bit4 is set) */
+                                  bit7 ... a step of the pass whose result is returned did (= bit6 unless bit4 is set),
+                                  bit8 the scenario was started from the handle's start state (hpf_start_*), not from the reference's start + pf */
     double  err;               /* final ||f||_inf                                        HG:389 */
     double  thd_max;           /* max over buses of THD_F                                HG:566-568 */
 } hpf_stat;
@@ -168,7 +169,9 @@ int  hpf_solve(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* 
  * solve alone (the arithmetic of a scenario does not depend on its slot).  Other handles (DENSE, meshed networks, pivoted mode) run waves of
  * S_max scenarios.  Outputs (host, may be NULL; Vm and Va together): stats [n_total], raw voltages Vm, Va [n_total][Hn*n] (stacked order,
  * signed / un-wrapped like hpf_get_state).  In the queued mode a scenario flagged by the static-pivot monitor (flags bit 3) or whose mismatch
- * turned non-finite (flags bit 2), or whose step missed the residual check (flags bit 6), is reported, not repeated: solve it again with hpf_solve (which repeats exactly those with partial pivoting).  Afterwards the handle holds no batch: set loads and state before per-batch calls. */
+ * turned non-finite (flags bit 2), or whose step missed the residual check (flags bit 6), is reported, not repeated: solve it again with hpf_solve (which repeats exactly those with partial pivoting).  Afterwards the handle holds no batch: set loads and state before per-batch calls.
+ * With a start state set (hpf_start_set / hpf_start_capture below) every scenario begins at that state instead: no pf phase -- thresh_f and
+ * max_iter_f are IGNORED -- and every record carries flags bit 8. */
 int  hpf_solve_queue(hpf_handle* h, int n_total, const double* P, const double* Q, double thresh_f, int max_iter_f, double thresh,
                      int max_iter, hpf_stat* stats, double* Vm, double* Va);
 
@@ -295,6 +298,37 @@ int  hpf_branch_stats_get(hpf_handle* h, int64_t* counts, double* irms_max, int3
                           uint32_t* irms_over, double* loss_max, int32_t* loss_arg, double* loss_sum, double* loss_sumsq, double* lossh_max,
                           int32_t* lossh_arg, double* lossh_sum, double* lossh_sumsq);
 int  hpf_branch_stats_end(hpf_handle* h);
+
+/* Start state: warm-start the scenarios of a sweep from one solved case instead of the reference's flat start (HG:174-184) + pf (HG:244-275).  The
+ * reference has no counterpart (hpf() always starts flat, HG:511-529).  The scenarios of a Monte-Carlo sweep sit close to each other: from the whole
+ * raw state of the feeder solved at its nominal loads the harmonic NR needs 2 - 3 iterations where the flat start needs 20 - 30.
+ * The handle owns ONE start state: Vm, Va of one scenario and the U = Vm e^(j Va), E = U / Vm formed from them once (the arithmetic hpf_solve applies
+ * to a state set with hpf_set_state), in the bus-major layout of the state.  Unset (the default): nothing is allocated, no kernel is launched, every
+ * output of every entry point is unchanged.
+ * hpf_start_set: Vm0, Va0 [Hn*n] host arrays in the ABI's stacked order, raw (signed, un-wrapped, as hpf_get_state returns them); replaces a set
+ *   one.  HPF_E_ARG for a NULL handle or pointer, a non-finite entry or a zero magnitude (E = U / Vm) -- all checked on the host before any HIP call.
+ * hpf_start_capture: the same from scenario `scen` of the current batch, device to device: a base case solved on this handle becomes the start
+ *   without a host round trip.  HPF_E_STATE without a batch, HPF_E_ARG for scen outside the batch.  A scenario whose state holds an entry
+ *   hpf_start_set would refuse (non-finite, zero magnitude; checked by the kernel) returns HPF_E_STATE; after that, or after a HIP error, the
+ *   handle holds NO start state (a set one is lost: its buffers were being overwritten).
+ * hpf_start_get: copies the start state out (stacked order); HPF_E_STATE when unset.
+ * hpf_start_clear: frees the buffers (HPF_OK when already unset); hpf_destroy frees a set one.
+ * hpf_start_apply: = hpf_set_state of the start state tiled to n_scen scenarios, broadcast on the device (the argument rules of hpf_set_state);
+ *   HPF_E_STATE when unset.  The handle remembers that the batch came from the start state until the next hpf_set_state: hpf_solve then sets
+ *   hpf_stat.flags bit 8.
+ * hpf_solve_queue with a start state set: every scenario begins at it and the pf phase is skipped (no pf waves, no seed arrays; thresh_f and
+ *   max_iter_f are ignored); radial BLOCK_TREE handles move a new scenario into its storage with the start state instead of the pf seed
+ *   (k_queue_init_start), the other handles run hpf_start_apply + hpf_solve per wave.  Every record carries flags bit 8, and a scenario's record and
+ *   voltages are bit-identical to hpf_start_apply(1) + hpf_set_loads + hpf_solve alone, whatever the slot count, "queue_chunk" or "scenario_groups".
+ *   Flags bits 2, 3 and 6 keep their meaning: hpf_solve repeats a flagged batch from the state the call was entered with, i.e. the start state.
+ *   A started scenario that does NOT converge (hit max_iter, non-finite) is reported with bit 8 and its usual bits; the caller solves it again from
+ *   the reference's start.  For the distortion accumulator and the branch statistics such a scenario (bit 8 set, bit 0 clear) counts as DEFERRED, not
+ *   skipped, so that this re-solve adds it exactly once. */
+int  hpf_start_set(hpf_handle* h, const double* Vm0, const double* Va0);
+int  hpf_start_capture(hpf_handle* h, int scen);
+int  hpf_start_get(hpf_handle* h, double* Vm0, double* Va0);
+int  hpf_start_clear(hpf_handle* h);
+int  hpf_start_apply(hpf_handle* h, int n_scen);
 
 /* Diagnostics: with env HPF_DEBUG_ABLATE & 16 the BLOCK_TREE factor kernel records shader-cycle stamps per (scenario, bus):
  * out[(s*n + k)*8 + 0..5] = assembly, packed sub-phases, packed Gauss-Jordan split, MFMA Gauss-Jordan, packed wave-0 roles,

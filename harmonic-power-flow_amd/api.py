@@ -239,8 +239,13 @@ def _postprocess(Vm, Va):
 
 
 def hpf(buses, lines, coupled, thresh_h=1e-4, max_iter_h=50, plt_convergence=False, settings=None, ne_dir=None,
-        solver="auto", verbose=True, return_jacobian=True, details=None, extra_iters=0, check_steps=False):
+        solver="auto", verbose=True, return_jacobian=True, details=None, extra_iters=0, check_steps=False, update="polar"):
     """HG:511-560 -> (V, err_h, n_iter_h, J).
+
+    `update` (not in the reference, default "polar" = the reference's update): "rectangular" applies every harmonic Newton step to
+    U = Vm e^(j Va) instead of adding it to (Va, Vm) (option "rectangular_update", include/hpf.h): 3 - 4 iterations from the
+    reference's start where the reference takes 20 - 30, the same fixed point, other iterates -- n_iter_h, err_h and the last digits of V differ
+    from the reference's.  The handle's option is put back on return.  ValueError for any other string.
 
     `check_steps` (not in the reference, default False): every harmonic Newton step's normwise backward error is evaluated on the device
     (option "step_residual_check"); a step above the limit repeats the solve with partial pivoting (radial block tree) or retries it on
@@ -253,6 +258,8 @@ def hpf(buses, lines, coupled, thresh_h=1e-4, max_iter_h=50, plt_convergence=Fal
     The reference stops at err_h <= 1e-4, up to 4e-7 p.u. away from the fixed point, and where exactly below the
     threshold the last iterate lands depends on the rounding of the linear solver; one or two more iterations put the result on
     the fixed point itself, which does not (n_iter_h and err_h still report the reference's stop)."""
+    if not (isinstance(update, str) and update in DeviceModel.UPDATES):
+        raise ValueError("hpf: update=%r ('polar' or 'rectangular')" % (update,))
     st = settings or globals()["settings"]
     harmonics = st.HARMONICS
     n = len(buses)
@@ -274,7 +281,8 @@ def hpf(buses, lines, coupled, thresh_h=1e-4, max_iter_h=50, plt_convergence=Fal
         want_J = bool(return_jacobian)
         dm.set_option("keep_previous_state", 1 if want_J else 0)      # (explicit both ways: the handle may be a borrowed one)
         dm.set_option("step_residual_check", 1 if check_steps else 0)  # (likewise)
-        n_iter, err, hist = dm.solve(thresh_h, max_iter_h)                        # HG:530-542
+        with dm.update_mode(update):
+            n_iter, err, hist = dm.solve(thresh_h, max_iter_h)                    # HG:530-542
         stats = dm.stats()
         step_eta_max = float(dm.step_residuals()[1][0]) if check_steps else None
         # a meshed network on the block-tree path has no pivoted repeat of its own (hpf.h): with solver="auto" a scenario the static-pivot monitor
@@ -291,8 +299,9 @@ def hpf(buses, lines, coupled, thresh_h=1e-4, max_iter_h=50, plt_convergence=Fal
             print("Warning! Static-pivot block elimination was flagged; the solve was repeated with partial pivoting.")
         if extra_iters > 0 and np.isfinite(err[0]):
             dm.mismatch(want_f=False)
-            dm.iterate(int(extra_iters))
-            dm.sync()
+            with dm.update_mode(update):
+                dm.iterate(int(extra_iters))
+                dm.sync()
         Vm_raw, Va_raw = dm.get_state()
         n_iter_h = int(n_iter[0])
         J = None
@@ -312,7 +321,7 @@ def hpf(buses, lines, coupled, thresh_h=1e-4, max_iter_h=50, plt_convergence=Fal
             print("Warning! The bordered block-tree step was flagged (static pivot order / non-finite mismatch); solving again with the dense LU.")
         return hpf(buses, lines, coupled, thresh_h=thresh_h, max_iter_h=max_iter_h, plt_convergence=plt_convergence, settings=settings, ne_dir=ne_dir,
                    solver="dense", verbose=verbose, return_jacobian=return_jacobian, details=details, extra_iters=extra_iters,
-                   check_steps=check_steps)
+                   check_steps=check_steps, update=update)
     Vm, Va = _postprocess(Vm_raw[0], Va_raw[0])                                   # HG:545-549
     V = _frame(Vm, Va, harmonics, n)
     err_h = float(err[0])
@@ -535,14 +544,15 @@ def line_summary(V, lines, buses, settings=None):
 
 
 def solve(filename_buses, filename_lines, coupled=True, settings=None, ne_dir=None, solver="auto", verbose=False, extra_iters=0,
-          check_steps=False, line_flows=False):
-    """Convenience wrapper (= init_network + hpf + get_THD) -> dict(V, err_h, n_iter_h, THD, details).  check_steps: see hpf.
+          check_steps=False, line_flows=False, update="polar"):
+    """Convenience wrapper (= init_network + hpf + get_THD) -> dict(V, err_h, n_iter_h, THD, details).  check_steps, update: see hpf.
     line_flows=True adds the keys "line_flows" and "line_summary" (the two functions of that name on the result)."""
     st = settings or globals()["settings"]
     buses, lines, m, n, c = init_network(filename_buses, filename_lines, settings=st)
     details = {}
     V, err_h, n_iter_h, J = hpf(buses, lines, coupled, st.thresh_h, st.max_iter_h, settings=st, ne_dir=ne_dir,
-                                solver=solver, verbose=verbose, details=details, extra_iters=extra_iters, check_steps=check_steps)
+                                solver=solver, verbose=verbose, details=details, extra_iters=extra_iters, check_steps=check_steps,
+                                update=update)
     # converged = the stop rule err_h <= thresh_h was met (flags bit 0) -- not "the loop ended": a NaN mismatch ends it too
     out = {"V": V, "err_h": err_h, "n_iter_h": n_iter_h, "THD": get_THD(V), "details": details,
            "converged": bool(details["stats"]["flags"][0] & 1)}

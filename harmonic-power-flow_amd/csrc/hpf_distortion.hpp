@@ -29,8 +29,10 @@ HPF_DIST_HD int dist_classify(int flags, double thd_max, bool queue) {
 // ... and with a start state (hpf_start_*): a scenario that was started from the handle's start state (flags bit 8) and did not converge is
 // solved again by the caller from the reference's start, which adds it -> deferred, not skipped (whoever looks: the queue or an explicit add);
 // every other record is classified as above.
+// The same holds for a scenario whose harmonic steps were applied in rectangular form (option "rectangular_update", flags bit 9) and that did
+// not converge: the caller solves it again with the reference's update.
 HPF_DIST_HD int dist_classify_start(int flags, double thd_max, bool queue) {
-    if ((flags & 256) && !(flags & 1)) return DIST_DEFER;
+    if ((flags & (256 | 512)) && !(flags & 1)) return DIST_DEFER;
     return dist_classify(flags, thd_max, queue);
 }
 

@@ -239,6 +239,7 @@ struct hpf_handle {
                                       //     bit2: exactly zero pivot met by the pivoted wave Gauss-Jordan (k_factor_w)
                                       //     bit3: a Newton step missed the residual check (k_step_eta) in the current pass, bit4: ... in the first pass of a repeated scenario
     int resid_check = 0;              // option "step_residual_check": k_step_residual + k_step_eta between the linear solve and the update
+    int rect_update = 0;              // option "rectangular_update": launch_update<false> applies the harmonic steps through U (k_update_rect); hpf_stat.flags bit 9
     double resid_limit = 1e-10;       // option "step_residual_limit_log10": eta above it (or not finite) flags the scenario
     unsigned long long* d_respart = nullptr;   // [S][4][errpart_stride] partial maxima of |r|, row sums of |J|, |dx|, |f| (one per wavefront of k_step_residual)
     double* d_eta = nullptr;          // [2][S_alloc] eta of the last step | largest eta of the solve (-1: no step yet)

@@ -23,6 +23,7 @@
 #include "hpf_branch.hpp"
 #include "hpf_distortion.hpp"
 #include "hpf_internal.hpp"
+#include "hpf_update.hpp"
 
 using namespace hpf;
 
@@ -508,6 +509,42 @@ __global__ void k_update(int n, int Hn, int c, int count, int stride, int N, int
     E[o] = e;
 }
 
+// k_update<false> with the step applied in rectangular form (option "rectangular_update", hpf_update.hpp): same grid, same thread <-> entry map,
+// same two step sources and slot list; it additionally reads the U, E of the entry (what polar<false> left there for the state it reads) before
+// it overwrites them.  Entries whose magnitude is not a state variable (k < c) take the reference's update, bit for bit.
+__global__ void k_update_rect(int n, int Hn, int c, int count, int stride, int N, int Nc, const int* __restrict__ active,
+                              const double* __restrict__ step, double* __restrict__ Vm, double* __restrict__ Va,
+                              cplx* __restrict__ U, cplx* __restrict__ E,
+                              const double* __restrict__ xbus, int Bst, int s0, unsigned hn_magic) {
+    const int s = active ? active[blockIdx.y + s0] : (int)blockIdx.y + s0;
+    if (s < 0) return;
+    const int t = blockIdx.x * TPB + threadIdx.x;
+    if (t >= count) return;
+    const int i = div_by(t, hn_magic), q = t - i * Hn;
+    const int k = q * n + i;
+    const size_t o = (size_t)s * stride + (size_t)i * Hn + q;
+    double va = Va[o], vm = Vm[o], dth = 0.0, dv = 0.0;
+    if (xbus) {
+        const double2 dx = *reinterpret_cast<const double2*>(xbus + ((size_t)s * n + i) * Bst + 2 * q);
+        dth = dx.x;
+        dv = dx.y;
+    } else {
+        const double* d = step + (size_t)s * N;
+        if (k >= 1) dth = d[k - 1];
+        if (k >= c) dv = d[Nc + k - c];
+    }
+    update_rect(vm, va, U[o], E[o], k, c, dth, dv);
+    Va[o] = va;
+    Vm[o] = vm;
+    cplx u, e;
+    if (k >= c)
+        update_rect_polar(vm, va, u, e);
+    else
+        polar<false>(vm, va, u, e);
+    U[o] = u;
+    E[o] = e;
+}
+
 // Per-scenario bookkeeping of the NR loop (HG:536-542 / HG:259-265).  The set of running scenarios is a SLOT LIST: active[i] =
 // scenario id that slot i runs, or -1 (frozen scenario / empty slot); every kernel of the loop maps its blockIdx.y through it.
 // first: slot i <- scenario i, record the initial mismatch, apply the stop rule (mask: a repeat pass starts masked scenarios only).
@@ -741,7 +778,8 @@ __global__ void k_start_apply(int count, const double* __restrict__ sVm, const d
 }
 
 // get_THD (HG:563-572) THD_F per bus, max over buses, plus the result flags; one block per scenario.  start_bit: 256 when the batch was started
-// from the handle's start state (hpf_start_apply; k_queue_harvest: the queue ran with a start state set), else 0.
+// from the handle's start state (hpf_start_apply; k_queue_harvest: the queue ran with a start state set), else 0.  It also carries 512 when
+// the harmonic steps of the solve are applied in rectangular form (option "rectangular_update": flags bit 9).
 __global__ void k_stats(int n, int Hn, double thresh, int max_iter, const double* __restrict__ Vm,
                         const double* __restrict__ err, const int* __restrict__ niter, const int* __restrict__ pivflag,
                         int start_bit, hpf_stat* __restrict__ out) {
@@ -1367,9 +1405,14 @@ int launch_update(hpf_handle* h, const int* active) {
     const int Nc = FUND ? h->n - 1 : h->Nc;
     const bool busx = !FUND && bus_images(h);
     const int bw = tree_bst(h);
-    hipLaunchKernelGGL((k_update<FUND>), grid2(count, h->cur_S), dim3(TPB), 0, h->cur_stream, h->n, h->Hn, h->c, count,
-                       h->n * h->Hn, N, Nc, active, h->d_f, h->d_Vm, h->d_Va, h->d_U, h->d_E,
-                       busx ? h->d_x : nullptr, bw, h->cur_s0, div_magic(h->Hn));
+    if (!FUND && h->rect_update)
+        hipLaunchKernelGGL(k_update_rect, grid2(count, h->cur_S), dim3(TPB), 0, h->cur_stream, h->n, h->Hn, h->c, count,
+                           h->n * h->Hn, N, Nc, active, h->d_f, h->d_Vm, h->d_Va, h->d_U, h->d_E,
+                           busx ? h->d_x : nullptr, bw, h->cur_s0, div_magic(h->Hn));
+    else
+        hipLaunchKernelGGL((k_update<FUND>), grid2(count, h->cur_S), dim3(TPB), 0, h->cur_stream, h->n, h->Hn, h->c, count,
+                           h->n * h->Hn, N, Nc, active, h->d_f, h->d_Vm, h->d_Va, h->d_U, h->d_E,
+                           busx ? h->d_x : nullptr, bw, h->cur_s0, div_magic(h->Hn));
     return launch_status(h);
 }
 
@@ -1746,7 +1789,7 @@ int nr_loop(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* err
     }
     if (!FUND) {
         hipLaunchKernelGGL(k_stats, dim3(S), dim3(TPB), 0, h->stream, h->n, h->Hn, thresh, max_iter, h->d_Vm, h->d_err,
-                           h->d_niter, h->d_pivflag, h->from_start ? 256 : 0, h->d_stats);
+                           h->d_niter, h->d_pivflag, (h->from_start ? 256 : 0) | (h->rect_update ? 512 : 0), h->d_stats);
         std::vector<int> pf(S);
         HIPCHK(hipMemcpyAsync(pf.data(), h->d_pivflag, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -1834,7 +1877,7 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
         hipLaunchKernelGGL(k_queue_refill, dim3(1), dim3(1024), q_lds, h->stream, S_max, n_total, h->d_active, h->d_nactive, slot_scen, next,
                            hlist, hg, newlist, base);
         hipLaunchKernelGGL(k_queue_harvest, dim3((unsigned)S_max), dim3(TPB), 0, h->stream, n, Hn, thresh, max_iter, hlist, hg, h->d_Vm,
-                           h->d_Va, h->d_err, h->d_niter, h->d_pivflag, warm ? 256 : 0, qst, qVm, qVa);
+                           h->d_Va, h->d_err, h->d_niter, h->d_pivflag, (warm ? 256 : 0) | (h->rect_update ? 512 : 0), qst, qVm, qVa);
         if (h->dist_open && distortion_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;   // (before the storages are refilled)
         if (h->bstat_open && branch_add_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;
         if (warm)
@@ -1931,7 +1974,7 @@ void free_all(hpf_handle* h) {
 // ------------------------------------------------------------------------------------------------------------
 extern "C" {
 
-int hpf_version(void) { return 100; }
+int hpf_version(void) { return 101; }
 
 const char* hpf_strerror(int code) {
     switch (code) {
@@ -2762,6 +2805,11 @@ int hpf_set_option(hpf_handle* h, const char* name, int value) {
             if ((rr = reset_step_eta(h))) return rr;
         }
         h->resid_check = value;
+        return HPF_OK;
+    }
+    if (!strcmp(name, "rectangular_update")) {      // 1: the harmonic Newton steps are applied to U = Vm e^(j Va) (k_update_rect), flags bit 9
+        if (value != 0 && value != 1) return HPF_E_ARG;
+        h->rect_update = value;
         return HPF_OK;
     }
     if (!strcmp(name, "step_residual_limit_log10")) {   // a step is flagged when its eta exceeds 10^value (-16..0, default -10)

@@ -392,6 +392,26 @@ class DeviceModel:
 
     def set_option(self, name, value):
         self._chk(self.lib.hpf_set_option(self._h, name.encode(), int(value)), "hpf_set_option")
+        self.__dict__.setdefault("_options", {})[name] = int(value)
+
+    UPDATES = ("polar", "rectangular")
+
+    def update_mode(self, update):
+        """Context manager: the handle's option "rectangular_update" set from update = "polar" | "rectangular" (ValueError for anything else)
+        for the block, and put back to what it was on exit -- a cached handle never carries the mode into a later call."""
+        import contextlib
+        if not (isinstance(update, str) and update in self.UPDATES):
+            raise ValueError("update=%r ('polar' or 'rectangular')" % (update,))
+
+        @contextlib.contextmanager
+        def scope():
+            before = self.__dict__.get("_options", {}).get("rectangular_update", 0)
+            self.set_option("rectangular_update", int(update == "rectangular"))
+            try:
+                yield self
+            finally:
+                self.set_option("rectangular_update", before)
+        return scope()
 
     def set_stream(self, stream_ptr):
         self._chk(self.lib.hpf_set_stream(self._h, C.c_void_p(int(stream_ptr)) if stream_ptr else None),

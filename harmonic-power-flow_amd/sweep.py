@@ -244,7 +244,7 @@ def gather_branch_stats(stats, world, ids=None):
 
 
 def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_iter_h=50, want_voltages=False, refill=True, distortion=None,
-                    branches=None, start=None):
+                    branches=None, start=None, update="polar"):
     """Monte-Carlo / what-if sweep on ONE GPU: every row of P, Q [n_scen][n] (p.u. loads, HG:197,372) is one scenario of the
     network `dm` (a DeviceModel) holds -- the reference's counterpart is one hpf() call per load case (HG:511).  Per scenario:
     reference start (HG:174-184), fundamental pf (HG:244), harmonic NR with the reference's stop rule (HG:536).
@@ -278,7 +278,23 @@ def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_i
     scenario that does not converge (bit 8 without bit 0) is solved again cold, exactly as with start=None (its final record has no bit 8); the
     flagged ones (bits 2, 3, 6) are repeated from the start state through apply_start + solve first and go the cold way if that leaves them
     not converged.  The accumulators count a scenario that is solved again as deferred and add it once, from the solve whose record is returned.
-    The start state is taken off the handle for the cold re-solves and put back after them, and cleared when the call returns."""
+    The start state is taken off the handle for the cold re-solves and put back after them, and cleared when the call returns.
+    update: "polar" (default): the reference's state update, today's behaviour bit for bit.  "rectangular": every harmonic Newton step is applied
+    to U = Vm e^(j Va) instead of being added to (Va, Vm) (option "rectangular_update", include/hpf.h) -- 3 - 4 iterations from
+    the reference's start instead of 20 - 30, the same fixed point; the base case of a warm start is solved in the same mode.  Records carry flags
+    bit 9.  A scenario that does not converge this way (bit 9 without bit 0, after the re-solves above) is solved again with the reference's
+    update, cold: its final record carries neither bit 9 nor bit 8 and is what update="polar" returns for it; the accumulators count it as deferred
+    and add it once.  The handle's option is put back to what it was when the call returns.  ValueError for any other string."""
+    from .device import DeviceModel
+    if not (isinstance(update, str) and update in DeviceModel.UPDATES):
+        raise ValueError("solve_scenarios: update=%r ('polar' or 'rectangular')" % (update,))
+    with dm.update_mode(update):
+        return _solve_scenarios_started(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion, branches, start,
+                                        update == "rectangular")
+
+
+def _solve_scenarios_started(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion, branches, start, rect):
+    """solve_scenarios inside the scope of its update mode: start state, accumulators, the sweep"""
     if start is None:
         if dm.has_start():
             raise ValueError("solve_scenarios(start=None) on a handle that holds a start state: clear_start() first, or pass start=dm.get_start()")
@@ -286,7 +302,8 @@ def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_i
         _set_start(dm, P, Q, start, thresh_f, max_iter_f, thresh_h, max_iter_h)
     try:
         if distortion is None and branches is None:
-            return _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, False, False, start is not None)
+            return _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, False, False, start is not None,
+                                    rect)
         if distortion is not None:
             dm.distortion_begin(distortion.get("limit"), distortion.get("thd_limit", np.inf), distortion.get("hist_max", 1.0),
                                 distortion.get("bins", 64))
@@ -294,7 +311,7 @@ def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_i
             if branches is not None:
                 dm.branch_stats_begin(branches.get("rating"))
             res = _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion is not None,
-                                   branches is not None, start is not None)
+                                   branches is not None, start is not None, rect)
             extra = (() if distortion is None else (dm.distortion_get(),)) + (() if branches is None else (dm.branch_stats_get(),))
         finally:
             dm.set_option("distortion_id_base", 0)
@@ -329,7 +346,7 @@ def _set_start(dm, P, Q, start, thresh_f, max_iter_f, thresh_h, max_iter_h):
     dm.capture_start(0)
 
 
-def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion, branches, warm=False):
+def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion, branches, warm=False, rect=False):
     P = np.ascontiguousarray(np.atleast_2d(P), dtype=np.float64)
     Q = np.ascontiguousarray(np.atleast_2d(Q), dtype=np.float64)
     n_scen = P.shape[0]
@@ -376,11 +393,30 @@ def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_
         finally:
             dm.set_start(*kept)
 
+    def polar_resolves():
+        # applied in rectangular form (bit 9) and not converged, after everything above: each alone with the reference's update from the
+        # reference's start, as update="polar" without a start solves it
+        todo = np.nonzero(((out["flags"] & 512) != 0) & ((out["flags"] & 1) == 0))[0].tolist()
+        if not (rect and todo):
+            return
+        kept = dm.get_start() if warm else None
+        dm.set_option("rectangular_update", 0)
+        try:
+            if warm:
+                dm.clear_start()
+            for s in todo:
+                wave(s, s + 1)
+        finally:
+            dm.set_option("rectangular_update", 1)
+            if warm:
+                dm.set_start(*kept)
+
     if not refill:
         for a in range(0, n_scen, dm.S_max):
             wave(a, min(a + dm.S_max, n_scen), from_start=warm)
         if warm:
             cold_resolves()
+        polar_resolves()
         return (out, Vm, Va) if want_voltages else out
     # the device keeps the voltages of a whole call: bound a call by ~8 GB of result buffers when they are asked for
     per_call = n_scen if not want_voltages else max(dm.S_max, int(8e9 // (16 * dm.n * dm.Hn)))
@@ -406,6 +442,7 @@ def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_
             failed.append(int(s))
     if warm:
         cold_resolves(failed)
+    polar_resolves()
     return (out, Vm, Va) if want_voltages else out
 
 

@@ -85,7 +85,8 @@ typedef struct hpf_stat {
                                   bit5 the pivoted elimination met an exactly zero pivot (hpf_solve returns HPF_E_SINGULAR),
                                   bit6 option "step_residual_check": a Newton step of the first pass missed the residual limit,
                                   bit7 ... a step of the pass whose result is returned did (= bit6 unless bit4 is set),
-                                  bit8 the scenario was started from the handle's start state (hpf_start_*), not from the reference's start + pf */
+                                  bit8 the scenario was started from the handle's start state (hpf_start_*), not from the reference's start + pf,
+                                  bit9 the scenario's harmonic steps were applied in rectangular form (option "rectangular_update") */
     double  err;               /* final ||f||_inf                                        HG:389 */
     double  thd_max;           /* max over buses of THD_F                                HG:566-568 */
 } hpf_stat;
@@ -356,6 +357,21 @@ int  hpf_debug_stamps(hpf_handle* h, long long* out, int count);
  * healthy steps of every path sit below 1e-12, the evaluation's own rounding below 2e-14) or a non-finite eta sets hpf_stat.flags bit 6; hpf_solve
  * treats the scenario like one flagged by the static-pivot monitor (repeat with partial pivoting where that exists, "auto_repivot"; the check runs
  * in the repeat too and bit 7 is the verdict on the pass whose result is returned).  Off: no launch is added, results are bit-identical.
+ * "rectangular_update" (0 / 1, default 0; any other value: HPF_E_ARG): how a harmonic Newton step dx = (dtheta, dV) of J dx = f moves the state.  0: the
+ * reference's update, added to (Va, Vm) (HG:478,484-485).  1: in rectangular coordinates, where the step is exact for every row that is linear in
+ * U = Vm e^(j Va) (all current-balance rows): for entry (bus i, harmonic position q), k = q n + i, with vm, va its state and u, e the U, E the handle
+ * holds for it (E = U / Vm),
+ *   k <  c (slack, PV fundamentals: the magnitude is no state variable): the reference's update, unchanged;
+ *   k >= c: b = vm dtheta,  dU = (e.re dV - e.im b, e.re b + e.im dV),  U' = u - dU,  vm' = sqrt(U'.re^2 + U'.im^2),  va' = atan2(U'.im, U'.re)
+ * (csrc/hpf_update.hpp; every product and sum rounded on its own; vm may be negative, vm' never is; U' = 0: vm' = 0, va' = 0).  The stored U, E are
+ * then formed from (vm', va') like after every update and hpf_set_state, NOT taken from U' (at vm' = 0: U = 0, E = 1).  From the reference's start
+ * the harmonic NR then needs 3 - 4 iterations where the reference's update needs 20 - 30; the fixed point is the same, the iterates
+ * and the last digits of the result are not.  One site serves hpf_solve (its pivoted repeat and the trace included), hpf_solve_queue (chunks and
+ * waves) and hpf_iterate, every solver; the fundamental pf (hpf_fund_pf) keeps the reference's update.  May be changed between calls: takes effect
+ * at the next hpf_solve / hpf_solve_queue / hpf_iterate.  Records of scenarios solved with it carry hpf_stat.flags bit 9.  A scenario with bit 9
+ * that does NOT converge (bit 0 clear) is solved again by the caller with the option off; for the distortion accumulator and the branch statistics
+ * it counts as DEFERRED, not skipped (like bit 8), so that this re-solve adds it exactly once.  Off: no launch is added or changed, every output of
+ * every entry point is bit-identical.
  * "distortion_id_base" (>= 0, default 0): with the distortion accumulator or the branch statistics open (it serves both), hpf_solve_queue adds
  * scenario g of a call under id value + g.
  * "scenario_groups" (1..8, default 4; at least 32 running scenarios per group): independent scenario pipelines on separate HIP streams -- group 0

@@ -8,6 +8,8 @@ LIB_PATH = os.environ.get("HPF_LIB_PATH") or os.path.join(_HERE, "libhpf.so")   
 
 SOLVER_DENSE = 0
 SOLVER_BLOCK_TREE = 1
+SRC_CURRENTS = 0
+SRC_SCALE_SHIFT = 1
 
 c_int_p = C.POINTER(C.c_int32)
 c_dbl_p = C.POINTER(C.c_double)
@@ -75,6 +77,10 @@ SYMBOLS = {
     "hpf_start_get": (C.c_int, [_H, c_dbl_p, c_dbl_p]),
     "hpf_start_clear": (C.c_int, [_H]),
     "hpf_start_apply": (C.c_int, [_H, C.c_int]),
+    "hpf_set_sources": (C.c_int, [_H, C.c_int, C.c_int, c_dbl_p, c_int_p]),
+    "hpf_get_sources": (C.c_int, [_H, c_dbl_p]),
+    "hpf_clear_sources": (C.c_int, [_H]),
+    "hpf_queue_sources": (C.c_int, [_H, C.c_int, C.c_int, c_dbl_p, c_int_p]),
     "hpf_debug_stamps": (C.c_int, [_H, C.POINTER(C.c_longlong), C.c_int]),
     "hpf_set_option": (C.c_int, [_H, C.c_char_p, C.c_int]),
     "hpf_set_stream": (C.c_int, [_H, C.c_void_p]),

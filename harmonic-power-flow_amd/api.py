@@ -239,8 +239,13 @@ def _postprocess(Vm, Va):
 
 
 def hpf(buses, lines, coupled, thresh_h=1e-4, max_iter_h=50, plt_convergence=False, settings=None, ne_dir=None,
-        solver="auto", verbose=True, return_jacobian=True, details=None, extra_iters=0, check_steps=False, update="polar"):
+        solver="auto", verbose=True, return_jacobian=True, details=None, extra_iters=0, check_steps=False, update="polar", sources=None):
     """HG:511-560 -> (V, err_h, n_iter_h, J).
+
+    `sources` (not in the reference, default None = the Norton source currents I_N of the device files): source currents of the nonlinear buses for
+    this one scenario (include/hpf.h "Source currents") -- {"scale": [n-m], "shift": [n-m]} (either may be missing: 1 / 0): scale
+    units of each bus's device, their waveform shifted in time by shift rad at the fundamental; or {"currents": [n-m][Hn]} complex, p.u., used as
+    given.  Y_N stays the device's.  ValueError for wrong shapes, before any device call.
 
     `update` (not in the reference, default "polar" = the reference's update): "rectangular" applies every harmonic Newton step to
     U = Vm e^(j Va) instead of adding it to (Va, Vm) (option "rectangular_update", include/hpf.h): 3 - 4 iterations from the
@@ -263,10 +268,18 @@ def hpf(buses, lines, coupled, thresh_h=1e-4, max_iter_h=50, plt_convergence=Fal
     st = settings or globals()["settings"]
     harmonics = st.HARMONICS
     n = len(buses)
+    src = None
+    if sources is not None:
+        from .sweep import sources_argument
+        if not isinstance(sources, dict):
+            raise ValueError("hpf: sources=%r ({'currents': ..} or {'scale': .., 'shift': ..})" % (sources,))
+        src = sources_argument({k: np.asarray(v)[None] for k, v in sources.items()}, 1, n - ingest.network_constants(buses)[0], len(harmonics), "hpf")
     Y = build_admittance_matrices(buses, lines, harmonics)                       # HG:523
     NE = import_Norton_Equivalents(buses, coupled, st, ne_dir)                    # HG:528
     with _borrow_model(buses, Y, NE, coupled, harmonics, solver=solver) as dm:
         dm.set_loads(buses["P"].to_numpy(dtype=float), buses["Q"].to_numpy(dtype=float))
+        if src:
+            dm.set_sources(src[1], src[0])
         dm.set_state(None, None, n_scen=1)
         nf, ef, hf = dm.fund_pf(st.thresh_f, st.max_iter_f)                       # HG:525 (pf with its defaults)
         seed = dm.get_state()
@@ -321,7 +334,7 @@ def hpf(buses, lines, coupled, thresh_h=1e-4, max_iter_h=50, plt_convergence=Fal
             print("Warning! The bordered block-tree step was flagged (static pivot order / non-finite mismatch); solving again with the dense LU.")
         return hpf(buses, lines, coupled, thresh_h=thresh_h, max_iter_h=max_iter_h, plt_convergence=plt_convergence, settings=settings, ne_dir=ne_dir,
                    solver="dense", verbose=verbose, return_jacobian=return_jacobian, details=details, extra_iters=extra_iters,
-                   check_steps=check_steps, update=update)
+                   check_steps=check_steps, update=update, sources=sources)
     Vm, Va = _postprocess(Vm_raw[0], Va_raw[0])                                   # HG:545-549
     V = _frame(Vm, Va, harmonics, n)
     err_h = float(err[0])
@@ -544,15 +557,15 @@ def line_summary(V, lines, buses, settings=None):
 
 
 def solve(filename_buses, filename_lines, coupled=True, settings=None, ne_dir=None, solver="auto", verbose=False, extra_iters=0,
-          check_steps=False, line_flows=False, update="polar"):
-    """Convenience wrapper (= init_network + hpf + get_THD) -> dict(V, err_h, n_iter_h, THD, details).  check_steps, update: see hpf.
+          check_steps=False, line_flows=False, update="polar", sources=None):
+    """Convenience wrapper (= init_network + hpf + get_THD) -> dict(V, err_h, n_iter_h, THD, details).  check_steps, update, sources: see hpf.
     line_flows=True adds the keys "line_flows" and "line_summary" (the two functions of that name on the result)."""
     st = settings or globals()["settings"]
     buses, lines, m, n, c = init_network(filename_buses, filename_lines, settings=st)
     details = {}
     V, err_h, n_iter_h, J = hpf(buses, lines, coupled, st.thresh_h, st.max_iter_h, settings=st, ne_dir=ne_dir,
                                 solver=solver, verbose=verbose, details=details, extra_iters=extra_iters, check_steps=check_steps,
-                                update=update)
+                                update=update, sources=sources)
     # converged = the stop rule err_h <= thresh_h was met (flags bit 0) -- not "the loop ended": a NaN mismatch ends it too
     out = {"V": V, "err_h": err_h, "n_iter_h": n_iter_h, "THD": get_THD(V), "details": details,
            "converged": bool(details["stats"]["flags"][0] & 1)}

@@ -128,9 +128,10 @@ HPF_HD cplx row_current_fund(const Model& M, const cplx* U, int i) {
 // chains, the group contributes (rr - ii, ri + ir) and groups are added in order; the remaining Hn % 4 rows
 // are accumulated over all columns as t += fma(ar, xr, -(ai*xi)).  Uncoupled (HG:322: np.diag(Y_N).dot):
 // one product, every partial rounded.
-HPF_HD cplx norton_injection(const Model& M, const cplx* U, int q, int i) {
+// norton_injection_in: the same with the source current `in` of (bus, q) supplied by the caller (a kernel that fetched it early).
+// src (norton_injection, optional): the bus's Hn per-scenario source currents (hpf_set_sources), read instead of I_N; nullptr = the model's I_N.
+HPF_HD cplx norton_injection_in(const Model& M, const cplx* U, int q, int i, cplx in) {
     const int d = M.dev[i];
-    const cplx in = M.IN[(size_t)d * M.Hn + q];
     cplx acc = {0.0, 0.0};
     if (M.coupled) {
         // Y_N[q, p]: row q of the device's matrix, or column q of its transposed copy (same values, coalesced on the device)
@@ -166,12 +167,18 @@ HPF_HD cplx norton_injection(const Model& M, const cplx* U, int q, int i) {
     return csub(in, acc);
 }
 
+HPF_HD cplx norton_injection(const Model& M, const cplx* U, int q, int i, const cplx* src = nullptr) {
+    return norton_injection_in(M, U, q, i, src ? src[q] : M.IN[(size_t)M.dev[i] * M.Hn + q]);
+}
+
 // Complex mismatch of stacked index k >= 1 (HG:360-390): power balance for linear buses at the fundamental,
 // current balance otherwise.  FUND: fundamental power flow (HG:195-202), every bus is a power row.
 // Iout (optional): receives the network current I of a power row -- the Jacobian's diagonal power entries (HG:451-459) need
 // the same sum again, and the block-tree kernels read it back instead of re-walking the admittance row.
+// src (optional, harmonic NR only): the Hn source currents of nonlinear bus i in this scenario (norton_injection).
 template <bool FUND>
-HPF_HD cplx mismatch_row_qi(const Model& M, const cplx* U, const double* P, const double* Q, int q, int i, cplx* Iout = nullptr) {
+HPF_HD cplx mismatch_row_qi(const Model& M, const cplx* U, const double* P, const double* Q, int q, int i, cplx* Iout = nullptr,
+                            const cplx* src = nullptr) {
     const cplx I = FUND ? row_current_fund(M, U, i) : row_current(M, U, q, i);
     if (FUND || (q == 0 && i < M.m)) {
         if (Iout) Iout[i] = I;
@@ -179,7 +186,7 @@ HPF_HD cplx mismatch_row_qi(const Model& M, const cplx* U, const double* P, cons
         const cplx sl = cmul_npy(U[M.vi(0, i)], cconj(I));
         return {P[i] + sl.re, Q[i] + sl.im};
     }
-    if (i >= M.m) return cadd(I, norton_injection(M, U, q, i));   // HG:351,354
+    if (i >= M.m) return cadd(I, norton_injection(M, U, q, i, src));   // HG:351,354
     return I;
 }
 

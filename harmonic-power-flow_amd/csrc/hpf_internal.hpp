@@ -280,6 +280,12 @@ struct hpf_handle {
     bool from_start = false;          // the current batch came from hpf_start_apply (until the next hpf_set_state): hpf_stat.flags bit 8
     double *d_sVm = nullptr, *d_sVa = nullptr;
     hpf::cplx *d_sU = nullptr, *d_sE = nullptr;
+    // per-scenario Norton source currents (hpf_set_sources / hpf_queue_sources, hpf_sources.hpp; nothing allocated until the first of them)
+    bool src_set = false;             // the current batch has sources: the mismatch and the step-residual kernels launch their source variants, hpf_stat.flags bit 10
+    hpf::cplx* d_src = nullptr;       // [S_max][n - m][Hn] I_src, indexed by scenario id like d_P (virtual slots of a meshed handle never form a mismatch: none)
+    int qsrc_n = 0, qsrc_form = 0;    // registration of hpf_queue_sources: scenarios (0: none), input form
+    void* d_qsrc = nullptr;           // the whole sweep's data in HBM: form 0 [n_total][n - m][Hn] complex, form 1 [n_total][n - m][2] doubles
+    int* d_qorders = nullptr;         // [Hn] harmonic orders (form 1)
     int keep_prev = 0;
     bool prev_valid = false;          // d_Vmp / d_Vap belong to the last hpf_solve (set_state / set_loads invalidate them)
     double* d_hist = nullptr;         // [S][hist_cap]

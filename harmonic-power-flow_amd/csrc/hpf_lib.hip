@@ -23,6 +23,7 @@
 #include "hpf_branch.hpp"
 #include "hpf_distortion.hpp"
 #include "hpf_internal.hpp"
+#include "hpf_sources.hpp"
 #include "hpf_update.hpp"
 
 using namespace hpf;
@@ -114,9 +115,10 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
 // Norton injection of harmonic position q (HG:313-323: I_N[q] - sum_p Y_N[q,p] U_p) with both operands in LDS: the device type's
 // Y_N^T (ynl[p*Hn + q]) and the bus's Hn voltages (ul[p]).  Same operations in the same order as norton_injection (hpf_assembly.hpp):
 // the reference's zgemv_n rounding -- 4-column groups of FMA chains, groups added in order; the Hn % 4 tail rows fused per column.
-__device__ __forceinline__ cplx norton_injection_lds(const Model& M, int d, const cplx* __restrict__ ynl, const cplx* __restrict__ ul, int q) {
+// norton_injection_lds_in: with the source current `in` of (bus, q) supplied by the caller (the source variants of the kernels fetch it with
+// their first batch of loads); norton_injection_lds: src = the bus's Hn per-scenario source currents, nullptr = the model's I_N.
+__device__ __forceinline__ cplx norton_injection_lds_in(const Model& M, const cplx* __restrict__ ynl, const cplx* __restrict__ ul, int q, cplx in) {
     const int Hn = M.Hn;
-    const cplx in = M.IN[(size_t)d * Hn + q];
     cplx acc = {0.0, 0.0};
     const cplx* yq = ynl + q;
     if (q < (Hn & ~3)) {
@@ -161,6 +163,11 @@ __device__ __forceinline__ cplx norton_injection_lds(const Model& M, int d, cons
     return csub(in, acc);
 }
 
+__device__ __forceinline__ cplx norton_injection_lds(const Model& M, int d, const cplx* __restrict__ ynl, const cplx* __restrict__ ul, int q,
+                                                     const cplx* __restrict__ src = nullptr) {
+    return norton_injection_lds_in(M, ynl, ul, q, src ? src[q] : M.IN[(size_t)d * M.Hn + q]);
+}
+
 // harmonic_mismatch (HG:360-390).  One workgroup = one scenario x a tile of consecutive buses (thread t = i*Hn + q: bus-major, so a
 // workgroup's 256 rows are ~10 whole buses and their voltages one contiguous run).  Staged in LDS per workgroup (coupled Norton data):
 // the device type's Y_N^T (Hn x Hn complex: 10.8 KB at K = 25, shared by every bus of that type -- L2-resident) and the tile's bus
@@ -169,11 +176,15 @@ __device__ __forceinline__ cplx norton_injection_lds(const Model& M, int d, cons
 // the XCD-aware placement (xcd_map) keeps in ONE L2 per scenario.  ||f||_inf: wave shuffle + one partial maximum per wavefront.
 // f: the reference's stacked real layout (HG:388; dense solver, C ABI) or nullptr; fb: bus-major image [bus][2q + (Re|Im)] with
 // stride Bst and zeros where there is no equation (tree kernels) or nullptr.
-template <bool FUND>
+// SRC (harmonic variant only; launched when the batch has sources, hpf_set_sources): the Norton rows take I_src[s][i - m][q] (src: [S][n - m][Hn],
+// thread t = i*Hn + q -> a wavefront reads one contiguous run of 16-byte values) in place of I_N[dev(i)][q].  The value is fetched with batch A
+// below -- independent of every other load -- so the kernel's chain of dependent fetches is as long as without sources.
+template <bool FUND, bool SRC>
 __global__ __launch_bounds__(TPB, 8) void k_mismatch(Model M, int count, int N, int Nc, const int* __restrict__ active, const cplx* __restrict__ U,
                            const double* __restrict__ P, const double* __restrict__ Q, double* __restrict__ f,
                            unsigned long long* __restrict__ errpart, int pstride, cplx* __restrict__ I0, double* __restrict__ fb, int Bst,
-                           int s0, int S_cnt, unsigned hn_magic) {
+                           int s0, int S_cnt, unsigned hn_magic, const cplx* __restrict__ src) {
+    static_assert(!(FUND && SRC), "the fundamental pf never reads sources");
     extern __shared__ cplx mm_lds[];                    // [Hn*Hn] Y_N^T of the tile's first device type | [tile buses][Hn] voltages
     int bx, slot;
     if (!xcd_map(S_cnt, bx, slot)) return;
@@ -194,9 +205,11 @@ __global__ __launch_bounds__(TPB, 8) void k_mismatch(Model M, int count, int N, 
     int d0 = -1, i_first = 0;
     int e0 = 0, e1 = 0;
     cplx yv[PF], ug[PF];
+    cplx sv = {0.0, 0.0};
     if (!FUND) {
         const int4 rr = reinterpret_cast<const int4*>(M.rowrec)[2 * i];          // (rowptr[i], rowptr[i+1], col[e0], col[e0+1])
         const int rr2 = M.rowrec[8 * i + 4];                                      //  col[e0+2]
+        if (SRC) sv = src[((size_t)s * (M.n - M.m) + (i >= M.m ? i - M.m : 0)) * Hn + q];   // (linear buses: a valid address, value unused)
         e0 = rr.x;
         e1 = rr.y;
         const bool has_nl = M.coupled && M.YNt;
@@ -261,9 +274,10 @@ __global__ __launch_bounds__(TPB, 8) void k_mismatch(Model M, int count, int N, 
                     v = {P[(size_t)s * M.n + i] + sl.re, Q[(size_t)s * M.n + i] + sl.im};
                 } else if (d0 >= 0 && i >= M.m && M.dev[i] == d0) {
                     // current-balance row of a nonlinear bus (HG:351,354): network current + Norton injection out of LDS
-                    v = cadd(I, norton_injection_lds(M, d0, mm_lds, mm_lds + Hn * Hn + (i - i_first) * Hn, q));
+                    v = cadd(I, SRC ? norton_injection_lds_in(M, mm_lds, mm_lds + Hn * Hn + (i - i_first) * Hn, q, sv)
+                                    : norton_injection_lds(M, d0, mm_lds, mm_lds + Hn * Hn + (i - i_first) * Hn, q));
                 } else if (i >= M.m) {
-                    v = cadd(I, norton_injection(M, Us, q, i));
+                    v = cadd(I, SRC ? norton_injection_in(M, Us, q, i, sv) : norton_injection(M, Us, q, i));
                 } else {
                     v = I;
                 }
@@ -295,11 +309,12 @@ __global__ __launch_bounds__(TPB, 8) void k_mismatch(Model M, int count, int N, 
 // step overwrote d_f on the stacked paths, the tree sweeps own d_fb).  It never reads a debug switch: the step is judged against the true J.
 // Every wavefront leaves four partial maxima (|r|, row sums of |J|, |dx|, |f|) -> respart[s][4][pstride]; k_step_eta forms eta.
 // BUSX: the step is the bus-major image (stride Bst) of the multi-wave block-tree sweep, else the stacked vector.  stage: the launch has the LDS.
-template <bool BUSX>
+// SRC: the batch has sources (hpf_set_sources) -- f is formed with I_src[s][i - m][q], fetched before the staging loads, as k_mismatch<false, true> forms it.
+template <bool BUSX, bool SRC>
 __global__ __launch_bounds__(TPB) void k_step_residual(Model M, int count, int N, int Nc, const int* __restrict__ active, const cplx* __restrict__ U,
                            const cplx* __restrict__ E, const double* __restrict__ P, const double* __restrict__ Q,
                            const double* __restrict__ step, int Bst, unsigned long long* __restrict__ respart, int pstride,
-                           int s0, int S_cnt, unsigned hn_magic, int stage_ok) {
+                           int s0, int S_cnt, unsigned hn_magic, int stage_ok, const cplx* __restrict__ src) {
     extern __shared__ cplx rs_lds[];                    // [Hn*Hn] Y_N^T of the tile's first device type | [tile buses][Hn] U | E | step
     int bx, slot;
     if (!xcd_map(S_cnt, bx, slot)) return;
@@ -315,6 +330,8 @@ __global__ __launch_bounds__(TPB) void k_step_residual(Model M, int count, int N
     const StepStacked dxs{ds, Nc, M.c};
     const bool live = t < count;
     const int i = live ? div_by(t, hn_magic) : M.n - 1, q = live ? t - i * Hn : 0;
+    cplx sv = {0.0, 0.0};
+    if (SRC) sv = src[((size_t)s * (M.n - M.m) + (i >= M.m ? i - M.m : 0)) * Hn + q];
     const int i_first = div_by(bx * TPB, hn_magic);
     int i_last = div_by(bx * TPB + TPB - 1, hn_magic);
     if (i_last > M.n - 1) i_last = M.n - 1;
@@ -341,8 +358,10 @@ __global__ __launch_bounds__(TPB) void k_step_residual(Model M, int count, int N
     if (live && k >= 1) {
         const bool mine = d0 >= 0 && i >= M.m && M.dev[i] == d0;       // nonlinear bus of the staged device type
         const int loc = (i - i_first) * Hn;
-        const cplx f = mine ? cadd(row_current(M, Us, q, i), norton_injection_lds(M, d0, rs_lds, ul + loc, q))
-                            : mismatch_row_qi<false>(M, Us, P + (size_t)s * M.n, Q + (size_t)s * M.n, q, i);
+        const cplx f = mine ? cadd(row_current(M, Us, q, i), SRC ? norton_injection_lds_in(M, rs_lds, ul + loc, q, sv)
+                                                                 : norton_injection_lds(M, d0, rs_lds, ul + loc, q))
+                       : (SRC && i >= M.m) ? cadd(row_current(M, Us, q, i), norton_injection_in(M, Us, q, i, sv))
+                                           : mismatch_row_qi<false>(M, Us, P + (size_t)s * M.n, Q + (size_t)s * M.n, q, i);
         StepRow rw;
         if (stage && i >= M.m) {
             // A nonlinear row of a staged tile: the entries of jcsr_walk with the cross terms' operands out of LDS.  The admittance row comes
@@ -779,7 +798,8 @@ __global__ void k_start_apply(int count, const double* __restrict__ sVm, const d
 
 // get_THD (HG:563-572) THD_F per bus, max over buses, plus the result flags; one block per scenario.  start_bit: 256 when the batch was started
 // from the handle's start state (hpf_start_apply; k_queue_harvest: the queue ran with a start state set), else 0.  It also carries 512 when
-// the harmonic steps of the solve are applied in rectangular form (option "rectangular_update": flags bit 9).
+// the harmonic steps of the solve are applied in rectangular form (option "rectangular_update": flags bit 9), and 1024 when the batch was solved
+// with per-scenario source currents (hpf_set_sources: flags bit 10).
 __global__ void k_stats(int n, int Hn, double thresh, int max_iter, const double* __restrict__ Vm,
                         const double* __restrict__ err, const int* __restrict__ niter, const int* __restrict__ pivflag,
                         int start_bit, hpf_stat* __restrict__ out) {
@@ -1146,6 +1166,34 @@ __global__ void k_queue_init_start(int n, int Hn, const int* __restrict__ newlis
     }
 }
 
+// Source currents, input form 1 -> slot storage (hpf_sources.hpp): one thread per (scenario, nonlinear bus, harmonic position).  ab [.][nnl][2] =
+// (a, phi) per (scenario, nonlinear bus), orders [Hn], dst [S_max][nnl][Hn].  Without lists (newlist == nullptr): scenario blockIdx.y of the batch
+// reads row g0 + blockIdx.y of ab (hpf_set_sources: g0 = 0; the waves of hpf_solve_queue: their first scenario).  With lists: storage
+// s = newlist[blockIdx.y] takes scenario slot_scen[s] of the queue (the freed slots of hpf_solve_queue, next to k_queue_init).
+__global__ void k_source_expand(int nnl, int Hn, int m, const int* __restrict__ newlist, const int* __restrict__ slot_scen, int g0,
+                                const double* __restrict__ ab, const int* __restrict__ orders, const int* __restrict__ dev,
+                                const cplx* __restrict__ IN, cplx* __restrict__ dst) {
+    const int s = newlist ? newlist[blockIdx.y] : (int)blockIdx.y;
+    if (s < 0) return;
+    const int g = newlist ? slot_scen[s] : g0 + (int)blockIdx.y;
+    const int k = blockIdx.x * TPB + threadIdx.x;
+    if (k >= nnl * Hn) return;
+    const int ib = k / Hn, q = k - ib * Hn;
+    const double2 v = reinterpret_cast<const double2*>(ab)[(size_t)g * nnl + ib];
+    dst[(size_t)s * nnl * Hn + k] = source_expand(v.x, v.y, orders[q], IN[(size_t)dev[m + ib] * Hn + q]);
+}
+
+// ... and input form 0: the queue's array in HBM [n_total][nnl][Hn] -> the storages of the new list
+__global__ void k_source_gather(int count, const int* __restrict__ newlist, const int* __restrict__ slot_scen, const cplx* __restrict__ qsrc,
+                                cplx* __restrict__ dst) {
+    const int s = newlist[blockIdx.y];
+    if (s < 0) return;
+    const int g = slot_scen[s];
+    const int k = blockIdx.x * TPB + threadIdx.x;
+    if (k >= count) return;
+    dst[(size_t)s * count + k] = qsrc[(size_t)g * count + k];
+}
+
 // the initial mismatch of the new scenarios against the stop rule (HG:531,536): a scenario that meets it at once leaves the slot list
 __global__ __launch_bounds__(64) void k_queue_first(int S_max, double thresh, int max_iter, const int* __restrict__ newlist, const int* __restrict__ base,
                               const unsigned long long* __restrict__ errpart, int pstride, int np, double* __restrict__ err,
@@ -1330,14 +1378,17 @@ int launch_mismatch(hpf_handle* h, const int* active, bool stacked = true) {
         // LDS: Y_N^T of one device type + the voltages of the workgroup's tile of buses (harmonic mismatch with coupled Norton data)
         const size_t lds = (!FUND && h->coupled && h->n > h->m)
                                ? sizeof(cplx) * ((size_t)h->Hn * h->Hn + (size_t)(TPB / h->Hn + 2) * h->Hn) : 0;
+        // the batch has sources (hpf_set_sources): the source variant of the harmonic kernel; without them exactly the launch of a handle that never had any
+        auto kern = (!FUND && h->src_set) ? &k_mismatch<false, true> : &k_mismatch<FUND, false>;
         if (lds > 64 * 1024) {                      // Hn >= 62 (H_MAX >= 123): beyond the default dynamic-LDS limit of a kernel
             if (lds > 160 * 1024) return HPF_E_ARG;
             // (per launch: the attribute belongs to the device the handle runs on, and the call costs nothing next to the launch)
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mismatch<FUND>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         }
-        hipLaunchKernelGGL((k_mismatch<FUND>), xcd_grid(nbx, h->cur_S), dim3(TPB), lds, h->cur_stream, h->M, count, N, Nc,
+        hipLaunchKernelGGL(kern, xcd_grid(nbx, h->cur_S), dim3(TPB), lds, h->cur_stream, h->M, count, N, Nc,
                            active, h->d_U, h->d_P, h->d_Q, (stacked || !img) ? h->d_f : nullptr, h->d_errpart, h->errpart_stride, h->d_I0,
-                           img ? h->d_fb : nullptr, tree_bst(h), h->cur_s0, h->cur_S, div_magic(h->Hn));
+                           img ? h->d_fb : nullptr, tree_bst(h), h->cur_s0, h->cur_S, div_magic(h->Hn),
+                           (!FUND && h->src_set) ? h->d_src : (const cplx*)nullptr);
         if (launch_status(h)) return HPF_E_HIP;
     }
     return HPF_OK;
@@ -1441,12 +1492,13 @@ int launch_step_residual(hpf_handle* h, const int* active) {
     const bool busx = bus_images(h);
     const int nbx = (count + TPB - 1) / TPB;
     const size_t lds = step_residual_lds(h);
-    auto kern = busx ? &k_step_residual<true> : &k_step_residual<false>;
+    auto kern = h->src_set ? (busx ? &k_step_residual<true, true> : &k_step_residual<false, true>)
+                           : (busx ? &k_step_residual<true, false> : &k_step_residual<false, false>);
     if (lds > 64 * 1024)        // beyond the default dynamic-LDS limit of a kernel (as launch_mismatch)
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     hipLaunchKernelGGL(kern, xcd_grid(nbx, h->cur_S), dim3(TPB), lds, h->cur_stream, h->M, count, h->N, h->Nc, active, h->d_U, h->d_E,
                        h->d_P, h->d_Q, busx ? h->d_x : h->d_f, tree_bst(h), h->d_respart, h->errpart_stride, h->cur_s0, h->cur_S,
-                       div_magic(h->Hn), lds > 0 ? 1 : 0);
+                       div_magic(h->Hn), lds > 0 ? 1 : 0, h->src_set ? h->d_src : (const cplx*)nullptr);
     hipLaunchKernelGGL(k_step_eta, dim3((unsigned)h->cur_S), dim3(64), 0, h->cur_stream, h->cur_S, active, h->d_respart, h->errpart_stride,
                        err_parts<false>(h), h->resid_limit, h->d_eta, h->S_alloc, h->d_pivflag, h->cur_s0);
     return launch_status(h);
@@ -1665,6 +1717,76 @@ int start_alloc(hpf_handle* h) {
     return HPF_OK;
 }
 
+// ---- per-scenario source currents (hpf_sources.hpp) ------------------------------------------------------------------------------------------
+void queue_sources_drop(hpf_handle* h) {
+    if (h->d_qsrc) hipFree(h->d_qsrc);
+    if (h->d_qorders) hipFree(h->d_qorders);
+    h->d_qsrc = nullptr;
+    h->d_qorders = nullptr;
+    h->qsrc_n = 0;
+}
+
+void sources_free(hpf_handle* h) {
+    queue_sources_drop(h);
+    if (h->d_src) hipFree(h->d_src);
+    h->d_src = nullptr;
+    h->src_set = false;
+}
+
+// doubles of the caller's array per scenario
+inline size_t sources_row(const hpf_handle* h, int form) { return (size_t)(h->n - h->m) * (form == SRC_CURRENTS ? 2 * (size_t)h->Hn : 2); }
+
+// the argument rules of hpf_set_sources / hpf_queue_sources, on the host, before any HIP call
+int sources_check(const hpf_handle* h, int n_scen, int form, const double* data, const int32_t* orders) {
+    if (!h || !data || n_scen < 1) return HPF_E_ARG;
+    if (form != SRC_CURRENTS && form != SRC_SCALE_SHIFT) return HPF_E_ARG;
+    if (form == SRC_SCALE_SHIFT && !orders) return HPF_E_ARG;
+    const size_t cnt = (size_t)n_scen * sources_row(h, form);
+    for (size_t k = 0; k < cnt; ++k)
+        if (!isfinite(data[k])) return HPF_E_ARG;
+    return HPF_OK;
+}
+
+// the caller's array (and the orders of form 1) -> fresh device buffers, on the handle's stream
+int sources_upload(hpf_handle* h, int n_scen, int form, const double* data, const int32_t* orders, void** d_data, int** d_orders) {
+    double* dd = nullptr;
+    int* od = nullptr;
+    int r;
+    const size_t cnt = (size_t)n_scen * sources_row(h, form);
+    if ((r = dev_alloc(h, &dd, cnt))) return r;
+    if (form == SRC_SCALE_SHIFT && (r = dev_alloc(h, &od, (size_t)h->Hn))) {
+        hipFree(dd);
+        return r;
+    }
+    hipError_t e = hipMemcpyAsync(dd, data, sizeof(double) * cnt, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && od) e = hipMemcpyAsync(od, orders, sizeof(int) * (size_t)h->Hn, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);            // (the caller's arrays may go away after the call)
+    if (e != hipSuccess) {
+        hipFree(dd);
+        if (od) hipFree(od);
+        h->last_detail = (int)e;
+        return HPF_E_HIP;
+    }
+    *d_data = dd;
+    *d_orders = od;
+    return HPF_OK;
+}
+
+// scenarios 0 .. S - 1 of the batch <- rows g0 .. g0 + S - 1 of a device array in input form `form`, device to device on the handle's stream
+int sources_fill(hpf_handle* h, int S, int form, const void* d_data, const int* d_orders, int g0) {
+    const int nnl = h->n - h->m;
+    int r;
+    if (!h->d_src && (r = dev_alloc(h, &h->d_src, (size_t)h->S_max * nnl * h->Hn))) return r;
+    if (form == SRC_CURRENTS) {
+        const size_t row = (size_t)nnl * h->Hn;
+        HIPCHK(hipMemcpyAsync(h->d_src, (const cplx*)d_data + (size_t)g0 * row, sizeof(cplx) * row * (size_t)S, hipMemcpyDeviceToDevice, h->stream));
+        return HPF_OK;
+    }
+    hipLaunchKernelGGL(k_source_expand, grid2(nnl * h->Hn, S), dim3(TPB), 0, h->stream, nnl, h->Hn, h->m, (const int*)nullptr, (const int*)nullptr,
+                       g0, (const double*)d_data, d_orders, h->d_dev, h->d_IN, h->d_src);
+    return launch_status(h);
+}
+
 void branch_stats_free(hpf_handle* h) {
     void* ptrs[] = {h->d_bs_f, h->d_bs_arg, h->d_bs_over, h->d_bs_cnt, h->d_bs_rating};
     for (void* p : ptrs)
@@ -1789,7 +1911,7 @@ int nr_loop(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* err
     }
     if (!FUND) {
         hipLaunchKernelGGL(k_stats, dim3(S), dim3(TPB), 0, h->stream, h->n, h->Hn, thresh, max_iter, h->d_Vm, h->d_err,
-                           h->d_niter, h->d_pivflag, (h->from_start ? 256 : 0) | (h->rect_update ? 512 : 0), h->d_stats);
+                           h->d_niter, h->d_pivflag, (h->from_start ? 256 : 0) | (h->rect_update ? 512 : 0) | (h->src_set ? 1024 : 0), h->d_stats);
         std::vector<int> pf(S);
         HIPCHK(hipMemcpyAsync(pf.data(), h->d_pivflag, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -1877,7 +1999,7 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
         hipLaunchKernelGGL(k_queue_refill, dim3(1), dim3(1024), q_lds, h->stream, S_max, n_total, h->d_active, h->d_nactive, slot_scen, next,
                            hlist, hg, newlist, base);
         hipLaunchKernelGGL(k_queue_harvest, dim3((unsigned)S_max), dim3(TPB), 0, h->stream, n, Hn, thresh, max_iter, hlist, hg, h->d_Vm,
-                           h->d_Va, h->d_err, h->d_niter, h->d_pivflag, (warm ? 256 : 0) | (h->rect_update ? 512 : 0), qst, qVm, qVa);
+                           h->d_Va, h->d_err, h->d_niter, h->d_pivflag, (warm ? 256 : 0) | (h->rect_update ? 512 : 0) | (h->src_set ? 1024 : 0), qst, qVm, qVa);
         if (h->dist_open && distortion_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;   // (before the storages are refilled)
         if (h->bstat_open && branch_add_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;
         if (warm)
@@ -1886,6 +2008,15 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
         else
             hipLaunchKernelGGL(k_queue_init, grid2((int)count, S_max), dim3(TPB), 0, h->stream, n, Hn, newlist, slot_scen, qP, qQ, sVm, sVa,
                                h->d_P, h->d_Q, h->d_Vm, h->d_Va, h->d_U, h->d_E, h->d_niter, h->d_pivflag);
+        if (h->src_set) {                                // (hpf_queue_sources: the new scenarios' sources move in with their loads)
+            const int nnl = n - h->m;
+            if (h->qsrc_form == SRC_CURRENTS)
+                hipLaunchKernelGGL(k_source_gather, grid2(nnl * Hn, S_max), dim3(TPB), 0, h->stream, nnl * Hn, newlist, slot_scen,
+                                   (const cplx*)h->d_qsrc, h->d_src);
+            else
+                hipLaunchKernelGGL(k_source_expand, grid2(nnl * Hn, S_max), dim3(TPB), 0, h->stream, nnl, Hn, h->m, newlist, slot_scen, 0,
+                                   (const double*)h->d_qsrc, h->d_qorders, h->d_dev, h->d_IN, h->d_src);
+        }
         set_ctx(h, h->stream, 0, S_max);
         int rr = launch_mismatch<false>(h, newlist, false);
         full_ctx(h);
@@ -1949,6 +2080,7 @@ void free_all(hpf_handle* h) {
     distortion_free(h);
     branch_free(h);
     start_free(h);
+    sources_free(h);
     tree_free(h);
     for (auto& sp : h->spans) {
         hipEventDestroy(sp.e0);
@@ -2158,9 +2290,69 @@ int hpf_set_loads(hpf_handle* h, int n_scen, const double* P, const double* Q) {
     HIPCHK(hipMemcpyAsync(h->d_Q, Q, sizeof(double) * (size_t)n_scen * h->n, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->loads_set = true;
+    h->src_set = false;                                  // (sources belong to a batch's loads: new loads, the model's I_N again)
     h->mismatch_valid = false;
     h->prev_valid = false;
     h->solve_done = false;
+    return HPF_OK;
+}
+
+int hpf_set_sources(hpf_handle* h, int n_scen, int form, const double* data, const int32_t* orders) {
+    int r;
+    if ((r = sources_check(h, n_scen, form, data, orders))) return r;
+    if (!h->loads_set || h->S < 1) return HPF_E_STATE;
+    if (n_scen != h->S) return HPF_E_ARG;
+    if (h->n == h->m) return HPF_OK;                     // no nonlinear bus: nothing to set
+    void* dd = nullptr;
+    int* od = nullptr;
+    if ((r = sources_upload(h, n_scen, form, data, orders, &dd, &od))) return r;
+    r = sources_fill(h, n_scen, form, dd, od, 0);
+    if (r == HPF_OK && hipStreamSynchronize(h->stream) != hipSuccess) r = HPF_E_HIP;
+    hipFree(dd);
+    if (od) hipFree(od);
+    if (r) {
+        h->src_set = false;
+        return r;
+    }
+    h->src_set = true;
+    h->mismatch_valid = false;
+    h->solve_done = false;
+    return HPF_OK;
+}
+
+int hpf_get_sources(hpf_handle* h, double* I_src) {
+    if (!h || !I_src) return HPF_E_ARG;
+    if (!h->src_set || h->S < 1) return HPF_E_STATE;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(I_src, h->d_src, sizeof(cplx) * (size_t)h->S * (h->n - h->m) * h->Hn, hipMemcpyDeviceToHost));
+    return HPF_OK;
+}
+
+int hpf_clear_sources(hpf_handle* h) {
+    if (!h) return HPF_E_ARG;
+    if (!h->d_src && !h->d_qsrc) {
+        h->src_set = false;
+        return HPF_OK;
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    sources_free(h);
+    h->mismatch_valid = false;
+    h->solve_done = false;
+    return HPF_OK;
+}
+
+int hpf_queue_sources(hpf_handle* h, int n_total, int form, const double* data, const int32_t* orders) {
+    int r;
+    if ((r = sources_check(h, n_total, form, data, orders))) return r;
+    if (h->n == h->m) return HPF_OK;
+    queue_sources_drop(h);                               // (a registration that was never consumed is replaced)
+    void* dd = nullptr;
+    int* od = nullptr;
+    if ((r = sources_upload(h, n_total, form, data, orders, &dd, &od))) return r;
+    h->d_qsrc = dd;
+    h->d_qorders = od;
+    h->qsrc_n = n_total;
+    h->qsrc_form = form;
     return HPF_OK;
 }
 
@@ -2454,18 +2646,32 @@ int hpf_solve(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* e
     return nr_loop<false>(h, thresh, max_iter, n_iter, err, err_hist);
 }
 
-int hpf_solve_queue(hpf_handle* h, int n_total, const double* P, const double* Q, double thresh_f, int max_iter_f, double thresh,
-                    int max_iter, hpf_stat* stats, double* Vm, double* Va) {
-    if (!h || !P || !Q || n_total < 1 || max_iter < 0 || max_iter_f < 0 || (Vm == nullptr) != (Va == nullptr)) return HPF_E_ARG;
+// hpf_solve_queue behind its argument checks.  With a registration of hpf_queue_sources every scenario is solved with its sources: the fast path
+// moves them into a scenario's storage with its loads (k_source_gather / k_source_expand), the waves set them device to device after the loads
+static int solve_queue_any(hpf_handle* h, int n_total, const double* P, const double* Q, double thresh_f, int max_iter_f, double thresh,
+                           int max_iter, hpf_stat* stats, double* Vm, double* Va) {
+    const bool with_src = h->qsrc_n > 0;
+    h->src_set = false;
+    if (with_src) {
+        int r;
+        if (!h->d_src && (r = dev_alloc(h, &h->d_src, (size_t)h->S_max * (h->n - h->m) * h->Hn))) return r;
+    }
     const bool fast = h->solver == HPF_SOLVER_BLOCK_TREE && h->n_ties == 0 && h->has_ctree && h->gj_mode == 1 &&
                       bus_images(h) && h->S_max <= 4096 && !h->trace_Vm;      // (k_queue_refill keeps its storage table in LDS: 8 B per slot)
-    if (fast) return solve_queue_fast(h, n_total, P, Q, thresh_f, max_iter_f, thresh, max_iter, stats, Vm, Va);
+    if (fast) {
+        h->src_set = with_src;
+        return solve_queue_fast(h, n_total, P, Q, thresh_f, max_iter_f, thresh, max_iter, stats, Vm, Va);
+    }
     // every other handle (dense solver, meshed network, pivoted mode): waves of up to S_max scenarios through the per-batch entry points
     const size_t cnt = (size_t)h->n * h->Hn;
     for (int g0 = 0; g0 < n_total; g0 += h->S_max) {
         const int S = n_total - g0 < h->S_max ? n_total - g0 : h->S_max;
         int r;
         if ((r = hpf_set_loads(h, S, P + (size_t)g0 * h->n, Q + (size_t)g0 * h->n))) return r;
+        if (with_src) {
+            if ((r = sources_fill(h, S, h->qsrc_form, h->d_qsrc, h->d_qorders, g0))) return r;
+            h->src_set = true;
+        }
         if (h->start_set) {                              // every scenario from the handle's start state, no pf
             if ((r = hpf_start_apply(h, S))) return r;
         } else {
@@ -2481,6 +2687,19 @@ int hpf_solve_queue(hpf_handle* h, int n_total, const double* P, const double* Q
     h->loads_set = h->state_set = h->solve_done = h->from_start = false;   // (as on the queued path: the handle is left without a defined batch)
     h->S = 0;
     return HPF_OK;
+}
+
+int hpf_solve_queue(hpf_handle* h, int n_total, const double* P, const double* Q, double thresh_f, int max_iter_f, double thresh,
+                    int max_iter, hpf_stat* stats, double* Vm, double* Va) {
+    if (!h || !P || !Q || n_total < 1 || max_iter < 0 || max_iter_f < 0 || (Vm == nullptr) != (Va == nullptr)) return HPF_E_ARG;
+    if (h->qsrc_n && h->qsrc_n != n_total) {             // sources registered for another sweep: refused, and the registration is gone
+        queue_sources_drop(h);
+        return HPF_E_ARG;
+    }
+    const int rq = solve_queue_any(h, n_total, P, Q, thresh_f, max_iter_f, thresh, max_iter, stats, Vm, Va);
+    queue_sources_drop(h);                               // (consumed; the handle holds no batch, hence no sources either)
+    h->src_set = false;
+    return rq;
 }
 
 // `iters` unconditional iterations of every scenario, enqueued group by group on the group streams (fork / join with h->stream)

@@ -193,6 +193,50 @@ class DeviceModel:
         """set_state of the start state tiled to n_scen scenarios, on the device; solve() then marks the records with flags bit 8."""
         self._chk(self.lib.hpf_start_apply(self._h, int(n_scen)), "hpf_start_apply")
 
+    # -- per-scenario source currents (hpf_set_sources / hpf_queue_sources) ----------------------------------
+    SOURCE_FORMS = {"currents": _lib.SRC_CURRENTS, "scale_shift": _lib.SRC_SCALE_SHIFT}
+
+    def _sources_args(self, data, form, where):
+        """(n_scen, form code, float64 array, orders) for the C ABI.  form="currents": data [S][n-m][Hn] complex; "scale_shift": data [S][n-m][2]
+        = (a, phi) per scenario and nonlinear bus (a 2-D array is one scenario).  ValueError for another form or shape, before any device call."""
+        if not (isinstance(form, str) and form in self.SOURCE_FORMS):
+            raise ValueError("%s: form=%r ('currents' or 'scale_shift')" % (where, form))
+        nnl = self.n - self.m
+        if form == "currents":
+            a = np.ascontiguousarray(data, dtype=np.complex128)
+            tail = (nnl, self.Hn)
+        else:
+            a = np.ascontiguousarray(data, dtype=np.float64)
+            tail = (nnl, 2)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.shape[1:] != tail or a.shape[0] < 1:
+            raise ValueError("%s: form %r takes an array [n_scen][%d][%d], got %s" % (where, form, tail[0], tail[1], a.shape))
+        return a.shape[0], self.SOURCE_FORMS[form], np.ascontiguousarray(a).view(np.float64), np.ascontiguousarray(self.harmonics, dtype=np.int32)
+
+    def set_sources(self, data, form="currents"):
+        """Norton source currents of the current batch (after set_loads; include/hpf.h "Source currents"): scenario s forms the current balance of
+        nonlinear bus i with I_src[s][i-m][q] in place of the model's I_N.  form="currents": data = I_src [S][n-m][Hn] complex, p.u.;
+        form="scale_shift": data [S][n-m][2] = (a, phi): a units of the bus's device, shifted in time by phi rad at the fundamental (harmonic h
+        rotates by h phi; the orders are self.harmonics), expanded on the device.  set_loads drops them."""
+        S, code, a, orders = self._sources_args(data, form, "set_sources")
+        self._chk(self.lib.hpf_set_sources(self._h, S, code, _dp(a), _ip(orders)), "hpf_set_sources")
+
+    def get_sources(self):
+        """-> I_src [S][n-m][Hn] complex as the device holds them; HPF_E_STATE when the batch has none (never set, cleared, or after set_loads)."""
+        out = np.empty((self._batch("hpf_get_sources"), self.n - self.m, self.Hn), dtype=np.complex128)
+        self._chk(self.lib.hpf_get_sources(self._h, out.view(np.float64).ctypes.data_as(_lib.c_dbl_p)), "hpf_get_sources")
+        return out
+
+    def clear_sources(self):
+        self._chk(self.lib.hpf_clear_sources(self._h), "hpf_clear_sources")
+
+    def queue_sources(self, data, form="currents"):
+        """The sources of the NEXT solve_queue call, one row per scenario of its P, Q (forms as set_sources); a call with another number of
+        scenarios is refused (HPF_E_ARG) and the registration dropped."""
+        S, code, a, orders = self._sources_args(data, form, "queue_sources")
+        self._chk(self.lib.hpf_queue_sources(self._h, S, code, _dp(a), _ip(orders)), "hpf_queue_sources")
+
     # -- kernels -------------------------------------------------------------------------------------------
     def mismatch(self, fund=False, want_f=True):
         N = self.Nf if fund else self.N

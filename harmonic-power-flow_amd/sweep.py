@@ -243,8 +243,53 @@ def gather_branch_stats(stats, world, ids=None):
     return _gather_merge(stats, world, ids)
 
 
+def source_currents(I_N_bus, scale, shift, orders, cs=None):
+    """Host expansion of the scale-and-shift form of the source currents (include/hpf.h "Source currents", csrc/hpf_sources.hpp):
+    I_src[..., b, q] = (scale[..., b] e^(j orders[q] shift[..., b])) I_N_bus[b, q] -- scale units of the device of nonlinear bus b, their waveform
+    shifted in time by shift rad at the fundamental.  I_N_bus [n-m][Hn] complex (the model's I_N of every nonlinear bus's device), scale / shift
+    [..., n-m], orders [Hn] -> [..., n-m][Hn] complex.  Written with real-array operations in the device's order -- ang = h * phi; w = (a cos, a sin);
+    (w.re in.re - w.im in.im, w.re in.im + w.im in.re) -- so that every product and sum is rounded on its own (a complex array multiply would be
+    free to fuse).  cs = (cos, sin) [..., n-m][Hn]: taken instead of numpy's own values of ang (tests: two implementations bit for bit)."""
+    I_N_bus = np.asarray(I_N_bus, dtype=np.complex128)
+    a = np.asarray(scale, dtype=np.float64)[..., None]
+    phi = np.asarray(shift, dtype=np.float64)[..., None]
+    if cs is None:
+        ang = np.asarray(orders).astype(np.float64) * phi
+        c, sn = np.cos(ang), np.sin(ang)
+    else:
+        c, sn = (np.asarray(x, dtype=np.float64) for x in cs)
+    wre, wim = a * c, a * sn
+    inr, ini = I_N_bus.real, I_N_bus.imag
+    out = np.empty(np.broadcast(wre, inr).shape, dtype=np.complex128)
+    out.real = wre * inr - wim * ini
+    out.imag = wre * ini + wim * inr
+    return out
+
+
+def sources_argument(sources, n_scen, nnl, Hn, where="solve_scenarios"):
+    """The `sources` dict of solve_scenarios / hpf -> None, or (form, array) as DeviceModel.set_sources takes them: {"currents": [n_scen][n-m][Hn]}
+    -> ("currents", complex array); {"scale": [n_scen][n-m], "shift": [n_scen][n-m]} (either may be missing: 1 / 0) -> ("scale_shift",
+    [n_scen][n-m][2]).  ValueError for anything else, on the host."""
+    if sources is None:
+        return None
+    if not isinstance(sources, dict) or not sources or not (set(sources) <= {"currents"} or set(sources) <= {"scale", "shift"}):
+        raise ValueError("%s: sources=%r ({'currents': ..} or {'scale': .., 'shift': ..})" % (where, sources))
+    if "currents" in sources:
+        a = np.asarray(sources["currents"], dtype=np.complex128)
+        if a.shape != (n_scen, nnl, Hn):
+            raise ValueError("%s: sources['currents'] must be [%d][%d][%d], got %s" % (where, n_scen, nnl, Hn, a.shape))
+        return "currents", np.ascontiguousarray(a)
+    ab = np.empty((n_scen, nnl, 2))
+    for k, (name, default) in enumerate((("scale", 1.0), ("shift", 0.0))):
+        v = np.asarray(sources.get(name, default), dtype=np.float64)
+        if name in sources and v.shape != (n_scen, nnl):
+            raise ValueError("%s: sources[%r] must be [%d][%d], got %s" % (where, name, n_scen, nnl, v.shape))
+        ab[:, :, k] = v
+    return "scale_shift", ab
+
+
 def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_iter_h=50, want_voltages=False, refill=True, distortion=None,
-                    branches=None, start=None, update="polar"):
+                    branches=None, start=None, update="polar", sources=None):
     """Monte-Carlo / what-if sweep on ONE GPU: every row of P, Q [n_scen][n] (p.u. loads, HG:197,372) is one scenario of the
     network `dm` (a DeviceModel) holds -- the reference's counterpart is one hpf() call per load case (HG:511).  Per scenario:
     reference start (HG:174-184), fundamental pf (HG:244), harmonic NR with the reference's stop rule (HG:536).
@@ -284,16 +329,27 @@ def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_i
     the reference's start instead of 20 - 30, the same fixed point; the base case of a warm start is solved in the same mode.  Records carry flags
     bit 9.  A scenario that does not converge this way (bit 9 without bit 0, after the re-solves above) is solved again with the reference's
     update, cold: its final record carries neither bit 9 nor bit 8 and is what update="polar" returns for it; the accumulators count it as deferred
-    and add it once.  The handle's option is put back to what it was when the call returns.  ValueError for any other string."""
+    and add it once.  The handle's option is put back to what it was when the call returns.  ValueError for any other string.
+    sources: None (default): every scenario has the model's Norton source currents I_N, today's behaviour bit for bit.  Otherwise per-scenario
+    source currents of the nonlinear buses (include/hpf.h "Source currents"; DESIGN.md 6.5): {"scale": [n_scen][n-m], "shift": [n_scen][n-m]}
+    (either may be missing: 1 / 0) -- scale units of each bus's device in service, their waveform shifted in time by shift rad at the fundamental,
+    expanded on the device with dm.harmonics -- or {"currents": [n_scen][n-m][Hn]} complex, used as given.  Row s belongs to row s of P, Q: every
+    path that solves a scenario (queue pieces, waves, the re-solves of flagged / not converged scenarios) sets its sources with its loads.  Records
+    carry flags bit 10.  The base case of a warm start {"P", "Q"} is solved with the model's I_N unless the dict carries its own one-row
+    "sources".  ValueError for wrong shapes, before any device call."""
     from .device import DeviceModel
     if not (isinstance(update, str) and update in DeviceModel.UPDATES):
         raise ValueError("solve_scenarios: update=%r ('polar' or 'rectangular')" % (update,))
+    src = sources_argument(sources, np.atleast_2d(np.asarray(P)).shape[0], dm.n - dm.m, dm.Hn)
+    if isinstance(start, dict) and start.get("sources") is not None:
+        sources_argument(start["sources"], 1, dm.n - dm.m, dm.Hn, "solve_scenarios: start")
     with dm.update_mode(update):
         return _solve_scenarios_started(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion, branches, start,
-                                        update == "rectangular")
+                                        update == "rectangular", src)
 
 
-def _solve_scenarios_started(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion, branches, start, rect):
+def _solve_scenarios_started(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion, branches, start, rect,
+                             src=None):
     """solve_scenarios inside the scope of its update mode: start state, accumulators, the sweep"""
     if start is None:
         if dm.has_start():
@@ -303,7 +359,7 @@ def _solve_scenarios_started(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_
     try:
         if distortion is None and branches is None:
             return _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, False, False, start is not None,
-                                    rect)
+                                    rect, src)
         if distortion is not None:
             dm.distortion_begin(distortion.get("limit"), distortion.get("thd_limit", np.inf), distortion.get("hist_max", 1.0),
                                 distortion.get("bins", 64))
@@ -311,7 +367,7 @@ def _solve_scenarios_started(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_
             if branches is not None:
                 dm.branch_stats_begin(branches.get("rating"))
             res = _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion is not None,
-                                   branches is not None, start is not None, rect)
+                                   branches is not None, start is not None, rect, src)
             extra = (() if distortion is None else (dm.distortion_get(),)) + (() if branches is None else (dm.branch_stats_get(),))
         finally:
             dm.set_option("distortion_id_base", 0)
@@ -336,6 +392,9 @@ def _set_start(dm, P, Q, start, thresh_f, max_iter_f, thresh_h, max_iter_h):
     if not (isinstance(start, dict) and "P" in start and "Q" in start):
         raise ValueError("solve_scenarios: start=%r (None, a pair (Vm0, Va0), {'P': .., 'Q': ..} or 'mean')" % (start,))
     dm.set_loads(np.asarray(start["P"], dtype=np.float64).reshape(1, -1), np.asarray(start["Q"], dtype=np.float64).reshape(1, -1))
+    base_src = sources_argument(start.get("sources"), 1, dm.n - dm.m, dm.Hn, "solve_scenarios: start")
+    if base_src:                                         # (else the base case has the model's I_N)
+        dm.set_sources(base_src[1], base_src[0])
     dm.set_state(None, None, n_scen=1)
     dm.fund_pf(thresh_f, max_iter_f)
     dm.solve(min(thresh_h, 1e-9), max_iter_h)
@@ -346,7 +405,8 @@ def _set_start(dm, P, Q, start, thresh_f, max_iter_f, thresh_h, max_iter_h):
     dm.capture_start(0)
 
 
-def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion, branches, warm=False, rect=False):
+def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion, branches, warm=False, rect=False,
+                     src=None):
     P = np.ascontiguousarray(np.atleast_2d(P), dtype=np.float64)
     Q = np.ascontiguousarray(np.atleast_2d(Q), dtype=np.float64)
     n_scen = P.shape[0]
@@ -360,6 +420,8 @@ def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_
         """scenarios a..b-1 as one batch: cold (reference start + pf) or from the start state.  keep_unconverged=False (one scenario): a result that did not converge is dropped, neither
         stored nor added -- the caller solves the scenario again -> False"""
         dm.set_loads(P[a:b], Q[a:b])
+        if src:                                          # (every path that sets the loads of rows a..b sets their sources right after)
+            dm.set_sources(src[1][a:b], src[0])
         if from_start:
             dm.apply_start(b - a)
         else:
@@ -424,6 +486,8 @@ def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_
         b = min(a + per_call, n_scen)
         if distortion or branches:
             dm.set_option("distortion_id_base", a)
+        if src:
+            dm.queue_sources(src[1][a:b], src[0])
         res = dm.solve_queue(P[a:b], Q[a:b], thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages=want_voltages)
         if want_voltages:
             rec, Vm[a:b], Va[a:b] = res

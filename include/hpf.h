@@ -86,7 +86,8 @@ typedef struct hpf_stat {
                                   bit6 option "step_residual_check": a Newton step of the first pass missed the residual limit,
                                   bit7 ... a step of the pass whose result is returned did (= bit6 unless bit4 is set),
                                   bit8 the scenario was started from the handle's start state (hpf_start_*), not from the reference's start + pf,
-                                  bit9 the scenario's harmonic steps were applied in rectangular form (option "rectangular_update") */
+                                  bit9 the scenario's harmonic steps were applied in rectangular form (option "rectangular_update"),
+                                  bit10 the scenario was solved with per-scenario source currents (hpf_set_sources / hpf_queue_sources) */
     double  err;               /* final ||f||_inf                                        HG:389 */
     double  thd_max;           /* max over buses of THD_F                                HG:566-568 */
 } hpf_stat;
@@ -330,6 +331,44 @@ int  hpf_start_capture(hpf_handle* h, int scen);
 int  hpf_start_get(hpf_handle* h, double* Vm0, double* Va0);
 int  hpf_start_clear(hpf_handle* h);
 int  hpf_start_apply(hpf_handle* h, int n_scen);
+
+/* Source currents: per-scenario Norton source currents, the quantity a probabilistic harmonic study randomises (how many units of a device are in
+ * service, and the phase-angle diversity between devices that decides their cancellation).  The reference has no counterpart: its Norton data are
+ * per device type (HG:278-310).  A nonlinear bus i (m <= i < n) has current-balance rows only, I_inj = I_N - Y_N U (HG:313-323, 347-354); with sources
+ * set, scenario s forms them with I_src[s][i - m][q] in place of I_N[dev(i)][q] at every harmonic position q.  Y_N stays the model's: the Jacobian,
+ * the tree plan and every per-model image are untouched, only the right-hand side of the Newton step changes.
+ * Two input forms (`form`):
+ *   HPF_SRC_CURRENTS (0): data = I_src itself, [S][n - m][Hn] complex (interleaved re, im), p.u.; used as given.
+ *   HPF_SRC_SCALE_SHIFT (1): data = (a, phi) [S][n - m][2] doubles -- a units of the bus's device, their waveform shifted in time by phi radians at
+ *     the fundamental, so that harmonic order h rotates by h phi: I_src[q] = (a e^(j h_q phi)) I_N[dev(i)][q].  The handle does not know the harmonic
+ *     orders: orders [Hn] (1, 3, 5, ...) comes with the data.  Expanded on the device (k_source_expand) with the rounding of csrc/hpf_sources.hpp:
+ *     ang = (double)h_q * phi; (s, c) = sincos(ang); w = (a c, a s); I = (w.re in.re - w.im in.im, w.re in.im + w.im in.re), every product and sum
+ *     rounded on its own.
+ * Sources belong to the batch's LOADS.  hpf_set_sources needs a batch with loads (HPF_E_STATE otherwise) and n_scen == hpf_num_scenarios (else
+ *   HPF_E_ARG); hpf_set_loads DROPS them -- the next mismatch uses the model's I_N again, so no source leaks into another batch.  hpf_set_state and
+ *   hpf_start_apply keep them.
+ * Argument checks, all on the host before any HIP call, HPF_E_ARG: a NULL handle or NULL data, an unknown form, orders NULL with form 1, n_scen < 1,
+ *   a non-finite entry.  A model without nonlinear buses (m == n): HPF_OK, nothing is done.
+ * hpf_get_sources: the I_src the device holds for the batch, [S][n - m][Hn] complex (after form 1: the expanded currents).  HPF_E_STATE when the
+ *   batch has none (never set, cleared, or dropped by hpf_set_loads).
+ * hpf_clear_sources: the batch goes back to the model's I_N; frees the storage and a pending registration (HPF_OK when there is none); hpf_destroy
+ *   frees them too.
+ * hpf_queue_sources: the sources of a whole sweep of n_total scenarios (same forms, [n_total][...]), uploaded to HBM and consumed by the NEXT
+ *   hpf_solve_queue.  If that call's n_total differs it returns HPF_E_ARG, the registration is dropped and nothing is solved.  Radial BLOCK_TREE
+ *   handles move a scenario's sources into its storage with its loads (k_source_gather / k_source_expand next to k_queue_init); the wave handles
+ *   (DENSE, meshed, pivoted) set each wave's sources device to device after its loads.  A scenario's record and voltages are bit-identical to
+ *   hpf_set_loads + hpf_set_sources + (hpf_fund_pf) + hpf_solve of that scenario alone, whatever the slot count, "queue_chunk" or
+ *   "scenario_groups".  Afterwards the handle holds no batch and no sources.
+ * What sees the sources: hpf_mismatch, hpf_solve (its pivoted repeat and the trace included), hpf_solve_queue, hpf_iterate, the step-residual check,
+ *   both update modes.  NOT affected: hpf_fund_mismatch / hpf_fund_pf (the fundamental pf uses P, Q only), the Jacobian entry points, the start
+ *   state, the accumulators (they read voltages).  Records of scenarios solved with sources carry hpf_stat.flags bit 10.
+ * Unset (the default): nothing is allocated, no launch is added or changed (the kernels' source variants are separate instantiations), every output
+ *   of every entry point is bit-identical. */
+enum { HPF_SRC_CURRENTS = 0, HPF_SRC_SCALE_SHIFT = 1 };
+int  hpf_set_sources(hpf_handle* h, int n_scen, int form, const double* data, const int32_t* orders);
+int  hpf_get_sources(hpf_handle* h, double* I_src /* [S][n-m][Hn] complex, as the device holds them */);
+int  hpf_clear_sources(hpf_handle* h);
+int  hpf_queue_sources(hpf_handle* h, int n_total, int form, const double* data, const int32_t* orders);
 
 /* Diagnostics: with env HPF_DEBUG_ABLATE & 16 the BLOCK_TREE factor kernel records shader-cycle stamps per (scenario, bus):
  * out[(s*n + k)*8 + 0..5] = assembly, packed sub-phases, packed Gauss-Jordan split, MFMA Gauss-Jordan, packed wave-0 roles,

@@ -21,6 +21,7 @@
 #include <complex>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <rocsolver/rocsolver.h>
 #include <thread>
 
@@ -1315,9 +1316,15 @@ static int back_depth(hpf_handle* h, const Tree& T, const TreeDev& td, int dl, i
 }
 
 // every bordered bus and constant-inverse leaf at once, 16 scenarios per workgroup: a leaf's x needs its parent's only, and nothing of the
-// dense tree hangs below a leaf (the 2x2 kernels that do come next)
+// dense tree hangs below a leaf (the 2x2 kernels that do come next) -- in one launch that walks their families (k_back_tail), or with
+// HPF_BACKTAIL=0 in one launch per nesting order of the bordered buses and one for the leaves
 template <int BW>
 static int back_batched(hpf_handle* h, const Tree& T, const int* active) {
+    if (h->sw.back_tail && T.n_tail_fam > 0 && T.d_tail_rec) {
+        if (int r = launch_back_tail<BW>(h, T, active)) return r;
+        ++h->n_back_tails;
+        return HPF_OK;
+    }
     // bordered buses first (leaves hang below them), in groups by nesting order: nested ones first
     for (size_t gi = 0; gi + 1 < T.bsleaf_ptr.size() && T.n_bsleaf > 0; ++gi) {
         const int b0 = T.bsleaf_ptr[gi], cnt = T.bsleaf_ptr[gi + 1] - b0;

@@ -34,6 +34,8 @@ struct TimedSpan {
 // back-sweep tree walk: at most WALK_LISTS subtree lists (x 32 scenarios: one workgroup per CU), an LDS ring of the x of the last
 // WALK_SLOTS buses a workgroup walked
 constexpr int WALK_LISTS = 8, WALK_SLOTS = 32;
+// back-sweep tail: LDS slots of a family's store of x (16 scenarios each); the children of a bus that gets none read its x from HBM
+constexpr int TAIL_SLOTS = 2;
 
 // Feeder-tree description for the BLOCK_TREE solver (host copies + device copies).
 struct Tree {
@@ -152,6 +154,15 @@ struct Tree {
     int* d_walk_ptr = nullptr;
     int* d_walk_rec = nullptr;
     int* d_walk_slot = nullptr;
+    // back-sweep tail (k_back_tail): the records of d_bsleaf and d_bleaf in families -- a batched bus whose dense parent is not batched (a bordered
+    // bus or a leaf under a Gauss-Jordan bus), then its nested bordered buses and the leaves below any of them, every member after its parent;
+    // families longest first.  One record per member: kind (0 bordered, 1 leaf), index of its record in d_bsleaf / d_bleaf, LDS slot of its
+    // parent's x (-1: from HBM, an earlier launch wrote it; -2: from HBM, the family's workgroup wrote it), LDS slot its own x goes to (-1: none of its family reads it from LDS)
+    int n_tail_fam = 0;
+    std::vector<int> tail_ptr;        // [n_tail_fam + 1] family f: members tail_ptr[f] .. tail_ptr[f + 1]
+    std::vector<int> tail_rec;        // [][4]
+    int* d_tail_ptr = nullptr;
+    int* d_tail_rec = nullptr;
     std::vector<void*> d_owned;       // every device array above, as tree_upload allocated it: what tree_free_one frees
     double plan_ms = 0.0;             // host time of tree_build_into up to the uploads (all planning, the back-sweep batch records included)
     double flops_per_solve = 0.0;     // factor sweep + back sweep
@@ -307,6 +318,7 @@ struct hpf_handle {
     hpf::Tree tree;                   // elimination tree as the network gives it (single-wave / generic kernels, pf)
     hpf::Tree ctree;                  // the same with pass-through buses contracted (multi-wave kernels, gj_mode 1)
     bool has_ctree = false;
+    long long n_back_tails = 0;       // back sweeps whose bordered buses and constant-inverse leaves went through k_back_tail (hpf_tree_census[16])
     long long n_back_walks = 0;       // back sweeps (scenario group x Newton step) whose Gauss-Jordan buses went through k_back_walk (hpf_tree_census[15])
     int auto_repivot = 1;             // hpf_solve repeats scenarios flagged by the static-pivot monitor with partial pivoting
     int* h_act[2] = {nullptr, nullptr};          // pinned copies of d_active (hpf_solve looks at chunk c - 1 while chunk c runs)

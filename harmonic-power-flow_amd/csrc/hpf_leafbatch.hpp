@@ -271,72 +271,140 @@ int launch_leaf_batch(hpf_handle* h, const TreeDev& T, const int* nodes, int cou
     return launch_status(h);
 }
 
+// The thread's place in a scenario-batched back-sweep workgroup (16 threads per scenario) and its scenario
+struct BatchLane {
+    int tid, lane, lg, jj, wv, sc, l16, s;
+    bool live;
+};
+
+__device__ __forceinline__ BatchLane batch_lane(int by_, const int* __restrict__ active, int S_cnt, int s0) {
+    BatchLane L;
+    L.tid = threadIdx.x; L.lane = L.tid & 63; L.lg = L.lane >> 4; L.jj = L.lane & 15;
+    L.wv = __builtin_amdgcn_readfirstlane(L.tid >> 6);
+    L.sc = L.tid >> 4; L.l16 = L.tid & 15;
+    const int sl = by_ * LB_SB + L.sc;
+    const int ss = sl < S_cnt ? (active ? active[sl + s0] : sl + s0) : -1;      // slot -> scenario (active list; -1: frozen / empty slot)
+    L.live = ss >= 0;
+    L.s = L.live ? ss : 0;
+    return L;
+}
+
+// One bus of a batched back-sweep body, from its record (workgroup-uniform).  pslot: where x_parent is -- an LDS slot of k_back_tail's store,
+// -1: in HBM since an earlier launch (the load part fetches it), -2: in HBM, written by this very thread earlier in this launch (read when
+// the compute part starts); oslot: the LDS slot the bus's own x goes to besides HBM (-1: none)
+struct BatchBus {
+    int kind, k, par, m, pslot, oslot;    // kind 0: bordered bus, 1: leaf
+    const double* img;                    // its per-model image
+    const double* qbm;                    // bordered bus: Qb [m][b]
+};
+
+// Everything a batched back-sweep body reads from HBM for one bus, held in registers between its load parts and its compute parts (as BackQIn
+// is for k_back_q).  One type for both bodies -- tr: the thread's row of T^-1 (bordered bus) or K | Lc of its harmonics (leaf).  The
+// operands come in two halves by their last use: `early` ones (A(k,parent), x_parent, W_k^-1, the image column of the first MFMAs) are free
+// again after the first half of the compute part, `late` ones (tr, the Pb column, S^-1, w) at its end -- k_back_tail refills each half
+// with the next member's there, so those requests are in flight while the current member computes, in no more registers than one bus needs.
+template <int B>
+struct BatchBackIn {
+    static constexpr int KS = SleafImg<B>::KS, KP = SleafImg<B>::KP, QI = (B / 2 + 15) / 16;
+    double ia[KS], wi[4], hk[2][4], xp[2][2];                 // early
+    double pa[KP], tr[12], si4[QI][4], w4[QI][2];             // late
+};
+
+// early operands of both kinds: the lane's image column, A(k,parent) and, where it is in HBM already, x_parent of the harmonics l16, l16 + 16
+template <int B>
+__device__ __forceinline__ void batch_back_load_early(BatchBackIn<B>& I, const BatchBus& U, const BatchLane& L, const Model& M,
+                                                      const double* __restrict__ xall, const double* __restrict__ Hall) {
+    constexpr int NTR = SleafImg<B>::NTR, KS = SleafImg<B>::KS;
+    const int n = M.n, Hn = M.Hn;
+    if (L.wv < NTR) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) I.ia[ks] = U.img[((size_t)L.wv * KS + ks) * 64 + L.lane];
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int q = L.l16 + 16 * j;
+        I.hk[j][0] = I.hk[j][1] = I.hk[j][2] = I.hk[j][3] = 0.0;
+        I.xp[j][0] = I.xp[j][1] = 0.0;
+        if (L.live && q < Hn) {
+            const double* hk = Hall + (((size_t)L.s * n + U.k) * Hn + q) * 4;
+            I.hk[j][0] = hk[0]; I.hk[j][1] = hk[1]; I.hk[j][2] = hk[2]; I.hk[j][3] = hk[3];
+            if (U.pslot == -1) {
+                const double2 xp = *reinterpret_cast<const double2*>(xall + ((size_t)L.s * n + U.par) * B + 2 * q);
+                I.xp[j][0] = xp.x; I.xp[j][1] = xp.y;
+            }
+        }
+    }
+}
+
+// t = A(k,parent) x_parent of harmonic l16 + 16 j; x_parent from the family's LDS store (the thread's own entries: it wrote them), else from HBM
+template <int B>
+__device__ __forceinline__ void batch_back_t(const BatchBackIn<B>& I, const BatchBus& U, const BatchLane& L, const Model& M, const double* xall,
+                                             const double2* XS, int j, double& t0, double& t1) {
+    constexpr int QI = BatchBackIn<B>::QI;
+    double2 xp = double2{I.xp[j][0], I.xp[j][1]};
+    if (U.pslot >= 0) xp = XS[((size_t)U.pslot * QI + (j < QI ? j : 0)) * 256 + L.tid];
+    else if (U.pslot == -2) xp = *reinterpret_cast<const double2*>(xall + ((size_t)L.s * M.n + U.par) * B + 2 * (L.l16 + 16 * j));
+    const double* hk = I.hk[j];
+    t0 = fma(hk[1], xp.y, hk[0] * xp.x);
+    t1 = fma(hk[3], xp.y, hk[2] * xp.x);
+}
+
 // Back sweep of the constant-inverse leaves, 16 scenarios per workgroup:  x_k = w_k - S^-1 Drect^-1 t,  t = A(k,parent) x_parent,
 // Drect^-1 t = [u; Vh + Lc u],  V = [0 Lr; 0 Ahh^-1] t  (the same per-model image on the matrix cores),  u = K (t0 + V0).
 // nodes: Tree::d_bdesc records (bus, parent, leaf slot + 1, 0) of leaves only.
 template <int B>
-__device__ __forceinline__ void leaf_back_batch_body(
-    const int bx_, const int by_, const Model& M, const int* __restrict__ nodes, int b, const int* __restrict__ active, int S_cnt, const double* __restrict__ wall,
-    double* __restrict__ xall, const double* __restrict__ Hall, const double* __restrict__ lbimg, const double* __restrict__ lfK,
-    const double* __restrict__ lfS, int s0) {
+__device__ __forceinline__ BatchBus leaf_back_bus(const int4 kp, int pslot, int oslot, const double* __restrict__ lbimg) {
+    return BatchBus{1, kp.x, kp.y, 0, pslot, oslot, lbimg + (size_t)(kp.z - 1) * LeafBatchImg<B>::SZ, nullptr};
+}
+
+// late operands: K, and Lc / S^-1 / w of the thread's harmonics (with the early ones: one round trip for everything addressed by the record)
+template <int B>
+__device__ __forceinline__ void leaf_back_load_late(BatchBackIn<B>& I, const BatchBus& U, const BatchLane& L, const Model& M,
+                                                    const double* __restrict__ wall, const double* __restrict__ lfK, const double* __restrict__ lfS) {
     constexpr int NTR = LeafBatchImg<B>::NTR, KS = LeafBatchImg<B>::KS, H2 = B / 2, QI = (H2 + 15) / 16;
-    const int4 kp = reinterpret_cast<const int4*>(nodes)[bx_];
-    const int k = kp.x, par = kp.y, slot = kp.z - 1;
-    const int tid = threadIdx.x, lane = tid & 63, lg = lane >> 4, jj = lane & 15;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = M.n, Hn = M.Hn;
-    const int sc = tid >> 4, l16 = tid & 15;
-    const int sl = by_ * LB_SB + sc;
-    const int ss = sl < S_cnt ? (active ? active[sl + s0] : sl + s0) : -1;      // slot -> scenario (active list; -1: frozen / empty slot)
-    const bool live = ss >= 0;
-    const int s = live ? ss : 0;
-    double* xs = xall + (size_t)s * n * B;
-    const double* img = lbimg + (size_t)slot * LeafBatchImg<B>::SZ;
-    const double* lcimg = img + NTR * KS * 64;
-
-    __shared__ double TT[64 * LBP];                        // t = A(k,parent) x_parent, [row][scenario]
-    __shared__ double V[64 * LBP];
-    __shared__ double UK[LB_SB * 2];
-
-    // one round trip for everything addressed by the record: the lane's image column, K, and Lc / S^-1 / w of the thread's harmonics
-    double ia[KS], k4[4] = {0.0, 0.0, 0.0, 0.0}, lc4[QI][4], si4[QI][4], w4[QI][2];
-    if (wv < NTR) {
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) ia[ks] = img[((size_t)wv * KS + ks) * 64 + lane];
-    }
+    const int k = U.k, n = M.n, Hn = M.Hn, s = L.s, l16 = L.l16;
+    const bool live = L.live;
+    const double* lcimg = U.img + NTR * KS * 64;
+    I.tr[0] = I.tr[1] = I.tr[2] = I.tr[3] = 0.0;
     if (live && l16 == 0) {
         const double* kk = lfK + ((size_t)s * n + k) * 12;
-        k4[0] = kk[0]; k4[1] = kk[1]; k4[2] = kk[2]; k4[3] = kk[3];
+        I.tr[0] = kk[0]; I.tr[1] = kk[1]; I.tr[2] = kk[2]; I.tr[3] = kk[3];
     }
 #pragma unroll
     for (int it = 0; it < QI; ++it) {
         const int q = l16 + 16 * it;
-        w4[it][0] = w4[it][1] = 0.0;
-        si4[it][0] = si4[it][3] = 1.0;
-        si4[it][1] = si4[it][2] = 0.0;
-        lc4[it][0] = lc4[it][1] = lc4[it][2] = lc4[it][3] = 0.0;
+        double* lc4 = I.tr + 4 + 4 * it;
+        I.w4[it][0] = I.w4[it][1] = 0.0;
+        I.si4[it][0] = I.si4[it][3] = 1.0;
+        I.si4[it][1] = I.si4[it][2] = 0.0;
+        lc4[0] = lc4[1] = lc4[2] = lc4[3] = 0.0;
         if (live && q < H2) {
-            const double2 w2 = *reinterpret_cast<const double2*>(wall + ((size_t)s * n + k) * B + 2 * q);
-            w4[it][0] = w2.x;
-            w4[it][1] = w2.y;
             const double2* lp = reinterpret_cast<const double2*>(lcimg + (2 * q) * 2);
             const double2 l0 = lp[0], l1 = lp[1];
-            lc4[it][0] = l0.x; lc4[it][1] = l0.y; lc4[it][2] = l1.x; lc4[it][3] = l1.y;
+            lc4[0] = l0.x; lc4[1] = l0.y; lc4[2] = l1.x; lc4[3] = l1.y;
             if (q < Hn) {
                 const double2* sp = reinterpret_cast<const double2*>(lfS + (((size_t)s * n + k) * Hn + q) * 4);
                 const double2 a = sp[0], c2 = sp[1];
-                si4[it][0] = a.x; si4[it][1] = a.y; si4[it][2] = c2.x; si4[it][3] = c2.y;
+                I.si4[it][0] = a.x; I.si4[it][1] = a.y; I.si4[it][2] = c2.x; I.si4[it][3] = c2.y;
             }
+            const double2 w2 = *reinterpret_cast<const double2*>(wall + ((size_t)s * n + k) * B + 2 * q);
+            I.w4[it][0] = w2.x;
+            I.w4[it][1] = w2.y;
         }
     }
-    for (int q = l16; q < 32; q += 16) {
+}
+
+// Compute part, first half (the early operands are free after it).  TT: t = A(k,parent) x_parent, [row][scenario]; V [64 * LBP]
+template <int B>
+__device__ __forceinline__ void leaf_back_compute_a(const BatchBackIn<B>& I, const BatchBus& U, const BatchLane& L, const Model& M, const double* xall,
+                                                    double* __restrict__ TT, double* __restrict__ V, const double2* XS) {
+    constexpr int NTR = LeafBatchImg<B>::NTR, KS = LeafBatchImg<B>::KS;
+    const int lg = L.lg, jj = L.jj, wv = L.wv, sc = L.sc, l16 = L.l16;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int q = l16 + 16 * j;
         double t0 = 0.0, t1 = 0.0;
-        if (live && q < Hn) {
-            const double* hk = Hall + (((size_t)s * n + k) * Hn + q) * 4;
-            const double2 xp = *reinterpret_cast<const double2*>(xs + (size_t)par * B + 2 * q);
-            t0 = fma(hk[1], xp.y, hk[0] * xp.x);
-            t1 = fma(hk[3], xp.y, hk[2] * xp.x);
-        }
+        if (L.live && q < M.Hn) batch_back_t<B>(I, U, L, M, xall, XS, j, t0, t1);
         TT[(2 * q) * LBP + sc] = t0;
         TT[(2 * q + 1) * LBP + sc] = t1;
     }
@@ -346,33 +414,60 @@ __device__ __forceinline__ void leaf_back_batch_body(
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const double bop = TT[(4 * ks + lg) * LBP + jj];
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ia[ks], bop, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(I.ia[ks], bop, acc, 0, 0, 0);
         }
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) V[(16 * wv + 4 * reg + lg) * LBP + jj] = acc[reg];
     }
+}
+
+// ... second half.  UK [LB_SB * 2]
+template <int B>
+__device__ __forceinline__ void leaf_back_compute_b(const BatchBackIn<B>& I, const BatchBus& U, const BatchLane& L, const Model& M, double* xall,
+                                                    const double* __restrict__ TT, const double* __restrict__ V, double* __restrict__ UK) {
+    constexpr int H2 = B / 2, QI = (H2 + 15) / 16;
+    const int k = U.k, sc = L.sc, l16 = L.l16;
+    double* xs = xall + (size_t)L.s * M.n * B;
     __syncthreads();
     if (l16 == 0) {
         const double r0 = TT[sc] + V[sc], r1 = TT[LBP + sc] + V[LBP + sc];                      // [I Lr] t
-        UK[sc * 2] = fma(k4[1], r1, k4[0] * r0);
-        UK[sc * 2 + 1] = fma(k4[3], r1, k4[2] * r0);
+        UK[sc * 2] = fma(I.tr[1], r1, I.tr[0] * r0);
+        UK[sc * 2 + 1] = fma(I.tr[3], r1, I.tr[2] * r0);
     }
     __syncthreads();
-    if (live) {
+    if (L.live) {
         const double u0 = UK[sc * 2], u1 = UK[sc * 2 + 1];
 #pragma unroll
         for (int it = 0; it < QI; ++it) {
             const int q = l16 + 16 * it;
             if (q >= H2) continue;
+            const double* lc4 = I.tr + 4 + 4 * it;
             double x0 = u0, x1 = u1;
             if (q > 0) {
-                x0 = V[(2 * q) * LBP + sc] + fma(lc4[it][1], u1, lc4[it][0] * u0);
-                x1 = V[(2 * q + 1) * LBP + sc] + fma(lc4[it][3], u1, lc4[it][2] * u0);
+                x0 = V[(2 * q) * LBP + sc] + fma(lc4[1], u1, lc4[0] * u0);
+                x1 = V[(2 * q + 1) * LBP + sc] + fma(lc4[3], u1, lc4[2] * u0);
             }
-            const double d0 = fma(si4[it][1], x1, si4[it][0] * x0), d1 = fma(si4[it][3], x1, si4[it][2] * x0);
-            *reinterpret_cast<double2*>(xs + (size_t)k * B + 2 * q) = double2{w4[it][0] - d0, w4[it][1] - d1};
+            const double d0 = fma(I.si4[it][1], x1, I.si4[it][0] * x0), d1 = fma(I.si4[it][3], x1, I.si4[it][2] * x0);
+            *reinterpret_cast<double2*>(xs + (size_t)k * B + 2 * q) = double2{I.w4[it][0] - d0, I.w4[it][1] - d1};
         }
     }
+}
+
+template <int B>
+__device__ __forceinline__ void leaf_back_batch_body(
+    const int bx_, const int by_, const Model& M, const int* __restrict__ nodes, int b, const int* __restrict__ active, int S_cnt, const double* __restrict__ wall,
+    double* __restrict__ xall, const double* __restrict__ Hall, const double* __restrict__ lbimg, const double* __restrict__ lfK,
+    const double* __restrict__ lfS, int s0) {
+    __shared__ double TT[64 * LBP];                        // t = A(k,parent) x_parent, [row][scenario]
+    __shared__ double V[64 * LBP];
+    __shared__ double UK[LB_SB * 2];
+    const BatchLane L = batch_lane(by_, active, S_cnt, s0);
+    const BatchBus U = leaf_back_bus<B>(reinterpret_cast<const int4*>(nodes)[bx_], -1, -1, lbimg);
+    BatchBackIn<B> I;
+    batch_back_load_early<B>(I, U, L, M, xall, Hall);
+    leaf_back_load_late<B>(I, U, L, M, wall, lfK, lfS);
+    leaf_back_compute_a<B>(I, U, L, M, xall, TT, V, nullptr);
+    leaf_back_compute_b<B>(I, U, L, M, xall, TT, V, UK);
 }
 
 template <int B>
@@ -397,75 +492,78 @@ int launch_leaf_back_batch(hpf_handle* h, const int* nodes, int count, const int
 // W_k^-1 were left by the factor kernel at the head of the bus's (otherwise unused) inverse slot.
 // nodes: records of 8 ints (bus, parent, slot in Tree::d_sbimg, offset of [Tc | Pb | Qb] in Tree::d_lzimg, m, 0, 0, 0).
 template <int B>
-__device__ __forceinline__ void sleaf_back_batch_body(
-    const int bx_, const int by_, const Model& M, const int* __restrict__ nodes, int b, const int* __restrict__ active, int S_cnt, const double* __restrict__ wall,
-    double* __restrict__ xall, const double* __restrict__ Hall, const double* __restrict__ sbimg, const double* __restrict__ lzimg,
-    const double* __restrict__ Zall, const double* __restrict__ lfS, int s0) {
+__device__ __forceinline__ BatchBus sleaf_back_bus(const int4 r0, const int4 r1, int pslot, int oslot, int b, const double* __restrict__ sbimg,
+                                                   const double* __restrict__ lzimg) {
+    const int m = r1.x;
+    const double* pbm = lzimg + (size_t)r0.w + m * m;           // Pb [b][m]
+    return BatchBus{0, r0.x, r0.y, m, pslot, oslot, sbimg + (size_t)r0.z * SleafImg<B>::SZ, pbm + (size_t)b * m};
+}
+
+// every operand whose address comes from the record alone is requested in one round trip with A(k,parent) and x_parent (the early ones, and
+// W_k^-1 here): the Pb column of the lane's MFMAs, the thread's row of T^-1, S^-1 and w of its harmonics
+template <int B>
+__device__ __forceinline__ void sleaf_back_load_wi(BatchBackIn<B>& I, const BatchBus& U, const BatchLane& L, const Model& M, const double* __restrict__ Zall) {
     constexpr int NT = (B + 16) / 16;
     constexpr size_t CT = (size_t)NT * NT * 256;
-    constexpr int NTR = SleafImg<B>::NTR, KS = SleafImg<B>::KS, KP = SleafImg<B>::KP, H2 = B / 2, QI = (H2 + 15) / 16;
-    constexpr bool QBR = SleafImg<B>::QB_ROWS;
-    const int4* rec = reinterpret_cast<const int4*>(nodes) + 2 * (size_t)bx_;
-    const int4 r0 = rec[0], r1 = rec[1];
-    const int k = r0.x, par = r0.y, m = r1.x;
-    const double* img = sbimg + (size_t)r0.z * SleafImg<B>::SZ;
-    const double* pbm = lzimg + (size_t)r0.w + m * m;           // Pb [b][m]
-    const double* qbm = pbm + (size_t)b * m;                    // Qb [m][b]
-    const int tid = threadIdx.x, lane = tid & 63, lg = lane >> 4, jj = lane & 15;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = M.n, Hn = M.Hn;
-    const int sc = tid >> 4, l16 = tid & 15;
-    const int sl = by_ * LB_SB + sc;
-    const int ss = sl < S_cnt ? (active ? active[sl + s0] : sl + s0) : -1;      // slot -> scenario (active list; -1: frozen / empty slot)
-    const bool live = ss >= 0;
-    const int s = live ? ss : 0;
-    double* xs = xall + (size_t)s * n * B;
-    const double* tk = Zall + ((size_t)s * n + k) * CT;         // T^-1 [10][10] | W_k^-1 [4]
-
-    __shared__ double TT[64 * LBP];                           // v = Wd^-1 t, [row][scenario]
-    __shared__ double V[64 * LBP];
-    __shared__ double RR[16 * LBP];                           // r = Qb v, then y = T^-1 r, [border unknown][scenario]
-    __shared__ double YY[16 * LBP];
-
-    // every operand whose address comes from the record alone is requested here, in one round trip with A(k,parent) and x_parent:
-    // the image column of the lane's MFMAs, the thread's row of T^-1, S^-1 and w of its harmonics
-    double ia[KS], pa[KP], trow[10], w4[QI][2], si4[QI][4];
-    if (wv < NTR) {
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) ia[ks] = img[((size_t)wv * KS + ks) * 64 + lane];
-#pragma unroll
-        for (int kp = 0; kp < KP; ++kp) pa[kp] = img[SleafImg<B>::MAIN + ((size_t)wv * KP + kp) * 64 + lane];
+    const double* tk = Zall + ((size_t)L.s * M.n + U.k) * CT;   // T^-1 [10][10] | W_k^-1 [4]
+    I.wi[0] = I.wi[1] = I.wi[2] = I.wi[3] = 0.0;
+    if (L.live && L.l16 == 0) {                                 // (harmonic 0 belongs to this thread)
+        I.wi[0] = tk[100]; I.wi[1] = tk[101]; I.wi[2] = tk[102]; I.wi[3] = tk[103];
     }
+}
+
+template <int B>
+__device__ __forceinline__ void sleaf_back_load_late(BatchBackIn<B>& I, const BatchBus& U, const BatchLane& L, const Model& M,
+                                                     const double* __restrict__ wall, const double* __restrict__ Zall, const double* __restrict__ lfS) {
+    constexpr int NT = (B + 16) / 16;
+    constexpr size_t CT = (size_t)NT * NT * 256;
+    constexpr int NTR = SleafImg<B>::NTR, KP = SleafImg<B>::KP, H2 = B / 2, QI = (H2 + 15) / 16;
+    const int k = U.k, m = U.m, n = M.n, Hn = M.Hn, s = L.s, l16 = L.l16;
+    const bool live = L.live;
+    const double* tk = Zall + ((size_t)s * n + k) * CT;
 #pragma unroll
-    for (int j = 0; j < 10; ++j) trow[j] = (live && l16 < m && j < m) ? tk[l16 * 10 + j] : 0.0;
+    for (int j = 0; j < 10; ++j) I.tr[j] = (live && l16 < m && j < m) ? tk[l16 * 10 + j] : 0.0;
+    if (L.wv < NTR) {
+#pragma unroll
+        for (int kp = 0; kp < KP; ++kp) I.pa[kp] = U.img[SleafImg<B>::MAIN + ((size_t)L.wv * KP + kp) * 64 + L.lane];
+    }
 #pragma unroll
     for (int it = 0; it < QI; ++it) {
         const int q = l16 + 16 * it;
-        w4[it][0] = w4[it][1] = 0.0;
-        si4[it][0] = si4[it][3] = 1.0;
-        si4[it][1] = si4[it][2] = 0.0;
+        I.w4[it][0] = I.w4[it][1] = 0.0;
+        I.si4[it][0] = I.si4[it][3] = 1.0;
+        I.si4[it][1] = I.si4[it][2] = 0.0;
         if (live && q < H2) {
-            const double2 w2 = *reinterpret_cast<const double2*>(wall + ((size_t)s * n + k) * B + 2 * q);
-            w4[it][0] = w2.x;
-            w4[it][1] = w2.y;
             if (q < Hn) {
                 const double2* sp = reinterpret_cast<const double2*>(lfS + (((size_t)s * n + k) * Hn + q) * 4);
                 const double2 a = sp[0], c2 = sp[1];
-                si4[it][0] = a.x; si4[it][1] = a.y; si4[it][2] = c2.x; si4[it][3] = c2.y;
+                I.si4[it][0] = a.x; I.si4[it][1] = a.y; I.si4[it][2] = c2.x; I.si4[it][3] = c2.y;
             }
+            const double2 w2 = *reinterpret_cast<const double2*>(wall + ((size_t)s * n + k) * B + 2 * q);
+            I.w4[it][0] = w2.x;
+            I.w4[it][1] = w2.y;
         }
     }
-    for (int q = l16; q < 32; q += 16) {
+}
+
+// Compute part, first half (the early operands are free after it): returns the accumulators of V.  TT: v = Wd^-1 t, [row][scenario];
+// RR: r = Qb v, [border unknown][scenario] (16 * LBP)
+template <int B>
+__device__ __forceinline__ d4_t sleaf_back_compute_a(const BatchBackIn<B>& I, const BatchBus& U, const BatchLane& L, const Model& M, int b,
+                                                     const double* xall, double* __restrict__ TT, double* __restrict__ RR, const double2* XS) {
+    constexpr int NTR = SleafImg<B>::NTR, KS = SleafImg<B>::KS;
+    constexpr bool QBR = SleafImg<B>::QB_ROWS;
+    const int m = U.m, lg = L.lg, jj = L.jj, wv = L.wv, sc = L.sc, l16 = L.l16;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int q = l16 + 16 * j;
         double t0 = 0.0, t1 = 0.0;
-        if (live && q < Hn) {
-            const double* hk = Hall + (((size_t)s * n + k) * Hn + q) * 4;
-            const double2 xp = *reinterpret_cast<const double2*>(xs + (size_t)par * B + 2 * q);
-            t0 = fma(hk[1], xp.y, hk[0] * xp.x);
-            t1 = fma(hk[3], xp.y, hk[2] * xp.x);
+        if (L.live && q < M.Hn) {
+            batch_back_t<B>(I, U, L, M, xall, XS, j, t0, t1);
             if (q == 0) {                                       // power rows of a linear bus arrive in polar form: W_k^-1 (identity otherwise)
                 const double a = t0, c2 = t1;
-                t0 = fma(tk[101], c2, tk[100] * a);
-                t1 = fma(tk[103], c2, tk[102] * a);
+                t0 = fma(I.wi[1], c2, I.wi[0] * a);
+                t1 = fma(I.wi[3], c2, I.wi[2] * a);
             }
         }
         TT[(2 * q) * LBP + sc] = t0;
@@ -477,7 +575,7 @@ __device__ __forceinline__ void sleaf_back_batch_body(
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const double bop = TT[(4 * ks + lg) * LBP + jj];
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ia[ks], bop, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(I.ia[ks], bop, acc, 0, 0, 0);
         }
         if (QBR && wv == NTR - 1) {                             // rows B.. of the last row tile: r = Qb v
 #pragma unroll
@@ -490,16 +588,27 @@ __device__ __forceinline__ void sleaf_back_batch_body(
     if (!QBR) {
         double r = 0.0;                                         // r_j = Qb[j][:] v   (thread (scenario, j))
         if (l16 < m) {
-            const double* qr = qbm + (size_t)l16 * b;
+            const double* qr = U.qbm + (size_t)l16 * b;
             for (int col = 0; col < b; ++col) r = fma(qr[col], TT[col * LBP + sc], r);
         }
         RR[l16 * LBP + sc] = r;
     }
+    return acc;
+}
+
+// ... second half.  V [64 * LBP]; YY: y = T^-1 r (16 * LBP); XS: k_back_tail's store of x (slot U.oslot takes the thread's harmonics besides HBM)
+template <int B>
+__device__ __forceinline__ void sleaf_back_compute_b(const BatchBackIn<B>& I, const BatchBus& U, const BatchLane& L, const Model& M, d4_t acc, double* xall,
+                                                     double* __restrict__ V, const double* __restrict__ RR, double* __restrict__ YY, double2* XS) {
+    constexpr int NTR = SleafImg<B>::NTR, KP = SleafImg<B>::KP, H2 = B / 2, QI = (H2 + 15) / 16;
+    const int k = U.k, m = U.m, lg = L.lg, jj = L.jj, wv = L.wv, sc = L.sc, l16 = L.l16;
+    const bool live = L.live;
+    double* xs = xall + (size_t)L.s * M.n * B;
     __syncthreads();
     {
         double y = 0.0;                                         // y_i = T^-1[i][:] r
 #pragma unroll
-        for (int j = 0; j < 10; ++j) y = fma(trow[j], (j < m ? RR[j * LBP + sc] : 0.0), y);
+        for (int j = 0; j < 10; ++j) y = fma(I.tr[j], (j < m ? RR[j * LBP + sc] : 0.0), y);
         YY[l16 * LBP + sc] = (live && l16 < m) ? y : 0.0;
     }
     __syncthreads();
@@ -507,7 +616,7 @@ __device__ __forceinline__ void sleaf_back_batch_body(
 #pragma unroll
         for (int kp = 0; kp < KP; ++kp) {
             const double bop = YY[(4 * kp + lg) * LBP + jj];
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[kp], bop, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(I.pa[kp], bop, acc, 0, 0, 0);
         }
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) V[(16 * wv + 4 * reg + lg) * LBP + jj] = acc[reg];
@@ -519,10 +628,32 @@ __device__ __forceinline__ void sleaf_back_batch_body(
             const int q = l16 + 16 * it;
             if (q >= H2) continue;
             const double x0 = V[(2 * q) * LBP + sc], x1 = V[(2 * q + 1) * LBP + sc];
-            const double d0 = fma(si4[it][1], x1, si4[it][0] * x0), d1 = fma(si4[it][3], x1, si4[it][2] * x0);
-            *reinterpret_cast<double2*>(xs + (size_t)k * B + 2 * q) = double2{w4[it][0] - d0, w4[it][1] - d1};
+            const double d0 = fma(I.si4[it][1], x1, I.si4[it][0] * x0), d1 = fma(I.si4[it][3], x1, I.si4[it][2] * x0);
+            const double2 x2 = double2{I.w4[it][0] - d0, I.w4[it][1] - d1};
+            *reinterpret_cast<double2*>(xs + (size_t)k * B + 2 * q) = x2;
+            if (XS && U.oslot >= 0) XS[((size_t)U.oslot * QI + it) * 256 + L.tid] = x2;
         }
     }
+}
+
+template <int B>
+__device__ __forceinline__ void sleaf_back_batch_body(
+    const int bx_, const int by_, const Model& M, const int* __restrict__ nodes, int b, const int* __restrict__ active, int S_cnt, const double* __restrict__ wall,
+    double* __restrict__ xall, const double* __restrict__ Hall, const double* __restrict__ sbimg, const double* __restrict__ lzimg,
+    const double* __restrict__ Zall, const double* __restrict__ lfS, int s0) {
+    __shared__ double TT[64 * LBP];                           // v = Wd^-1 t, [row][scenario]
+    __shared__ double V[64 * LBP];
+    __shared__ double RR[16 * LBP];                           // r = Qb v, then y = T^-1 r, [border unknown][scenario]
+    __shared__ double YY[16 * LBP];
+    const int4* rec = reinterpret_cast<const int4*>(nodes) + 2 * (size_t)bx_;
+    const BatchLane L = batch_lane(by_, active, S_cnt, s0);
+    const BatchBus U = sleaf_back_bus<B>(rec[0], rec[1], -1, -1, b, sbimg, lzimg);
+    BatchBackIn<B> I;
+    batch_back_load_early<B>(I, U, L, M, xall, Hall);
+    sleaf_back_load_wi<B>(I, U, L, M, Zall);
+    sleaf_back_load_late<B>(I, U, L, M, wall, Zall, lfS);
+    const d4_t acc = sleaf_back_compute_a<B>(I, U, L, M, b, xall, TT, RR, nullptr);
+    sleaf_back_compute_b<B>(I, U, L, M, acc, xall, V, RR, YY, nullptr);
 }
 
 template <int B>
@@ -538,6 +669,84 @@ int launch_sleaf_back_batch(hpf_handle* h, const int* nodes, int count, const in
     const dim3 grid((unsigned)count, (unsigned)((h->cur_S + LB_SB - 1) / LB_SB));
     hipLaunchKernelGGL((k_sleaf_back_batch<B>), grid, dim3(256), 0, h->cur_stream, h->M, nodes, 2 * h->Hn, active, h->cur_S, h->d_w,
                        h->d_x, h->d_H, active_tree(h).d_sbimg, active_tree(h).d_lzimg, h->d_Z, h->d_lfS, h->cur_s0);
+    return launch_status(h);
+}
+
+// Back-sweep tail (HPF_BACKTAIL): every bordered bus and constant-inverse leaf of the batched back sweep in ONE launch -- one workgroup per
+// (family, 16 scenarios) walks the family's members (Tree::tail_*: a bordered bus under a Gauss-Jordan bus, its nested bordered buses, the
+// leaves of any of them; a leaf under a Gauss-Jordan bus alone), each after its parent, with the arithmetic of the two bodies above.  The x of a
+// member with children goes to an LDS slot besides HBM, and its children take x_parent from there instead of waiting for a launch boundary
+// and a round trip; each half of the next member's operands is requested as soon as the current member has used its own (BatchBackIn).
+// A thread reads back from the store exactly the entries it wrote itself (harmonics l16, l16 + 16 of scenario sc), as it would from HBM: the
+// store needs no barrier of its own, and the four work arrays are used as in the bodies, whose barriers keep a member's phases apart -- the
+// first write of the next member (TT) follows the last barrier of the current one, which nothing reads TT behind.
+// recs: [member][4] kind (0 bordered bus, 1 leaf), index of its record in sl_nodes / lf_nodes, slot of x_parent, own slot.
+constexpr int BACK_TAIL_WORK = 2 * 64 * LBP + 2 * 16 * LBP + LB_SB * 2;       // doubles: TT | V | RR | YY | UK
+
+template <int B>
+constexpr int back_tail_lds_bytes() { return 8 * BACK_TAIL_WORK + TAIL_SLOTS * BatchBackIn<B>::QI * 256 * 16; }
+
+template <int B>
+__device__ __forceinline__ BatchBus back_tail_bus(const int4 t, const int* __restrict__ sl_nodes, const int* __restrict__ lf_nodes, int b,
+                                                  const double* __restrict__ sbimg, const double* __restrict__ lzimg, const double* __restrict__ lbimg) {
+    if (t.x == 0) {
+        const int4* rec = reinterpret_cast<const int4*>(sl_nodes) + 2 * (size_t)t.y;
+        return sleaf_back_bus<B>(rec[0], rec[1], t.z, t.w, b, sbimg, lzimg);
+    }
+    return leaf_back_bus<B>(reinterpret_cast<const int4*>(lf_nodes)[t.y], t.z, t.w, lbimg);
+}
+
+template <int B>
+__global__ __launch_bounds__(256) void k_back_tail(
+    Model M, const int* __restrict__ fam_ptr, const int* __restrict__ recs, const int* __restrict__ sl_nodes, const int* __restrict__ lf_nodes, int b,
+    const int* __restrict__ active, int S_cnt, const double* __restrict__ wall, double* xall, const double* __restrict__ Hall,
+    const double* __restrict__ sbimg, const double* __restrict__ lzimg, const double* __restrict__ lbimg, const double* __restrict__ Zall,
+    const double* __restrict__ lfK, const double* __restrict__ lfS, int s0) {
+    __shared__ __attribute__((aligned(16))) double smem[back_tail_lds_bytes<B>() / 8];
+    double* TT = smem;
+    double* V = TT + 64 * LBP;
+    double* RR = V + 64 * LBP;
+    double* YY = RR + 16 * LBP;
+    double* UK = YY + 16 * LBP;
+    double2* XS = reinterpret_cast<double2*>(UK + LB_SB * 2);
+    const int beg = fam_ptr[blockIdx.x], end = fam_ptr[blockIdx.x + 1];
+    if (beg >= end) return;
+    const BatchLane L = batch_lane(blockIdx.y, active, S_cnt, s0);
+    const int4* tr = reinterpret_cast<const int4*>(recs);
+    BatchBus cur = back_tail_bus<B>(tr[beg], sl_nodes, lf_nodes, b, sbimg, lzimg, lbimg), nxt = cur;
+    BatchBackIn<B> I;
+    batch_back_load_early<B>(I, cur, L, M, xall, Hall);
+    if (cur.kind == 0) {
+        sleaf_back_load_wi<B>(I, cur, L, M, Zall);
+        sleaf_back_load_late<B>(I, cur, L, M, wall, Zall, lfS);
+    } else {
+        leaf_back_load_late<B>(I, cur, L, M, wall, lfK, lfS);
+    }
+    for (int i = beg; i < end; ++i) {
+        const bool more = i + 1 < end;
+        if (more) nxt = back_tail_bus<B>(tr[i + 1], sl_nodes, lf_nodes, b, sbimg, lzimg, lbimg);
+        d4_t acc = {0.0, 0.0, 0.0, 0.0};
+        if (cur.kind == 0) acc = sleaf_back_compute_a<B>(I, cur, L, M, b, xall, TT, RR, XS);
+        else leaf_back_compute_a<B>(I, cur, L, M, xall, TT, V, XS);
+        if (more) {
+            batch_back_load_early<B>(I, nxt, L, M, xall, Hall);
+            if (nxt.kind == 0) sleaf_back_load_wi<B>(I, nxt, L, M, Zall);
+        }
+        if (cur.kind == 0) sleaf_back_compute_b<B>(I, cur, L, M, acc, xall, V, RR, YY, XS);
+        else leaf_back_compute_b<B>(I, cur, L, M, xall, TT, V, UK);
+        if (more) {
+            if (nxt.kind == 0) sleaf_back_load_late<B>(I, nxt, L, M, wall, Zall, lfS);
+            else leaf_back_load_late<B>(I, nxt, L, M, wall, lfK, lfS);
+        }
+        cur = nxt;
+    }
+}
+
+template <int B>
+int launch_back_tail(hpf_handle* h, const Tree& tr, const int* active) {
+    const dim3 grid((unsigned)tr.n_tail_fam, (unsigned)((h->cur_S + LB_SB - 1) / LB_SB));
+    hipLaunchKernelGGL((k_back_tail<B>), grid, dim3(256), 0, h->cur_stream, h->M, tr.d_tail_ptr, tr.d_tail_rec, tr.d_bsleaf, tr.d_bleaf, 2 * h->Hn,
+                       active, h->cur_S, h->d_w, h->d_x, h->d_H, tr.d_sbimg, tr.d_lzimg, tr.d_lbimg, h->d_Z, h->d_lfK, h->d_lfS, h->cur_s0);
     return launch_status(h);
 }
 

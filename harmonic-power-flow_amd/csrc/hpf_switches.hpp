@@ -26,6 +26,8 @@ struct Switches {
     int back_walk_min = 16;           // HPF_BACKWALK_MIN: smallest scenario group that takes the tree walk (at 1 - 4 its serial per-bus steps lose
                                       // ~8 % of the step to the few short depth launches; at 16 the two tie)
     int back_walk_max = 256;          // HPF_BACKWALK_MAX: largest scenario group that takes the tree walk (measured up to 256: a tie above 32)
+    bool back_tail = true;            // HPF_BACKTAIL=0: the batched back sweep behind the walk in one launch per nesting order of the bordered buses and one for
+                                      // the leaves instead of one launch that walks their families (k_back_tail)
     int border_slot_cap = 1024;       // HPF_BORDER_SLOTS: cap of the virtual scenario slots of a meshed handle's bordered step
     // the tree planner
     bool lintree = true;              // HPF_LINTREE=0: the 2x2 algebra of the linear subtrees in one launch per height
@@ -82,6 +84,7 @@ inline Switches parse_switches(const char* options, bool env_opt_in) {
     flag("HPF_BACKWALK", s.back_walk);
     integer("HPF_BACKWALK_MIN", s.back_walk_min);
     integer("HPF_BACKWALK_MAX", s.back_walk_max);
+    flag("HPF_BACKTAIL", s.back_tail);
     integer("HPF_BORDER_SLOTS", s.border_slot_cap);
     flag("HPF_LINTREE", s.lintree);
     flag("HPF_LINBUNDLE", s.linbundle);

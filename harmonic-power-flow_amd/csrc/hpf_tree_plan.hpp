@@ -1472,7 +1472,7 @@ static void put_bsleaf(const PlanWork& W, int kb, std::vector<int>& v) {
 }
 
 // Phase: back-sweep batch records.  Consumes the depth lists, W.bdesc, W.sb_ord / sb_m / sl_off / sl_nest / lz_idx, W.sl_base.  Produces W.bsleaf
-// (T.bsleaf_ptr, T.n_bsleaf), W.bsd (T.bsl_dep_ptr), W.bleaf (T.bleaf_dep_ptr, T.n_bleaf).
+// (T.bsleaf_ptr, T.n_bsleaf), W.bsd (T.bsl_dep_ptr), W.bleaf (T.bleaf_dep_ptr, T.n_bleaf), T.tail_ptr / tail_rec (T.n_tail_fam).
 static void plan_back_batches(Tree& T, PlanWork& W) {
     const int n = W.n;
     const std::vector<int>&sb_ord = W.sb_ord, &sl_nest = W.sl_nest, &lz_idx = W.lz_idx, &bdesc = W.bdesc;
@@ -1508,6 +1508,53 @@ static void plan_back_batches(Tree& T, PlanWork& W) {
         T.bleaf_dep_ptr.push_back((int)bleaf.size() / 4);
     }
     T.n_bleaf = (int)bleaf.size() / 4;
+    // the same records in families (k_back_tail): a batched bus needs the x of its dense parent only; where that parent is batched too (a
+    // bordered bus), the two belong to one family, whose workgroup keeps the parent's x in LDS.  Members in depth-first order -- a bus, its
+    // leaves, then its nested bordered buses with theirs --; the x of a bus with children keeps one of the TAIL_SLOTS slots of the LDS store until
+    // its last child has read it, and the children of a bus that found no free slot read it from HBM (-2).
+    T.tail_ptr.assign(1, 0);
+    T.tail_rec.clear();
+    {
+        std::vector<int> sl_rec(n, -1), lf_rec(n, -1);
+        for (int i = 0; i < T.n_bsleaf; ++i) sl_rec[bsleaf[(size_t)i * 8]] = i;
+        for (int i = 0; i < T.n_bleaf; ++i) lf_rec[bleaf[(size_t)i * 4]] = i;
+        std::vector<std::vector<int>> kids(n);              // batched children of a bordered bus: leaves first, then bordered buses, each in depth order
+        std::vector<int> roots;
+        for (int pass = 0; pass < 2; ++pass)
+            for (int pos = 0; pos < T.n_dense; ++pos) {
+                const int kb = T.dep_nodes[pos];
+                if ((pass == 0 ? lf_rec[kb] : sl_rec[kb]) < 0) continue;
+                const int p = W.pard[kb];
+                if (p >= 0 && sl_rec[p] >= 0) kids[p].push_back(kb);
+                else roots.push_back(kb);
+            }
+        std::vector<std::vector<int>> fams;
+        bool slot_used[TAIL_SLOTS];
+        std::function<void(std::vector<int>&, int, int)> emit = [&](std::vector<int>& fam, int kb, int ps) {
+            int own = -1;                                   // a slot for the x of a bus with children, while one is free
+            for (int sl = 0; sl < TAIL_SLOTS && own < 0 && !kids[kb].empty(); ++sl)
+                if (!slot_used[sl]) own = sl;
+            if (own >= 0) slot_used[own] = true;
+            const int rec[4] = {sl_rec[kb] >= 0 ? 0 : 1, sl_rec[kb] >= 0 ? sl_rec[kb] : lf_rec[kb], ps, own};
+            fam.insert(fam.end(), rec, rec + 4);
+            for (size_t ci = 0; ci < kids[kb].size(); ++ci) {
+                // (the last child reads the slot before it writes its own x: it may take the very slot over)
+                if (own >= 0 && ci + 1 == kids[kb].size()) slot_used[own] = false;
+                emit(fam, kids[kb][ci], own >= 0 ? own : -2);
+            }
+        };
+        for (int root : roots) {
+            for (bool& u : slot_used) u = false;
+            fams.emplace_back();
+            emit(fams.back(), root, -1);
+        }
+        std::stable_sort(fams.begin(), fams.end(), [](const std::vector<int>& a, const std::vector<int>& b2) { return a.size() > b2.size(); });
+        for (const auto& fam : fams) {
+            T.tail_rec.insert(T.tail_rec.end(), fam.begin(), fam.end());
+            T.tail_ptr.push_back((int)T.tail_rec.size() / 4);
+        }
+        T.n_tail_fam = (int)fams.size();
+    }
 }
 
 // Phase: census and flop / byte model.  Consumes the bus kinds, the final levels and dense-children lists.  Produces T.census, T.flops_*,
@@ -1650,6 +1697,22 @@ static void plan_report(hpf_handle* h, const hpf_desc& d, const Switches& sw, co
                 }
                 for (int i = 0; i < T.n_comp; ++i) fprintf(fp, "# walk_comp %d %d\n", T.comp_v[i], T.comp_c[i]);
             }
+            if (T.n_bsleaf + T.n_bleaf > 0) {       // the back sweep's batch records (bus ids in record order) and their families: bus:parent's slot:own slot
+                fprintf(fp, "# tail: %d families, %d slots\n", T.n_tail_fam, TAIL_SLOTS);
+                fprintf(fp, "# tail_bsleaf");
+                for (int i = 0; i < T.n_bsleaf; ++i) fprintf(fp, " %d", W.bsleaf[(size_t)i * 8]);
+                fprintf(fp, "\n# tail_bleaf");
+                for (int i = 0; i < T.n_bleaf; ++i) fprintf(fp, " %d", W.bleaf[(size_t)i * 4]);
+                fprintf(fp, "\n");
+                for (int f = 0; f < T.n_tail_fam; ++f) {
+                    fprintf(fp, "# tail_family %d", f);
+                    for (int i = T.tail_ptr[f]; i < T.tail_ptr[f + 1]; ++i) {
+                        const int* r4 = &T.tail_rec[(size_t)i * 4];
+                        fprintf(fp, " %d:%d:%d", r4[0] ? W.bleaf[(size_t)r4[1] * 4] : W.bsleaf[(size_t)r4[1] * 8], r4[2], r4[3]);
+                    }
+                    fprintf(fp, "\n");
+                }
+            }
             for (int pos = 0; pos < T.n_dense; ++pos) {
                 const int k = T.lvl_nodes[pos];
                 const int kind = cleaf_of[k] >= 0 ? 1 : ((sl_off[k] >= 0 && lz_idx[k] >= 0) ? 2 : 0);
@@ -1701,6 +1764,8 @@ static int plan_upload(hpf_handle* h, Tree& T, const PlanWork& W) {
     up(&T.d_walk_ptr, T.walk_ptr);
     up(&T.d_walk_rec, T.walk_rec);
     up(&T.d_walk_slot, T.walk_slot);
+    up(&T.d_tail_ptr, T.tail_ptr);
+    up(&T.d_tail_rec, T.tail_rec);
     up(&T.d_chain_ptr, T.chain_ptr);
     up(&T.d_chain_nodes, T.chain_nodes);
     up(&T.d_chain_ch, T.chain_ch);

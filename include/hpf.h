@@ -448,6 +448,9 @@ int  hpf_debug_stamps(hpf_handle* h, long long* out, int count);
  * HPF_BACKWALK=0 runs the back sweep's Gauss-Jordan buses in one launch per depth instead of two tree walks (k_back_walk: the trunk,
  * then up to 8 subtree lists, one workgroup per list and scenario; blocks of 52, groups of HPF_BACKWALK_MIN = 16 to HPF_BACKWALK_MAX = 256
  * scenarios: groups of 1 - 4 run faster on the depth launches; the batched workgroups follow the walk),
+ * HPF_BACKTAIL=0 runs those batched workgroups, wherever they follow the Gauss-Jordan buses, in one launch per nesting order of the bordered
+ * buses and one for the leaves instead of one launch (k_back_tail: one workgroup per family -- a bordered bus under a Gauss-Jordan bus, its nested
+ * bordered buses and their leaves -- and 16 scenarios, the x of a member's parent kept in LDS),
  * HPF_GROUPS=n presets "scenario_groups".  Every switch selects a path with the same Newton steps (tests/test_gpu_robustness.py). */
 int  hpf_set_option(hpf_handle* h, const char* name, int value);
 
@@ -500,7 +503,8 @@ int  hpf_kernel_model(const hpf_handle* h, int which, double* bytes, double* flo
  * [12] border unknowns of a meshed network (2 Hn x distinct endpoint buses of the loop-closing lines), [13] buses on the endpoints' root paths
  * (kept as plain Gauss-Jordan buses by the factor-once bordered step; 0: virtual-sweep form), [14] form of the bordered step: 0 virtual sweeps,
  * 1 factor-once with rocSOLVER's LU of the border system, 2 factor-once with the block Gauss-Jordan solve, [15] back sweeps (scenario group x
- * Newton step) since hpf_create whose Gauss-Jordan buses went through the tree walk (HPF_BACKWALK).
+ * Newton step) since hpf_create whose Gauss-Jordan buses went through the tree walk (HPF_BACKWALK), [16] back sweeps since hpf_create whose
+ * bordered buses and constant-inverse leaves went through one launch that walks their families (k_back_tail, HPF_BACKTAIL).
  * HPF_E_STATE for DENSE. */
 int  hpf_tree_census(const hpf_handle* h, int* counts, int n_counts);
 /* Wall-clock milliseconds hpf_create spent: ms[0] total, [1] planning the elimination trees on the host (classification of the buses,

@@ -82,6 +82,7 @@ SYMBOLS = {
     "hpf_clear_sources": (C.c_int, [_H]),
     "hpf_queue_sources": (C.c_int, [_H, C.c_int, C.c_int, c_dbl_p, c_int_p]),
     "hpf_debug_stamps": (C.c_int, [_H, C.POINTER(C.c_longlong), C.c_int]),
+    "hpf_debug_device_memory": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "hpf_set_option": (C.c_int, [_H, C.c_char_p, C.c_int]),
     "hpf_set_stream": (C.c_int, [_H, C.c_void_p]),
     "hpf_sync": (C.c_int, [_H]),

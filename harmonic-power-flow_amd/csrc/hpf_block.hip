@@ -806,24 +806,6 @@ int launch_level(hpf_handle* h, const TreeDev& T, const int* nodes, int kind, in
 // Gauss-Jordan kernel only -- no constant-inverse leaves / lazy leaves / super-leaves there yet); 0: the 256-thread generic kernels
 int wave_block_size(int b) { return b <= 12 ? 12 : (b <= 28 ? 28 : (b <= 52 ? 52 : (b <= 100 ? 100 : 0))); }
 
-template <class T>
-int upload(hpf_handle* h, T** dst, const std::vector<T>& v) {
-    const size_t cnt = v.empty() ? 1 : v.size();
-    hipError_t e = hipMalloc((void**)dst, cnt * sizeof(T));
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        return e == hipErrorOutOfMemory ? HPF_E_NOMEM : HPF_E_HIP;
-    }
-    if (!v.empty()) {
-        e = hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            h->last_detail = (int)e;
-            return HPF_E_HIP;
-        }
-    }
-    return HPF_OK;
-}
-
 size_t factor_lds_bytes(int b) { return gj_dense_lds_bytes(b); }
 
 template <int R>
@@ -1028,16 +1010,6 @@ __global__ __launch_bounds__(256) void k_border_finish(int count, int r, int v0,
 
 }  // namespace
 
-namespace hpf {
-
-// frees what tree_upload allocated for the tree
-static void tree_free_one(Tree& T) {
-    for (void* p : T.d_owned) hipFree(p);
-    T.d_owned.clear();
-}
-
-}  // namespace hpf
-
 #include "hpf_tree_plan.hpp"      // the host-side planner: tree_build_into, tree_plan_dump, tree_build
 
 namespace hpf {
@@ -1073,43 +1045,22 @@ bool tree_levels_fused(hpf_handle* h) {
 // the tree the Newton step of the current mode runs on
 Tree& active_tree(hpf_handle* h) { return (h->has_ctree && h->gj_mode == 1) ? h->ctree : h->tree; }
 
-void tree_free(hpf_handle* h) {
-    tree_free_one(h->tree);
-    tree_free_one(h->ctree);
-    void* bp[] = {h->d_tb_bus, h->d_tb_ptr, h->d_tb_adj, h->d_bM, h->d_brhs, h->d_bipiv, h->d_binfo, h->d_bM0, h->d_brhs0,
-                  h->d_sel_P, h->d_sel_pidx, h->d_sel_toff, h->d_sel_S, h->d_sel_Z, h->d_sel_Up, h->d_sel_W, h->d_sel_X, h->d_sel_tie, h->d_sel_jobs,
-                  h->d_sel_hl, h->d_sel_slot, h->d_sel_cptr, h->d_sel_clist, h->d_sel_dw, h->d_bB, h->d_bgj_jobs,
-                  h->d_sel_bM, h->d_sel_rhs, h->d_sel_g, h->d_sel_res, h->d_sel_info};
-    for (void* q2 : bp)
-        if (q2) hipFree(q2);
-}
-
 int tree_alloc_scenarios(hpf_handle* h) {
     const int bw = wave_block_size(2 * h->Hn);
     const size_t b = bw ? (size_t)bw : 2 * (size_t)h->Hn, S = h->S_alloc, n = h->n;
-    hipError_t e;
     const size_t ct = bw ? (size_t)(((bw + 16) / 16) * ((bw + 16) / 16) * 256) : 0;     // accumulator-tile image of a block
-    if ((e = hipMalloc((void**)&h->d_Z, sizeof(double) * S * n * (b * b > ct ? b * b : ct))) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_w, sizeof(double) * S * n * b)) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_x, sizeof(double) * S * n * b)) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_linA, sizeof(double) * S * n * (size_t)h->Hn * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_H, sizeof(double) * S * n * (size_t)h->Hn * 4)) != hipSuccess ||
-        (e = hipMalloc((void**)&h->d_fb, sizeof(double) * S * n * b)) != hipSuccess ||
-        (h->has_ctree && ((e = hipMalloc((void**)&h->d_chG, sizeof(double) * S * n * (size_t)h->Hn * 4)) != hipSuccess ||
-                          (e = hipMalloc((void**)&h->d_chH, sizeof(double) * S * n * (size_t)h->Hn * 4)) != hipSuccess ||
-                          (e = hipMalloc((void**)&h->d_chD, sizeof(double) * S * n * (size_t)h->Hn * 4)) != hipSuccess ||
-                          (e = hipMalloc((void**)&h->d_chy, sizeof(double) * S * n * (size_t)h->Hn * 2)) != hipSuccess ||
-                          (e = hipMalloc((void**)&h->d_chZ, sizeof(double) * S * n * (size_t)h->Hn * 4)) != hipSuccess ||
-                          (e = hipMalloc((void**)&h->d_lfK, sizeof(double) * S * n * 12)) != hipSuccess ||
-                          (e = hipMalloc((void**)&h->d_lfS, sizeof(double) * S * n * (size_t)h->Hn * 4)) != hipSuccess)) ||
-        ((h->sw.debug_ablate & 16) && (e = hipMalloc((void**)&h->d_dbg, sizeof(long long) * S * n * 8)) != hipSuccess) ||
-        (bw && (e = hipMalloc((void**)&h->d_C, sizeof(double) * S * n * (size_t)(((bw + 16) / 16) * ((bw + 16) / 16) * 256))) != hipSuccess) ||
+    const size_t h4 = S * n * (size_t)h->Hn * 4;
+    DevMem& mem = h->mem;
+    int r;
+    if ((r = mem.alloc(&h->d_Z, S * n * (b * b > ct ? b * b : ct))) || (r = mem.alloc(&h->d_w, S * n * b)) || (r = mem.alloc(&h->d_x, S * n * b)) ||
+        (r = mem.alloc(&h->d_linA, h4)) || (r = mem.alloc(&h->d_H, h4)) || (r = mem.alloc(&h->d_fb, S * n * b)) ||
+        (h->has_ctree && ((r = mem.alloc(&h->d_chG, h4)) || (r = mem.alloc(&h->d_chH, h4)) || (r = mem.alloc(&h->d_chD, h4)) ||
+                          (r = mem.alloc(&h->d_chy, S * n * (size_t)h->Hn * 2)) || (r = mem.alloc(&h->d_chZ, h4)) ||
+                          (r = mem.alloc(&h->d_lfK, S * n * 12)) || (r = mem.alloc(&h->d_lfS, h4)))) ||
+        ((h->sw.debug_ablate & 16) && (r = mem.alloc(&h->d_dbg, S * n * 8))) || (bw && (r = mem.alloc(&h->d_C, S * n * ct))) ||
         (h->has_ctree && h->ctree.n_comp > 0 &&
-         ((e = hipMalloc((void**)&h->d_F, sizeof(double) * S * (size_t)h->ctree.n_comp * 3 * ct)) != hipSuccess ||
-          (e = hipMalloc((void**)&h->d_H2, sizeof(double) * S * (size_t)h->ctree.n_comp * (size_t)h->Hn * 4)) != hipSuccess))) {
-        h->last_detail = (int)e;
-        return e == hipErrorOutOfMemory ? HPF_E_NOMEM : HPF_E_HIP;
-    }
+         ((r = mem.alloc(&h->d_F, S * (size_t)h->ctree.n_comp * 3 * ct)) || (r = mem.alloc(&h->d_H2, S * (size_t)h->ctree.n_comp * (size_t)h->Hn * 4)))))
+        return r;
     if (h->d_dbg) hipMemset(h->d_dbg, 0, sizeof(long long) * S * n * 8);
     return HPF_OK;
 }
@@ -1486,14 +1437,12 @@ int tree_find_ties(hpf_handle* h, const hpf_desc* d) {
     }
     if (h->plan_only) return HPF_OK;                     // (hpf_tree_plan: the host side alone -- ties, endpoint buses, the planner's mask)
     int r;
-    if ((r = upload(h, &h->d_tb_bus, tb_bus))) return r;
-    if ((r = upload(h, &h->d_tb_ptr, tb_ptr))) return r;
-    if ((r = upload(h, &h->d_tb_adj, tb_adj))) return r;
+    DevMem& mem = h->mem;
     const size_t m = (size_t)h->m_border;
-    if (hipMalloc((void**)&h->d_bM, sizeof(double) * m * m) != hipSuccess || hipMalloc((void**)&h->d_brhs, sizeof(double) * m) != hipSuccess ||
-        hipMalloc((void**)&h->d_bipiv, sizeof(int) * m) != hipSuccess || hipMalloc((void**)&h->d_binfo, sizeof(int)) != hipSuccess ||
-        hipMalloc((void**)&h->d_bM0, sizeof(double) * m * m) != hipSuccess || hipMalloc((void**)&h->d_brhs0, sizeof(double) * (2 * m + 2)) != hipSuccess)
-        return HPF_E_NOMEM;
+    if ((r = mem.upload(&h->d_tb_bus, tb_bus)) || (r = mem.upload(&h->d_tb_ptr, tb_ptr)) || (r = mem.upload(&h->d_tb_adj, tb_adj)) ||
+        (r = mem.alloc(&h->d_bM, m * m)) || (r = mem.alloc(&h->d_brhs, m)) || (r = mem.alloc(&h->d_bipiv, m)) || (r = mem.alloc(&h->d_binfo, 1)) ||
+        (r = mem.alloc(&h->d_bM0, m * m)) || (r = mem.alloc(&h->d_brhs0, 2 * m + 2)))
+        return r;
     return HPF_OK;
 }
 
@@ -1823,10 +1772,9 @@ int tree_sel_build(hpf_handle* h, const hpf_desc* d) {
         std::vector<int> pos(cptr.begin(), cptr.end() - 1);
         for (size_t q = 1; q < nP; ++q) clist[pos[pidx[T.parent[Pbus[q]]]]++] = (int)q;
         int r2;
-        if ((r2 = upload(h, &h->d_sel_hl, byh))) return r2;
-        if ((r2 = upload(h, &h->d_sel_slot, slot))) return r2;
-        if ((r2 = upload(h, &h->d_sel_cptr, cptr))) return r2;
-        if ((r2 = upload(h, &h->d_sel_clist, clist))) return r2;
+        if ((r2 = h->mem.upload(&h->d_sel_hl, byh)) || (r2 = h->mem.upload(&h->d_sel_slot, slot)) || (r2 = h->mem.upload(&h->d_sel_cptr, cptr)) ||
+            (r2 = h->mem.upload(&h->d_sel_clist, clist)))
+            return r2;
     }
     h->sel_nP = (int)nP;
     h->sel_npairs = (int)npairs;
@@ -1848,19 +1796,16 @@ int tree_sel_build(hpf_handle* h, const hpf_desc* d) {
     const size_t cap = (size_t)h->sel_cap;
     h->sel_res_host.assign(2 * cap, 0ull);
     h->sel_info_host.assign(cap, 0);
-    if (hipMalloc((void**)&h->d_sel_dw, sizeof(double) * cap * nP * b) != hipSuccess) return HPF_E_NOMEM;
-    auto dalloc = [&](double** p2, size_t cnt) { return hipMalloc((void**)p2, sizeof(double) * (cnt ? cnt : 1)) == hipSuccess; };
-    if (!dalloc(&h->d_sel_S, cap * nP * bb) || !dalloc(&h->d_sel_Z, cap * nP * bb) || !dalloc(&h->d_sel_Up, cap * nP * bb) ||
-        !dalloc(&h->d_sel_W, cap * npairs * bb) || !dalloc(&h->d_sel_X, cap * nP * (size_t)mT * bb) ||
-        !dalloc(&h->d_sel_tie, cap * 2 * h->n_ties * h->Hn * 4) || !dalloc(&h->d_sel_bM, cap * mb * mb) || !dalloc(&h->d_sel_rhs, cap * mb) ||
-        !dalloc(&h->d_sel_g, cap * mb) || hipMalloc((void**)&h->d_sel_res, sizeof(unsigned long long) * 2 * cap) != hipSuccess ||
-        hipMalloc((void**)&h->d_sel_info, sizeof(int) * cap) != hipSuccess)
-        return HPF_E_NOMEM;
-    const long long sS = (long long)(nP * bb), sW = (long long)(npairs * bb), sX = (long long)(nP * (size_t)mT * bb);
+    DevMem& mem = h->mem;
     int r;
-    if ((r = upload(h, &h->d_sel_P, Prec))) return r;
-    if ((r = upload(h, &h->d_sel_pidx, pidx))) return r;
-    if ((r = upload(h, &h->d_sel_toff, T.toff_tab))) return r;
+    if ((r = mem.alloc(&h->d_sel_dw, cap * nP * b)) || (r = mem.alloc(&h->d_sel_S, cap * nP * bb)) || (r = mem.alloc(&h->d_sel_Z, cap * nP * bb)) ||
+        (r = mem.alloc(&h->d_sel_Up, cap * nP * bb)) || (r = mem.alloc(&h->d_sel_W, cap * npairs * bb)) ||
+        (r = mem.alloc(&h->d_sel_X, cap * nP * (size_t)mT * bb)) || (r = mem.alloc(&h->d_sel_tie, cap * 2 * h->n_ties * h->Hn * 4)) ||
+        (r = mem.alloc(&h->d_sel_bM, cap * mb * mb)) || (r = mem.alloc(&h->d_sel_rhs, cap * mb)) || (r = mem.alloc(&h->d_sel_g, cap * mb)) ||
+        (r = mem.alloc(&h->d_sel_res, 2 * cap)) || (r = mem.alloc(&h->d_sel_info, cap)) || (r = mem.upload(&h->d_sel_P, Prec)) ||
+        (r = mem.upload(&h->d_sel_pidx, pidx)) || (r = mem.upload(&h->d_sel_toff, T.toff_tab)))
+        return r;
+    const long long sS = (long long)(nP * bb), sW = (long long)(npairs * bb), sX = (long long)(nP * (size_t)mT * bb);
     std::vector<BlkJob> jobs;
     jobs.reserve(npairs + nP * (size_t)mT);
     h->sel_fwd_beg.assign(1, 0);
@@ -1896,8 +1841,7 @@ int tree_sel_build(hpf_handle* h, const hpf_desc* d) {
             h->sel_back_beg.push_back(jobs.size());
         }
     }
-    if (hipMalloc(&h->d_sel_jobs, sizeof(BlkJob) * (jobs.size() ? jobs.size() : 1)) != hipSuccess) return HPF_E_NOMEM;
-    if (hipMemcpy(h->d_sel_jobs, jobs.data(), sizeof(BlkJob) * jobs.size(), hipMemcpyHostToDevice) != hipSuccess) return HPF_E_HIP;
+    if ((r = mem.upload((BlkJob**)&h->d_sel_jobs, jobs))) return r;
     // Border systems of up to HPF_BORDER_GJ blocks (default 96) are solved by a block Gauss-Jordan elimination on the b x b grid with the block-product
     // kernel instead of rocSOLVER's unpivoted LU (hundreds of small launches at these sizes): step k inverts block (k, k) in place on the matrix
     // cores (k_blk_invert_mfma: static 4 x 4 pivot blocks under the same watch as the tree's; the residual check and the pivoted rocSOLVER
@@ -1906,7 +1850,7 @@ int tree_sel_build(hpf_handle* h, const hpf_desc* d) {
     // per Newton step against 2.2 / 5.7 / 11.7 / 31 ms with rocSOLVER (1.5 x the flops of an LU, block products at ~2 TFLOP/s).
     if (h->border_gj) {
         const size_t W = (size_t)mT + 1;
-        if (!dalloc(&h->d_bB, cap * (size_t)mT * W * bb)) return HPF_E_NOMEM;
+        if ((r = mem.alloc(&h->d_bB, cap * (size_t)mT * W * bb))) return r;
         const long long sB = (long long)((size_t)mT * W * bb);
         std::vector<BlkJob> gj;
         h->bgj_beg.assign(1, 0);
@@ -1919,8 +1863,7 @@ int tree_sel_build(hpf_handle* h, const hpf_desc* d) {
                     for (size_t t2 = k + 1; t2 < W; ++t2) gj.push_back({blk(i, k), blk(k, t2), blk(i, t2), blk(i, t2), -1.0, sB, sB, sB, sB});
             h->bgj_beg.push_back(gj.size());
         }
-        if (hipMalloc(&h->d_bgj_jobs, sizeof(BlkJob) * (gj.size() ? gj.size() : 1)) != hipSuccess) return HPF_E_NOMEM;
-        if (hipMemcpy(h->d_bgj_jobs, gj.data(), sizeof(BlkJob) * gj.size(), hipMemcpyHostToDevice) != hipSuccess) return HPF_E_HIP;
+        if ((r = mem.upload((BlkJob**)&h->d_bgj_jobs, gj))) return r;
     }
     if (h->sw.tree_info)
         fprintf(stderr, "hpf tree: factor-once bordered step: %d ties, %d endpoint buses (border %d), %zu buses on their root paths, %zu forward pairs, "

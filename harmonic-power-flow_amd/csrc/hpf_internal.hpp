@@ -12,9 +12,19 @@
 
 #include "../../include/hpf.h"
 #include "hpf_assembly.hpp"
+#include "hpf_devmem.hpp"
 #include "hpf_switches.hpp"
 
 namespace hpf {
+
+// device blocks come from hipMalloc (hpf_devmem.hpp: the one place that allocates and frees them)
+struct HipBackend {
+    static constexpr int oom = (int)hipErrorOutOfMemory;
+    static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static int free(void* p) { return (int)hipFree(p); }
+    static int copy_in(void* dst, const void* src, size_t bytes) { return (int)hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }
+};
+using DevMem = DevOwner<HipBackend>;
 
 // form of the 2x2 algebra of the all-linear subtrees in a block-tree Newton step (Tree::lin_form, decided by the planner)
 enum LinForm {
@@ -163,7 +173,6 @@ struct Tree {
     std::vector<int> tail_rec;        // [][4]
     int* d_tail_ptr = nullptr;
     int* d_tail_rec = nullptr;
-    std::vector<void*> d_owned;       // every device array above, as tree_upload allocated it: what tree_free_one frees
     double plan_ms = 0.0;             // host time of tree_build_into up to the uploads (all planning, the back-sweep batch records included)
     double flops_per_solve = 0.0;     // factor sweep + back sweep
     double flops_factor = 0.0;        // factor sweep only (k_tree_factor, all levels)
@@ -360,6 +369,20 @@ struct hpf_handle {
     static constexpr int TS_CAP = 16384;         // launches of the general factor kernel a timing leg can stamp
     unsigned long long* d_tstamp = nullptr;      // [TS_CAP][2] first workgroup start / last workgroup end (wall_clock64) per launch
     int ts_next = 0;
+
+    // Owners of every device block above (hpf_devmem.hpp; declared last: they go first, and null the pointers they hold).  What lives as long as
+    // the handle is in `mem`; buffers that come and go share one owner per group, allocated all-or-nothing and released by its clear().
+    hpf::DevMem mem{&last_detail};        // model, per-scenario state, both trees, tree scratch, mesh / selected inversion / border, stamps, CSR export, swap, d_hist
+    hpf::DevMem dist_mem{&last_detail};   // d_dist_*
+    hpf::DevMem bstat_mem{&last_detail};  // d_bs_*
+    hpf::DevMem br_mem{&last_detail};     // d_br_*
+    hpf::DevMem start_mem{&last_detail};  // d_sVm, d_sVa, d_sU, d_sE
+    hpf::DevMem src_mem{&last_detail};    // d_src
+    hpf::DevMem qsrc_mem{&last_detail};   // d_qsrc, d_qorders
+    hpf::DevMem repeat_mem{&last_detail}; // d_Vm0, d_Va0, d_mask
+    hpf::DevMem prev_mem{&last_detail};   // d_Vmp, d_Vap
+    hpf::DevMem resid_mem{&last_detail};  // d_respart, d_eta
+    hpf::DevMem dense_mem{&last_detail};  // d_J, d_ipiv, d_info
 };
 
 namespace hpf {
@@ -401,7 +424,6 @@ int tree_build(hpf_handle* h, const hpf_desc* d);
 int tree_plan_dump(const hpf_desc* d, const char* path);  // host-only planning run (hpf_tree_plan), no device touched
 hpf::Tree& active_tree(hpf_handle* h);
 bool tree_levels_fused(hpf_handle* h);                   // every elimination level of the current mode is one k_level launch
-void tree_free(hpf_handle* h);
 int tree_alloc_scenarios(hpf_handle* h);
 int tree_fund_step(hpf_handle* h, bool only_active);     // fundamental pf Newton step on the tree (2x2 blocks)
 int tree_newton_step(hpf_handle* h, bool only_active);   // assembles, eliminates, back-substitutes -> d_f holds the step

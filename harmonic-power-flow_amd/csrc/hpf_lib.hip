@@ -1225,45 +1225,21 @@ __global__ void k_queue_keep_seed(int n, int Hn, int g0, const double* __restric
 // ------------------------------------------------------------------------------------------------------------
 namespace {
 
-template <class T>
-int dev_alloc(hpf_handle* h, T** p, size_t count) {
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-    if (e != hipSuccess) {
-        h->last_detail = (int)e;
-        *p = nullptr;
-        return e == hipErrorOutOfMemory ? HPF_E_NOMEM : HPF_E_HIP;
-    }
-    return HPF_OK;
-}
-
-template <class T>
-int dev_upload(hpf_handle* h, T** p, const T* src, size_t count) {
-    int r = dev_alloc(h, p, count);
-    if (r) return r;
-    if (count) HIPCHK(hipMemcpy(*p, src, count * sizeof(T), hipMemcpyHostToDevice));
-    return HPF_OK;
-}
-
 inline dim3 grid2(int count, int S) { return dim3((unsigned)((count + TPB - 1) / TPB), (unsigned)S, 1); }
 
 int ensure_dense(hpf_handle* h, int Nsys) {
     size_t want = (size_t)Nsys * Nsys;                         // (N * N >= 2^31: rocSOLVER's 64-bit entry points, dense_solve)
     if (h->solver == HPF_SOLVER_DENSE && (size_t)h->N * h->N > want) want = (size_t)h->N * h->N;
     if (h->d_J && h->J_elems_per_scen >= want) return HPF_OK;
-    if (h->d_J) {
-        hipFree(h->d_J);
-        hipFree(h->d_ipiv);
-        hipFree(h->d_info);
-        h->d_J = nullptr;
-        h->d_ipiv = nullptr;
-        h->d_info = nullptr;
-    }
-    int r = dev_alloc(h, &h->d_J, want * (size_t)h->S_max);
-    if (r) return r;
+    h->dense_mem.clear();
     const int Nmax = h->N > h->Nf ? h->N : h->Nf;
-    if ((r = dev_alloc(h, &h->d_ipiv, 2 * (size_t)Nmax * h->S_max))) return r;       // (room for the int64 pivots of the 64-bit path)
-    if ((r = dev_alloc(h, &h->d_info, 2 * (size_t)h->S_max))) return r;
+    int r;
+    if ((r = h->dense_mem.alloc(&h->d_J, want * (size_t)h->S_max)) ||
+        (r = h->dense_mem.alloc(&h->d_ipiv, 2 * (size_t)Nmax * h->S_max)) ||          // (room for the int64 pivots of the 64-bit path)
+        (r = h->dense_mem.alloc(&h->d_info, 2 * (size_t)h->S_max))) {
+        h->dense_mem.clear();
+        return r;
+    }
     HIPCHK(hipMemset(h->d_info, 0, sizeof(int) * 2 * h->S_max));
     h->J_elems_per_scen = want;
     return HPF_OK;
@@ -1685,22 +1661,12 @@ int distortion_launch(hpf_handle* h, int L, const int* slots, const int* gids, i
 }
 
 void distortion_free(hpf_handle* h) {
-    void* ptrs[] = {h->d_dist_f, h->d_dist_arg, h->d_dist_u, h->d_dist_cnt, h->d_dist_limit};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    h->d_dist_f = h->d_dist_limit = nullptr;
-    h->d_dist_arg = nullptr;
-    h->d_dist_u = nullptr;
-    h->d_dist_cnt = nullptr;
+    h->dist_mem.clear();
     h->dist_open = false;
 }
 
 void start_free(hpf_handle* h) {
-    void* ptrs[] = {h->d_sVm, h->d_sVa, h->d_sU, h->d_sE};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    h->d_sVm = h->d_sVa = nullptr;
-    h->d_sU = h->d_sE = nullptr;
+    h->start_mem.clear();
     h->start_set = false;
 }
 
@@ -1709,8 +1675,8 @@ int start_alloc(hpf_handle* h) {
     if (h->d_sVm) return HPF_OK;
     const size_t count = (size_t)h->n * h->Hn;
     int r;
-    if ((r = dev_alloc(h, &h->d_sVm, count)) || (r = dev_alloc(h, &h->d_sVa, count)) || (r = dev_alloc(h, &h->d_sU, count)) ||
-        (r = dev_alloc(h, &h->d_sE, count))) {
+    DevMem& mem = h->start_mem;
+    if ((r = mem.alloc(&h->d_sVm, count)) || (r = mem.alloc(&h->d_sVa, count)) || (r = mem.alloc(&h->d_sU, count)) || (r = mem.alloc(&h->d_sE, count))) {
         start_free(h);
         return r;
     }
@@ -1719,17 +1685,13 @@ int start_alloc(hpf_handle* h) {
 
 // ---- per-scenario source currents (hpf_sources.hpp) ------------------------------------------------------------------------------------------
 void queue_sources_drop(hpf_handle* h) {
-    if (h->d_qsrc) hipFree(h->d_qsrc);
-    if (h->d_qorders) hipFree(h->d_qorders);
-    h->d_qsrc = nullptr;
-    h->d_qorders = nullptr;
+    h->qsrc_mem.clear();
     h->qsrc_n = 0;
 }
 
 void sources_free(hpf_handle* h) {
     queue_sources_drop(h);
-    if (h->d_src) hipFree(h->d_src);
-    h->d_src = nullptr;
+    h->src_mem.clear();
     h->src_set = false;
 }
 
@@ -1747,28 +1709,22 @@ int sources_check(const hpf_handle* h, int n_scen, int form, const double* data,
     return HPF_OK;
 }
 
-// the caller's array (and the orders of form 1) -> fresh device buffers, on the handle's stream
-int sources_upload(hpf_handle* h, int n_scen, int form, const double* data, const int32_t* orders, void** d_data, int** d_orders) {
-    double* dd = nullptr;
-    int* od = nullptr;
+// the caller's array (and the orders of form 1) -> fresh device buffers of `mem` (empty; cleared on failure), on the handle's stream
+int sources_upload(hpf_handle* h, DevMem& mem, int n_scen, int form, const double* data, const int32_t* orders, void** d_data, int** d_orders) {
     int r;
     const size_t cnt = (size_t)n_scen * sources_row(h, form);
-    if ((r = dev_alloc(h, &dd, cnt))) return r;
-    if (form == SRC_SCALE_SHIFT && (r = dev_alloc(h, &od, (size_t)h->Hn))) {
-        hipFree(dd);
+    if ((r = mem.alloc((double**)d_data, cnt)) || (form == SRC_SCALE_SHIFT && (r = mem.alloc(d_orders, (size_t)h->Hn)))) {
+        mem.clear();
         return r;
     }
-    hipError_t e = hipMemcpyAsync(dd, data, sizeof(double) * cnt, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess && od) e = hipMemcpyAsync(od, orders, sizeof(int) * (size_t)h->Hn, hipMemcpyHostToDevice, h->stream);
+    hipError_t e = hipMemcpyAsync(*d_data, data, sizeof(double) * cnt, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && *d_orders) e = hipMemcpyAsync(*d_orders, orders, sizeof(int) * (size_t)h->Hn, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);            // (the caller's arrays may go away after the call)
     if (e != hipSuccess) {
-        hipFree(dd);
-        if (od) hipFree(od);
+        mem.clear();
         h->last_detail = (int)e;
         return HPF_E_HIP;
     }
-    *d_data = dd;
-    *d_orders = od;
     return HPF_OK;
 }
 
@@ -1776,7 +1732,7 @@ int sources_upload(hpf_handle* h, int n_scen, int form, const double* data, cons
 int sources_fill(hpf_handle* h, int S, int form, const void* d_data, const int* d_orders, int g0) {
     const int nnl = h->n - h->m;
     int r;
-    if (!h->d_src && (r = dev_alloc(h, &h->d_src, (size_t)h->S_max * nnl * h->Hn))) return r;
+    if (!h->d_src && (r = h->src_mem.alloc(&h->d_src, (size_t)h->S_max * nnl * h->Hn))) return r;
     if (form == SRC_CURRENTS) {
         const size_t row = (size_t)nnl * h->Hn;
         HIPCHK(hipMemcpyAsync(h->d_src, (const cplx*)d_data + (size_t)g0 * row, sizeof(cplx) * row * (size_t)S, hipMemcpyDeviceToDevice, h->stream));
@@ -1788,24 +1744,13 @@ int sources_fill(hpf_handle* h, int S, int form, const void* d_data, const int* 
 }
 
 void branch_stats_free(hpf_handle* h) {
-    void* ptrs[] = {h->d_bs_f, h->d_bs_arg, h->d_bs_over, h->d_bs_cnt, h->d_bs_rating};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    h->d_bs_f = h->d_bs_rating = nullptr;
-    h->d_bs_arg = nullptr;
-    h->d_bs_over = nullptr;
-    h->d_bs_cnt = nullptr;
+    h->bstat_mem.clear();
     h->bstat_open = false;
 }
 
 void branch_free(hpf_handle* h) {
     branch_stats_free(h);
-    void* ptrs[] = {h->d_br_from, h->d_br_to, h->d_br_y, h->d_br_part};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    h->d_br_from = h->d_br_to = nullptr;
-    h->d_br_y = nullptr;
-    h->d_br_part = nullptr;
+    h->br_mem.clear();
     h->br_built = false;
 }
 
@@ -1829,8 +1774,9 @@ int branch_build(hpf_handle* h) {
         for (int q = 0; q < Hn; ++q) yb[(size_t)e * Hn + q] = cneg(Y[(size_t)h->br_ypos[e] * Hn + q]);
     const int tiles = (nb + BRANCH_TILE - 1) / BRANCH_TILE;
     int r;
-    if ((r = dev_upload(h, &h->d_br_from, h->br_from.data(), (size_t)nb)) || (r = dev_upload(h, &h->d_br_to, h->br_to.data(), (size_t)nb)) ||
-        (r = dev_upload(h, &h->d_br_y, yb.data(), yb.size())) || (r = dev_alloc(h, &h->d_br_part, (size_t)h->S_max * tiles * Hn))) {
+    DevMem& mem = h->br_mem;
+    if ((r = mem.upload(&h->d_br_from, h->br_from)) || (r = mem.upload(&h->d_br_to, h->br_to)) || (r = mem.upload(&h->d_br_y, yb)) ||
+        (r = mem.alloc(&h->d_br_part, (size_t)h->S_max * tiles * Hn))) {
         branch_free(h);
         return r;
     }
@@ -1855,8 +1801,8 @@ int nr_loop(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* err
     const int S = h->S;
     const int cap = max_iter + 1;
     if (h->hist_cap < cap) {
-        if (h->d_hist) hipFree(h->d_hist);
-        if ((r = dev_alloc(h, &h->d_hist, (size_t)cap * h->S_max))) return r;
+        h->hist_cap = 0;
+        if ((r = h->mem.alloc(&h->d_hist, (size_t)cap * h->S_max))) return r;       // (releases the smaller one first)
         h->hist_cap = cap;
     }
     {
@@ -1875,9 +1821,12 @@ int nr_loop(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* err
     if (!FUND && h->resid_check && (r = reset_step_eta(h))) return r;
     if (can_repeat) {
         if (!h->d_Vm0) {
-            if ((r = dev_alloc(h, &h->d_Vm0, (size_t)h->S_max * count))) return r;
-            if ((r = dev_alloc(h, &h->d_Va0, (size_t)h->S_max * count))) return r;
-            if ((r = dev_alloc(h, &h->d_mask, (size_t)h->S_max))) return r;
+            DevMem& mem = h->repeat_mem;
+            if ((r = mem.alloc(&h->d_Vm0, (size_t)h->S_max * count)) || (r = mem.alloc(&h->d_Va0, (size_t)h->S_max * count)) ||
+                (r = mem.alloc(&h->d_mask, (size_t)h->S_max))) {
+                mem.clear();
+                return r;
+            }
         }
         HIPCHK(hipMemcpyAsync(h->d_Vm0, h->d_Vm, sizeof(double) * S * count, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(h->d_Va0, h->d_Va, sizeof(double) * S * count, hipMemcpyDeviceToDevice, h->stream));
@@ -1939,19 +1888,18 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
     double *qP = nullptr, *qQ = nullptr, *sVm = nullptr, *sVa = nullptr, *qVm = nullptr, *qVa = nullptr;
     hpf_stat* qst = nullptr;
     int* qi = nullptr;                                   // slot_scen [S_max] | hlist | hg | newlist | next, base
+    DevMem tmp(&h->last_detail);                         // the whole sweep's arrays: gone on every return path ...
     auto cleanup = [&](int code) {
-        hipStreamSynchronize(h->stream);
-        void* ptrs[] = {qP, qQ, sVm, sVa, qVm, qVa, qst, qi};
-        for (void* q : ptrs)
-            if (q) hipFree(q);
+        hipStreamSynchronize(h->stream);                 // ... once the stream is done with them
+        tmp.clear();
         return code;
     };
     const bool warm = h->start_set;                      // every scenario begins at the handle's start state: no pf, no seed arrays
-    if ((r = dev_alloc(h, &qP, (size_t)n_total * n)) || (r = dev_alloc(h, &qQ, (size_t)n_total * n)) ||
-        (!warm && ((r = dev_alloc(h, &sVm, (size_t)n_total * n)) || (r = dev_alloc(h, &sVa, (size_t)n_total * n)))) ||
-        (r = dev_alloc(h, &qst, (size_t)n_total)) || (r = dev_alloc(h, &qi, (size_t)4 * S_max + 2)))
+    if ((r = tmp.alloc(&qP, (size_t)n_total * n)) || (r = tmp.alloc(&qQ, (size_t)n_total * n)) ||
+        (!warm && ((r = tmp.alloc(&sVm, (size_t)n_total * n)) || (r = tmp.alloc(&sVa, (size_t)n_total * n)))) ||
+        (r = tmp.alloc(&qst, (size_t)n_total)) || (r = tmp.alloc(&qi, (size_t)4 * S_max + 2)))
         return cleanup(r);
-    if (Vm && ((r = dev_alloc(h, &qVm, (size_t)n_total * count)) || (r = dev_alloc(h, &qVa, (size_t)n_total * count)))) return cleanup(r);
+    if (Vm && ((r = tmp.alloc(&qVm, (size_t)n_total * count)) || (r = tmp.alloc(&qVa, (size_t)n_total * count)))) return cleanup(r);
     int *slot_scen = qi, *hlist = qi + S_max, *hg = qi + 2 * S_max, *newlist = qi + 3 * S_max, *next = qi + 4 * S_max, *base = next + 1;
     if (hipMemcpyAsync(qP, P, sizeof(double) * (size_t)n_total * n, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         hipMemcpyAsync(qQ, Q, sizeof(double) * (size_t)n_total * n, hipMemcpyHostToDevice, h->stream) != hipSuccess)
@@ -2071,17 +2019,8 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
     return cleanup(HPF_OK);
 }
 
+// everything of the handle that is no device block (those go with their owners, hpf_internal.hpp, when the handle is deleted)
 void free_all(hpf_handle* h) {
-    void* ptrs[] = {h->d_rowrec, h->d_rowptr, h->d_col, h->d_diag, h->d_erow, h->d_dev, h->d_Y, h->d_YN, h->d_YNt, h->d_IN, h->d_P, h->d_Q,
-                    h->d_Vm, h->d_Va, h->d_U, h->d_E, h->d_I0, h->d_f, h->d_errbits, h->d_errpart, h->d_err, h->d_niter, h->d_active,
-                    h->d_nactive, h->d_pivflag, h->d_mask, h->d_Vm0, h->d_Va0, h->d_Vmp, h->d_Vap, h->d_swapVm, h->d_swapVa, h->d_tstamp, h->d_hist, h->d_stats, h->d_J, h->d_ipiv, h->d_info, h->d_Z, h->d_w, h->d_x, h->d_linA, h->d_C, h->d_dbg, h->d_H, h->d_chG, h->d_chH, h->d_chD, h->d_chy, h->d_chZ, h->d_lfK, h->d_lfS, h->d_fb, h->d_F, h->d_H2, h->d_jptr, h->d_jcol, h->d_jval, h->d_respart, h->d_eta};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    distortion_free(h);
-    branch_free(h);
-    start_free(h);
-    sources_free(h);
-    tree_free(h);
     for (auto& sp : h->spans) {
         hipEventDestroy(sp.e0);
         hipEventDestroy(sp.e1);
@@ -2195,11 +2134,12 @@ int hpf_create_opts(hpf_handle** out, const hpf_desc* d, const char* options) {
     }
     const size_t HnN = (size_t)d->Hn * d->n, S = (size_t)h->S_alloc;
     const size_t ynsz = (size_t)d->n_dev * d->Hn * (d->coupled ? d->Hn : 1);
-    if ((r = dev_upload(h, &h->d_rowptr, d->rowptr, (size_t)d->n + 1))) return fail(r);
-    if ((r = dev_upload(h, &h->d_col, d->col, (size_t)d->nnz))) return fail(r);
-    if ((r = dev_upload(h, &h->d_diag, diag.data(), (size_t)d->n))) return fail(r);
-    if ((r = dev_upload(h, &h->d_erow, erow.data(), (size_t)d->nnz))) return fail(r);
-    if ((r = dev_upload(h, &h->d_dev, d->dev_of_bus, (size_t)d->n))) return fail(r);
+    DevMem& mem = h->mem;
+    if ((r = mem.upload(&h->d_rowptr, d->rowptr, (size_t)d->n + 1))) return fail(r);
+    if ((r = mem.upload(&h->d_col, d->col, (size_t)d->nnz))) return fail(r);
+    if ((r = mem.upload(&h->d_diag, diag.data(), (size_t)d->n))) return fail(r);
+    if ((r = mem.upload(&h->d_erow, erow.data(), (size_t)d->nnz))) return fail(r);
+    if ((r = mem.upload(&h->d_dev, d->dev_of_bus, (size_t)d->n))) return fail(r);
     {   // row records of the mismatch kernel (Model::rowrec)
         std::vector<int> rec((size_t)d->n * 8, 0);
         for (int i = 0; i < d->n; ++i) {
@@ -2208,16 +2148,16 @@ int hpf_create_opts(hpf_handle** out, const hpf_desc* d, const char* options) {
             rec[(size_t)i * 8 + 1] = e1;
             for (int u = 0; u < 3; ++u) rec[(size_t)i * 8 + 2 + u] = d->col[e0 + u < e1 ? e0 + u : e1 - 1];
         }
-        if ((r = dev_upload(h, &h->d_rowrec, rec.data(), rec.size()))) return fail(r);
+        if ((r = mem.upload(&h->d_rowrec, rec.data(), rec.size()))) return fail(r);
     }
     {   // device copy of the admittances: entry-major [nnz][Hn] (Model::yi)
         std::vector<cplx> yt((size_t)d->Hn * d->nnz);
         const cplx* src = (const cplx*)d->Yval;
         for (int q = 0; q < d->Hn; ++q)
             for (int e = 0; e < d->nnz; ++e) yt[(size_t)e * d->Hn + q] = src[(size_t)q * d->nnz + e];
-        if ((r = dev_upload(h, &h->d_Y, yt.data(), yt.size()))) return fail(r);
+        if ((r = mem.upload(&h->d_Y, yt.data(), yt.size()))) return fail(r);
     }
-    if ((r = dev_upload(h, &h->d_YN, (const cplx*)d->Y_N, ynsz))) return fail(r);
+    if ((r = mem.upload(&h->d_YN, (const cplx*)d->Y_N, ynsz))) return fail(r);
     if (h->coupled) {                                     // transposed copy for the mismatch kernel (Model::YNt)
         std::vector<cplx> yt(ynsz);
         const cplx* src = (const cplx*)d->Y_N;
@@ -2225,28 +2165,28 @@ int hpf_create_opts(hpf_handle** out, const hpf_desc* d, const char* options) {
             for (int q = 0; q < d->Hn; ++q)
                 for (int p2 = 0; p2 < d->Hn; ++p2)
                     yt[((size_t)dv * d->Hn + p2) * d->Hn + q] = src[((size_t)dv * d->Hn + q) * d->Hn + p2];
-        if ((r = dev_upload(h, &h->d_YNt, yt.data(), ynsz))) return fail(r);
+        if ((r = mem.upload(&h->d_YNt, yt.data(), ynsz))) return fail(r);
     }
-    if ((r = dev_upload(h, &h->d_IN, (const cplx*)d->I_N, (size_t)d->n_dev * d->Hn))) return fail(r);
-    if ((r = dev_alloc(h, &h->d_P, S * d->n))) return fail(r);
-    if ((r = dev_alloc(h, &h->d_Q, S * d->n))) return fail(r);
-    if ((r = dev_alloc(h, &h->d_Vm, S * HnN))) return fail(r);
-    if ((r = dev_alloc(h, &h->d_Va, S * HnN))) return fail(r);
-    if ((r = dev_alloc(h, &h->d_U, S * HnN))) return fail(r);
-    if ((r = dev_alloc(h, &h->d_E, S * HnN))) return fail(r);
-    if ((r = dev_alloc(h, &h->d_I0, S * (size_t)h->n))) return fail(r);
-    if ((r = dev_alloc(h, &h->d_f, S * (size_t)(h->N > h->Nf ? h->N : h->Nf)))) return fail(r);
-    if ((r = dev_alloc(h, &h->d_errbits, S))) return fail(r);
+    if ((r = mem.upload(&h->d_IN, (const cplx*)d->I_N, (size_t)d->n_dev * d->Hn))) return fail(r);
+    if ((r = mem.alloc(&h->d_P, S * d->n))) return fail(r);
+    if ((r = mem.alloc(&h->d_Q, S * d->n))) return fail(r);
+    if ((r = mem.alloc(&h->d_Vm, S * HnN))) return fail(r);
+    if ((r = mem.alloc(&h->d_Va, S * HnN))) return fail(r);
+    if ((r = mem.alloc(&h->d_U, S * HnN))) return fail(r);
+    if ((r = mem.alloc(&h->d_E, S * HnN))) return fail(r);
+    if ((r = mem.alloc(&h->d_I0, S * (size_t)h->n))) return fail(r);
+    if ((r = mem.alloc(&h->d_f, S * (size_t)(h->N > h->Nf ? h->N : h->Nf)))) return fail(r);
+    if ((r = mem.alloc(&h->d_errbits, S))) return fail(r);
     h->errpart_stride = err_parts<false>(h) > err_parts<true>(h) ? err_parts<false>(h) : err_parts<true>(h);
-    if ((r = dev_alloc(h, &h->d_errpart, S * (size_t)h->errpart_stride))) return fail(r);
+    if ((r = mem.alloc(&h->d_errpart, S * (size_t)h->errpart_stride))) return fail(r);
     if (hipMemset(h->d_errpart, 0, sizeof(unsigned long long) * S * (size_t)h->errpart_stride) != hipSuccess) return fail(HPF_E_HIP);
-    if ((r = dev_alloc(h, &h->d_err, S))) return fail(r);
-    if ((r = dev_alloc(h, &h->d_niter, S))) return fail(r);
-    if ((r = dev_alloc(h, &h->d_active, S))) return fail(r);
-    if ((r = dev_alloc(h, &h->d_nactive, (size_t)1))) return fail(r);
-    if ((r = dev_alloc(h, &h->d_pivflag, S))) return fail(r);
+    if ((r = mem.alloc(&h->d_err, S))) return fail(r);
+    if ((r = mem.alloc(&h->d_niter, S))) return fail(r);
+    if ((r = mem.alloc(&h->d_active, S))) return fail(r);
+    if ((r = mem.alloc(&h->d_nactive, (size_t)1))) return fail(r);
+    if ((r = mem.alloc(&h->d_pivflag, S))) return fail(r);
     if (hipMemset(h->d_pivflag, 0, sizeof(int) * S) != hipSuccess) return fail(HPF_E_HIP);
-    if ((r = dev_alloc(h, &h->d_stats, S))) return fail(r);
+    if ((r = mem.alloc(&h->d_stats, S))) return fail(r);
     Model& M = h->M;
     M.n = d->n; M.m = d->m; M.c = d->c; M.Hn = d->Hn; M.nnz = d->nnz; M.n_dev = d->n_dev; M.coupled = h->coupled; M.bus_major = 1;
     M.rowptr = h->d_rowptr; M.col = h->d_col; M.diag = h->d_diag; M.Y = h->d_Y; M.dev = h->d_dev;
@@ -2305,11 +2245,10 @@ int hpf_set_sources(hpf_handle* h, int n_scen, int form, const double* data, con
     if (h->n == h->m) return HPF_OK;                     // no nonlinear bus: nothing to set
     void* dd = nullptr;
     int* od = nullptr;
-    if ((r = sources_upload(h, n_scen, form, data, orders, &dd, &od))) return r;
+    DevMem tmp(&h->last_detail);
+    if ((r = sources_upload(h, tmp, n_scen, form, data, orders, &dd, &od))) return r;
     r = sources_fill(h, n_scen, form, dd, od, 0);
     if (r == HPF_OK && hipStreamSynchronize(h->stream) != hipSuccess) r = HPF_E_HIP;
-    hipFree(dd);
-    if (od) hipFree(od);
     if (r) {
         h->src_set = false;
         return r;
@@ -2346,11 +2285,7 @@ int hpf_queue_sources(hpf_handle* h, int n_total, int form, const double* data, 
     if ((r = sources_check(h, n_total, form, data, orders))) return r;
     if (h->n == h->m) return HPF_OK;
     queue_sources_drop(h);                               // (a registration that was never consumed is replaced)
-    void* dd = nullptr;
-    int* od = nullptr;
-    if ((r = sources_upload(h, n_total, form, data, orders, &dd, &od))) return r;
-    h->d_qsrc = dd;
-    h->d_qorders = od;
+    if ((r = sources_upload(h, h->qsrc_mem, n_total, form, data, orders, &h->d_qsrc, &h->d_qorders))) return r;
     h->qsrc_n = n_total;
     h->qsrc_form = form;
     return HPF_OK;
@@ -2412,7 +2347,8 @@ int hpf_start_set(hpf_handle* h, const double* Vm0, const double* Va0) {
         if (!isfinite(Vm0[k]) || !isfinite(Va0[k]) || Vm0[k] == 0.0) return HPF_E_ARG;      // (E = U / Vm)
     int r;
     double* tmp = nullptr;                               // the caller's arrays as they are (stacked); the kernel transposes
-    if ((r = start_alloc(h)) || (r = dev_alloc(h, &tmp, 2 * count))) return r;
+    DevMem tmp_mem(&h->last_detail);
+    if ((r = start_alloc(h)) || (r = tmp_mem.alloc(&tmp, 2 * count))) return r;
     hipError_t e = hipMemcpyAsync(tmp, Vm0, sizeof(double) * count, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(tmp + count, Va0, sizeof(double) * count, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) {
@@ -2421,7 +2357,7 @@ int hpf_start_set(hpf_handle* h, const double* Vm0, const double* Va0) {
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    hipFree(tmp);
+    tmp_mem.clear();
     if (e != hipSuccess) {
         h->last_detail = (int)e;
         start_free(h);
@@ -2539,29 +2475,23 @@ int hpf_jacobian(hpf_handle* h, int scen, double* J) { return jacobian_impl(h, f
 static int jcsr_pattern(hpf_handle* h) {
     if (h->d_jptr) return HPF_OK;
     int r;
-    int* ptr = nullptr;
     long long* tot = nullptr;
-    if ((r = dev_alloc(h, &ptr, (size_t)h->N + 1))) return r;
-    if ((r = dev_alloc(h, &tot, (size_t)1))) {
-        hipFree(ptr);
-        return r;
-    }
-    hipLaunchKernelGGL(k_jcsr_count, dim3((unsigned)((h->N + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, h->M, h->N, h->Nc, ptr);
-    hipLaunchKernelGGL(k_jcsr_scan, dim3(1), dim3(1024), 0, h->stream, h->N, ptr, tot);
+    DevMem tmp(&h->last_detail);
+    auto fail = [&](int code) {          // (d_jptr stays null until the pattern stands: the next call builds it again)
+        h->mem.release(&h->d_jptr);
+        return code;
+    };
+    if ((r = h->mem.alloc(&h->d_jptr, (size_t)h->N + 1)) || (r = tmp.alloc(&tot, (size_t)1))) return fail(r);
+    hipLaunchKernelGGL(k_jcsr_count, dim3((unsigned)((h->N + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, h->M, h->N, h->Nc, h->d_jptr);
+    hipLaunchKernelGGL(k_jcsr_scan, dim3(1), dim3(1024), 0, h->stream, h->N, h->d_jptr, tot);
     long long nnz = 0;
     hipError_t e = hipMemcpyAsync(&nnz, tot, sizeof(long long), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    hipFree(tot);
     if (e != hipSuccess) {
-        hipFree(ptr);
         h->last_detail = (int)e;
-        return HPF_E_HIP;
+        return fail(HPF_E_HIP);
     }
-    if (nnz >= 0x7fffffffll) {           // 32-bit column indices / offsets, like scipy's default index type
-        hipFree(ptr);
-        return HPF_E_ARG;
-    }
-    h->d_jptr = ptr;
+    if (nnz >= 0x7fffffffll) return fail(HPF_E_ARG);     // 32-bit column indices / offsets, like scipy's default index type
     h->jnnz = nnz;
     return HPF_OK;
 }
@@ -2571,8 +2501,8 @@ static int jacobian_csr_impl(hpf_handle* h, int scen, int32_t* indptr, int32_t* 
     if (!h->loads_set || !h->state_set) return HPF_E_STATE;
     int r;
     if ((r = jcsr_pattern(h))) return r;
-    if (!h->d_jval && (r = dev_alloc(h, &h->d_jval, (size_t)h->jnnz))) return r;      // (each buffer under its own check: a failed second
-    if (!h->d_jcol && (r = dev_alloc(h, &h->d_jcol, (size_t)h->jnnz))) return r;      //  allocation is retried by the next call)
+    if (!h->d_jval && (r = h->mem.alloc(&h->d_jval, (size_t)h->jnnz))) return r;      // (each buffer under its own check: a failed second
+    if (!h->d_jcol && (r = h->mem.alloc(&h->d_jcol, (size_t)h->jnnz))) return r;      //  allocation is retried by the next call)
     if ((r = launch_polar<false>(h))) return r;
     const size_t so = (size_t)scen * h->n * h->Hn;
     hipLaunchKernelGGL(k_jcsr_fill, dim3((unsigned)((h->N + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, h->M, h->N, h->Nc, h->d_jptr,
@@ -2610,8 +2540,8 @@ static int with_previous_state(hpf_handle* h, int scen, const std::function<int(
     // (the swap buffers belong to the handle: no allocation / release per call -- a hipFree right after another handle returned tens of GB to
     //  the driver was seen to take 60 ms)
     int r;
-    if (!h->d_swapVm && (r = dev_alloc(h, &h->d_swapVm, (size_t)h->S_alloc * h->n * h->Hn))) return r;
-    if (!h->d_swapVa && (r = dev_alloc(h, &h->d_swapVa, (size_t)h->S_alloc * h->n * h->Hn))) return r;
+    if (!h->d_swapVm && (r = h->mem.alloc(&h->d_swapVm, (size_t)h->S_alloc * h->n * h->Hn))) return r;
+    if (!h->d_swapVa && (r = h->mem.alloc(&h->d_swapVa, (size_t)h->S_alloc * h->n * h->Hn))) return r;
     double *tm = h->d_swapVm, *ta = h->d_swapVa;
     hipMemcpyAsync(tm, h->d_Vm, sizeof(double) * cnt, hipMemcpyDeviceToDevice, h->stream);
     hipMemcpyAsync(ta, h->d_Va, sizeof(double) * cnt, hipMemcpyDeviceToDevice, h->stream);
@@ -2654,7 +2584,7 @@ static int solve_queue_any(hpf_handle* h, int n_total, const double* P, const do
     h->src_set = false;
     if (with_src) {
         int r;
-        if (!h->d_src && (r = dev_alloc(h, &h->d_src, (size_t)h->S_max * (h->n - h->m) * h->Hn))) return r;
+        if (!h->d_src && (r = h->src_mem.alloc(&h->d_src, (size_t)h->S_max * (h->n - h->m) * h->Hn))) return r;
     }
     const bool fast = h->solver == HPF_SOLVER_BLOCK_TREE && h->n_ties == 0 && h->has_ctree && h->gj_mode == 1 &&
                       bus_images(h) && h->S_max <= 4096 && !h->trace_Vm;      // (k_queue_refill keeps its storage table in LDS: 8 B per slot)
@@ -2783,8 +2713,9 @@ int hpf_distortion_begin(hpf_handle* h, const double* limit, double thd_limit, d
     distortion_free(h);                                  // (an open accumulator is reset; the bin count may differ)
     const size_t T = (size_t)h->n * h->Hn + h->n, nu = T + (size_t)h->n * (hist_bins + 1);
     int r;
-    if ((r = dev_alloc(h, &h->d_dist_f, 3 * T)) || (r = dev_alloc(h, &h->d_dist_arg, T)) || (r = dev_alloc(h, &h->d_dist_u, nu)) ||
-        (r = dev_alloc(h, &h->d_dist_cnt, (size_t)3)) || (r = dev_upload(h, &h->d_dist_limit, lim.data(), lim.size()))) {
+    DevMem& mem = h->dist_mem;
+    if ((r = mem.alloc(&h->d_dist_f, 3 * T)) || (r = mem.alloc(&h->d_dist_arg, T)) || (r = mem.alloc(&h->d_dist_u, nu)) ||
+        (r = mem.alloc(&h->d_dist_cnt, (size_t)3)) || (r = mem.upload(&h->d_dist_limit, lim))) {
         distortion_free(h);
         return r;
     }
@@ -2877,16 +2808,15 @@ int hpf_branch_flows(hpf_handle* h, double* I, double* irms, double* thd_i, doub
     cplx* dI = nullptr;
     double* dv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};      // irms, thd_i, loss, loss_harm, loss_h
     double* host[5] = {irms, thd_i, loss, loss_harm, loss_h};
+    DevMem tmp(&h->last_detail);
     auto cleanup = [&](int code) {
         hipStreamSynchronize(h->stream);
-        if (dI) hipFree(dI);
-        for (double* p : dv)
-            if (p) hipFree(p);
+        tmp.clear();
         return code;
     };
-    if (I && (r = dev_alloc(h, &dI, (size_t)S * Hn * nb))) return cleanup(r);
+    if (I && (r = tmp.alloc(&dI, (size_t)S * Hn * nb))) return cleanup(r);
     for (int k = 0; k < 5; ++k)
-        if (host[k] && (r = dev_alloc(h, &dv[k], (size_t)S * (k == 4 ? Hn : nb)))) return cleanup(r);
+        if (host[k] && (r = tmp.alloc(&dv[k], (size_t)S * (k == 4 ? Hn : nb)))) return cleanup(r);
     hipLaunchKernelGGL(k_branch_refresh_u, grid2((int)count, S), dim3(TPB), 0, h->stream, (int)count, h->d_Vm, h->d_Va, h->d_U);
     if (nb > 0) {
         if (lds > 64 * 1024 &&
@@ -2918,8 +2848,9 @@ int hpf_branch_stats_begin(hpf_handle* h, const double* rating) {
     HIPCHK(hipStreamSynchronize(h->stream));
     branch_stats_free(h);                                // (an open accumulator is reset)
     const size_t nb = (size_t)h->nb;
-    if ((r = dev_alloc(h, &h->d_bs_f, 9 * nb)) || (r = dev_alloc(h, &h->d_bs_arg, 3 * nb)) || (r = dev_alloc(h, &h->d_bs_over, nb)) ||
-        (r = dev_alloc(h, &h->d_bs_cnt, (size_t)3)) || (r = dev_upload(h, &h->d_bs_rating, lim.data(), lim.size()))) {
+    DevMem& mem = h->bstat_mem;
+    if ((r = mem.alloc(&h->d_bs_f, 9 * nb)) || (r = mem.alloc(&h->d_bs_arg, 3 * nb)) || (r = mem.alloc(&h->d_bs_over, nb)) ||
+        (r = mem.alloc(&h->d_bs_cnt, (size_t)3)) || (r = mem.upload(&h->d_bs_rating, lim))) {
         branch_stats_free(h);
         return r;
     }
@@ -2976,6 +2907,12 @@ int hpf_debug_stamps(hpf_handle* h, long long* out, int count) {
     return HPF_OK;
 }
 
+int hpf_debug_device_memory(int64_t* blocks, int64_t* bytes) {
+    if (blocks) *blocks = devmem_live().blocks.load();
+    if (bytes) *bytes = devmem_live().bytes.load();
+    return HPF_OK;
+}
+
 int hpf_set_option(hpf_handle* h, const char* name, int value) {
     if (!h || !name) return HPF_E_ARG;
     if (!strcmp(name, "scenario_groups")) {         // independent scenario pipelines on separate streams (1..8)
@@ -2994,12 +2931,15 @@ int hpf_set_option(hpf_handle* h, const char* name, int value) {
         return HPF_OK;
     }
     if (!strcmp(name, "keep_previous_state")) {     // hpf_solve keeps, per scenario, the state its last Newton step started from
-        h->keep_prev = value ? 1 : 0;
-        if (h->keep_prev && !h->d_Vmp) {
+        if (value && !h->d_Vmp) {
             int rr;
-            if ((rr = dev_alloc(h, &h->d_Vmp, (size_t)h->S_alloc * h->n * h->Hn))) return rr;
-            if ((rr = dev_alloc(h, &h->d_Vap, (size_t)h->S_alloc * h->n * h->Hn))) return rr;
+            const size_t cnt = (size_t)h->S_alloc * h->n * h->Hn;
+            if ((rr = h->prev_mem.alloc(&h->d_Vmp, cnt)) || (rr = h->prev_mem.alloc(&h->d_Vap, cnt))) {
+                h->prev_mem.clear();
+                return rr;
+            }
         }
+        h->keep_prev = value ? 1 : 0;                // (only with both buffers in place)
         return HPF_OK;
     }
     if (!strcmp(name, "border_pivoting")) {         // meshed BLOCK_TREE handles: 1 = the border system always through the pivoted LU
@@ -3015,8 +2955,11 @@ int hpf_set_option(hpf_handle* h, const char* name, int value) {
         if (value != 0 && value != 1) return HPF_E_ARG;
         if (value && !h->d_eta) {
             int rr;
-            if ((rr = dev_alloc(h, &h->d_respart, (size_t)h->S_alloc * 4 * h->errpart_stride))) return rr;
-            if ((rr = dev_alloc(h, &h->d_eta, 2 * (size_t)h->S_alloc))) return rr;
+            if ((rr = h->resid_mem.alloc(&h->d_respart, (size_t)h->S_alloc * 4 * h->errpart_stride)) ||
+                (rr = h->resid_mem.alloc(&h->d_eta, 2 * (size_t)h->S_alloc))) {
+                h->resid_mem.clear();
+                return rr;
+            }
         }
         if (value && !h->resid_check) {
             int rr;
@@ -3078,7 +3021,7 @@ int hpf_timing_enable(hpf_handle* h, int on) {
             init[i] = ~0ull;
             init[i + 1] = 0ull;
         }
-        int rr = dev_upload(h, &h->d_tstamp, init.data(), init.size());
+        int rr = h->mem.upload(&h->d_tstamp, init);
         if (rr) return rr;
     }
     int r = resolve_spans(h);
@@ -3127,9 +3070,8 @@ int hpf_dense_solve(int device, int N, const double* J_colmajor, const double* f
     int64_t info64 = 0;
     int info32 = 0, rc = HPF_OK;
     if (rocblas_create_handle(&blas) != rocblas_status_success) return HPF_E_ROCSOLVER;
-    if (hipMalloc((void**)&dJ, sizeof(double) * elems) != hipSuccess || hipMalloc((void**)&df, sizeof(double) * N) != hipSuccess ||
-        hipMalloc((void**)&dip, sizeof(int64_t) * N) != hipSuccess || hipMalloc((void**)&dinfo, sizeof(int64_t)) != hipSuccess)
-        rc = HPF_E_NOMEM;
+    DevMem tmp;
+    if (!(rc = tmp.alloc(&dJ, elems)) && !(rc = tmp.alloc(&df, (size_t)N)) && !(rc = tmp.alloc(&dip, (size_t)N))) rc = tmp.alloc(&dinfo, (size_t)1);
     if (!rc && (hipMemcpy(dJ, J_colmajor, sizeof(double) * elems, hipMemcpyHostToDevice) != hipSuccess ||
                 hipMemcpy(df, f, sizeof(double) * N, hipMemcpyHostToDevice) != hipSuccess))
         rc = HPF_E_HIP;
@@ -3152,10 +3094,7 @@ int hpf_dense_solve(int device, int N, const double* J_colmajor, const double* f
                 hipMemcpy(dx, df, sizeof(double) * N, hipMemcpyDeviceToHost) != hipSuccess))
         rc = HPF_E_HIP;
     if (!rc && (wide ? info64 != 0 : info32 != 0)) rc = HPF_E_SINGULAR;
-    hipFree(dJ);
-    hipFree(df);
-    hipFree(dip);
-    hipFree(dinfo);
+    tmp.clear();
     rocblas_destroy_handle(blas);
     return rc;
 }

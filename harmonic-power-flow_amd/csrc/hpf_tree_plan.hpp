@@ -1725,19 +1725,12 @@ static void plan_report(hpf_handle* h, const hpf_desc& d, const Switches& sw, co
     }
 }
 
-// records a device array of the tree for tree_free_one, also when its copy failed
-template <class V>
-static int tree_upload(hpf_handle* h, Tree& T, V** dst, const std::vector<V>& v) {
-    const int r = upload(h, dst, v);
-    if (*dst) T.d_owned.push_back(*dst);
-    return r;
-}
-
-// Phase: upload.  The only phase that talks to the device: every device array of the Tree, in one list, no planning.
+// Phase: upload.  The only phase that talks to the device: every device array of the Tree, in one list, no planning.  The arrays belong to the
+// handle's owner (T is one of the handle's two trees).
 static int plan_upload(hpf_handle* h, Tree& T, const PlanWork& W) {
     int r = HPF_OK;
     auto up = [&](auto** dst, const auto& v) {
-        if (!r) r = tree_upload(h, T, dst, v);
+        if (!r) r = h->mem.upload(dst, v);
     };
     up(&T.d_parent, T.parent);
     up(&T.d_lvl_nodes, T.lvl_nodes);
@@ -1825,12 +1818,9 @@ int tree_plan_dump(const hpf_desc* d, const char* path) {
     tmp.plan_path = path;
     tmp.plan_only = true;
     tmp.sw = parse_switches(nullptr, env_switches_opted_in());     // (the environment under the same opt-in as hpf_create)
-    Tree T;
     int r = tree_find_ties(&tmp, d);                     // (meshed models: the loop-closing lines and the buses the factor-once bordered step keeps plain)
     if (r) return r;
-    r = tree_build_into(&tmp, d, T, true);
-    tree_free_one(T);
-    if (r) return r;
+    if ((r = tree_build_into(&tmp, d, tmp.tree, true))) return r;
     return tmp.plan_written ? HPF_OK : HPF_E_ARG;       // (the file could not be opened)
 }
 

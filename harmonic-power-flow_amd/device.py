@@ -33,6 +33,14 @@ def is_radial(n, rowptr, col):
     return bool(seen.all())
 
 
+def device_memory():
+    """-> (blocks, bytes) of device memory the library holds right now, over every handle of the process (hpf_debug_device_memory: the library's
+    own bookkeeping, exact and independent of what else runs on the device -- 0, 0 once every handle is closed)."""
+    blocks, nbytes = C.c_int64(), C.c_int64()
+    _lib.load().hpf_debug_device_memory(C.byref(blocks), C.byref(nbytes))
+    return int(blocks.value), int(nbytes.value)
+
+
 class DeviceModel:
     """One libhpf handle of capacity `max_scenarios`.  The capacity is NOT a build parameter of the block tree (it was in rounds 3-4): every
     handle eliminates the Gauss-Jordan skeleton with compress steps (fewer, wider elimination levels), so the Newton steps of a

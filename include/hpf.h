@@ -376,6 +376,13 @@ int  hpf_queue_sources(hpf_handle* h, int n_total, int form, const double* data,
  * [7] nonlinear bus.  Timing-only; never read by any kernel. */
 int  hpf_debug_stamps(hpf_handle* h, long long* out, int count);
 
+/* Diagnostics: device blocks and bytes the library holds at this moment, over all handles and running calls of the process (its own
+ * bookkeeping: every block it allocates has one owner, and the owners count; the per-call workspace of hpf_sparse_solve is not included).
+ * Either argument may be null.  After the last hpf_destroy both are 0; a begin / end pair (hpf_distortion_*, hpf_branch_stats_*,
+ * hpf_start_set / _clear, hpf_set_sources / hpf_clear_sources) leaves both as they were.  Unlike the device's free memory the figures do
+ * not depend on what else runs on the device, so a test can assert them exactly.  Always HPF_OK. */
+int  hpf_debug_device_memory(int64_t* blocks, int64_t* bytes);
+
 /* Options.  "block_pivoting" (BLOCK_TREE only): 0 (default) inverts the 2Hn x 2Hn bus blocks on the FP64 matrix cores with
  * a static pivot order (4x4 blocks = two harmonics, lane-parallel cofactor inverse), after contracting pass-through buses and
  * with per-model constant inverses for nonlinear leaf buses; 1 uses wave-level Gauss-Jordan with partial pivoting over the

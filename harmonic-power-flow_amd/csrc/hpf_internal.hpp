@@ -43,7 +43,11 @@ struct TimedSpan {
 
 // back-sweep tree walk: at most WALK_LISTS subtree lists (x 32 scenarios: one workgroup per CU), an LDS ring of the x of the last
 // WALK_SLOTS buses a workgroup walked
-constexpr int WALK_LISTS = 8, WALK_SLOTS = 32;
+#ifndef HPF_WALK_SLOTS
+#define HPF_WALK_SLOTS 32             // (a build flag for tests of the ring at another size)
+#endif
+constexpr int WALK_LISTS = 8, WALK_SLOTS = HPF_WALK_SLOTS;
+static_assert(WALK_SLOTS >= 2, "the walk's ring holds at least the previous bus");
 // back-sweep tail: LDS slots of a family's store of x (16 scenarios each); the children of a bus that gets none read its x from HBM
 constexpr int TAIL_SLOTS = 2;
 
@@ -106,6 +110,7 @@ struct Tree {
     // ... and for the one-round-trip kernels (k_lin_bundle_factor / _back): bundles of at most 256 * lin_np items (bus, harmonic),
     // records with cbeg = first child slot, d_lb2x[record] = (own slot | -1, local index of the parent | -1)
     int n_lin_bundles2 = 0, lin_np = 0;
+    int lin_maxunit = 0;              // buses of the largest unit (a chain's hanging subtrees, or a free subtree) the bundles are sized by
     int* d_lb2rec = nullptr;
     int* d_lb2x = nullptr;
     int* d_lb2ptr = nullptr;

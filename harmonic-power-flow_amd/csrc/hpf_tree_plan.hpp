@@ -558,6 +558,7 @@ static void plan_lin_records(const hpf_desc& d, const Switches& sw, Tree& T, Pla
     // bundles of whole all-linear subtrees for the one-launch kernels: subtrees in bus order, a bundle is closed before a height
     // of it would need a second pass of the 256 threads (one thread per (bus, harmonic) of a height)
     T.n_lin_bundles = 0;
+    T.lin_maxunit = 0;
     if (sw.lintree && T.n_lin_heights > 1) {
         const int NH = T.n_lin_heights, cap = std::max(1, 256 / d.Hn);
         std::vector<int> root_of(n, -1);
@@ -615,6 +616,7 @@ static void plan_lin_records(const hpf_desc& d, const Switches& sw, Tree& T, Pla
             size_t maxunit = 0;
             for (const std::vector<int>& ub : unit_bus) maxunit = std::max(maxunit, ub.size());
             const size_t mi = maxunit * (size_t)d.Hn;
+            T.lin_maxunit = (int)maxunit;
             T.lin_np = !sw.linbundle ? 0 : (mi <= 256 ? 1 : (mi <= 512 ? 2 : (mi <= 1024 ? 4 : 0)));
             T.n_lin_bundles2 = 0;
             T.chains_bundled = 0;
@@ -1688,6 +1690,15 @@ static void plan_report(hpf_handle* h, const hpf_desc& d, const Switches& sw, co
             if (h->n_ties > 0)
                 fprintf(fp, "# meshed: %d loop-closing lines, %d endpoint buses, border %d unknowns, bordered step %s\n", h->n_ties, h->n_tb, h->m_border,
                         h->mesh_sel ? "factor-once" : "virtual sweeps");
+            {                                       // the 2x2 algebra: its form, the bundles' size class, the chains and the linear subtrees
+                int max_chain = 0, max_sub = 0;
+                for (int r2 = 0; r2 < T.n_chains; ++r2) max_chain = std::max(max_chain, T.chain_ptr[r2 + 1] - T.chain_ptr[r2]);
+                for (int r2 = 0; r2 < T.n_lin_roots; ++r2) max_sub = std::max(max_sub, T.lin_ptr[r2 + 1] - T.lin_ptr[r2]);
+                fprintf(fp, "# caps: walk_slots %d walk_lists %d tail_slots %d\n", WALK_SLOTS, WALK_LISTS, TAIL_SLOTS);
+                fprintf(fp, "# lin: form %d lin_np %d bundles %d tree_bundles %d heights %d roots %d max_subtree %d max_unit %d\n", (int)T.lin_form, T.lin_np,
+                        T.n_lin_bundles2, T.n_lin_bundles, T.n_lin_heights, T.n_lin_roots, max_sub, T.lin_maxunit);
+                fprintf(fp, "# chains: %d chains, longest %d, own launches %d, bundled %d\n", T.n_chains, max_chain, T.chain_launches ? 1 : 0, T.chains_bundled);
+            }
             if (!T.walk_ptr.empty()) {              // the back-sweep walk: trunk (list 0) and branch lists, bus ids in walk order
                 fprintf(fp, "# walk: %d trunk depths, %d branch lists\n", T.walk_depth, T.walk_lists);
                 for (size_t l = 0; l + 1 < T.walk_ptr.size(); ++l) {

@@ -335,7 +335,7 @@ struct hpf_handle {
     long long n_back_tails = 0;       // back sweeps whose bordered buses and constant-inverse leaves went through k_back_tail (hpf_tree_census[16])
     long long n_back_walks = 0;       // back sweeps (scenario group x Newton step) whose Gauss-Jordan buses went through k_back_walk (hpf_tree_census[15])
     int auto_repivot = 1;             // hpf_solve repeats scenarios flagged by the static-pivot monitor with partial pivoting
-    int* h_act[2] = {nullptr, nullptr};          // pinned copies of d_active (hpf_solve looks at chunk c - 1 while chunk c runs)
+    int* h_act[2] = {nullptr, nullptr};          // pinned copies of the slot counter d_nactive, and of the queue's `next` (poll_post / poll_wait: the host looks at chunk c - 1 while chunk c runs)
     hipEvent_t poll_ev[2] = {nullptr, nullptr};
     double *trace_Vm = nullptr, *trace_Va = nullptr;   // hpf_set_trace: caller's [S][trace_cap][Hn*n] arrays (per-iteration states)
     int trace_cap = 0;

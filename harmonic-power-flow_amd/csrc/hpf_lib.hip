@@ -22,6 +22,7 @@
 
 #include "hpf_branch.hpp"
 #include "hpf_distortion.hpp"
+#include "hpf_groups.hpp"
 #include "hpf_internal.hpp"
 #include "hpf_sources.hpp"
 #include "hpf_update.hpp"
@@ -1287,42 +1288,6 @@ inline void set_ctx(hpf_handle* h, hipStream_t st, int s0, int cnt) {
 }
 inline void full_ctx(hpf_handle* h) { set_ctx(h, h->stream, 0, h->S); }
 
-inline int groups_for(const hpf_handle* h, int count) {
-    if (h->solver != HPF_SOLVER_BLOCK_TREE || h->n_ties > 0) return 1;
-    int g = h->n_groups;
-    while (g > 1 && count < 32 * g) --g;       // at least 32 scenarios per group (below that the launches of a group no longer fill their levels: tools/groups_sweep.py)
-    return g < 1 ? 1 : g;
-}
-inline int groups_for(const hpf_handle* h) { return groups_for(h, h->S); }
-
-// Run body() once per scenario group (slots [0, count) of the active list / scenarios [0, S) split evenly), each group on its
-// own stream between a fork and a join with the main stream.
-template <class F>
-int for_groups(hpf_handle* h, int count, F body) {
-    const int G = groups_for(h, count);
-    if (G == 1) {
-        set_ctx(h, h->stream, 0, count);
-        const int rc1 = body();
-        full_ctx(h);
-        return rc1;
-    }
-    HIPCHK(hipEventRecord(h->fork_ev, h->stream));
-    int rc = HPF_OK;
-    // group boundaries on multiples of 16 slots: the scenario-batched workgroups of the tree kernels take 16 scenarios each, an even
-    // split of e.g. 128 into 43 + 43 + 42 would run 3 x 3 tiles with ragged ends instead of 3 + 2 + 3 full ones
-    auto bound = [&](int g) { return g >= G ? count : (int)(16 * (((long long)count * g / G + 8) / 16)); };
-    for (int g = 0; g < G && rc == HPF_OK; ++g) {
-        const int s0 = bound(g), s1 = bound(g + 1);
-        HIPCHK(hipStreamWaitEvent(group_stream(h, g), h->fork_ev, 0));
-        set_ctx(h, group_stream(h, g), s0, s1 - s0);
-        rc = body();
-        HIPCHK(hipEventRecord(h->join_ev[g], group_stream(h, g)));
-    }
-    for (int g = 0; g < G; ++g) HIPCHK(hipStreamWaitEvent(h->stream, h->join_ev[g], 0));
-    full_ctx(h);
-    return rc;
-}
-
 // polar + mismatch (+ optional err conversion) for the current state
 template <bool FUND>
 int launch_polar(hpf_handle* h) {
@@ -1494,6 +1459,77 @@ int newton_step(hpf_handle* h, const int* active) {
     return dense_solve(h, Nsys);
 }
 
+// what one Newton iteration of the current launch context launches besides step, update and mismatch; the defaults: nothing (hpf_iterate)
+struct IterSpec {
+    const int* active = nullptr;   // slot list, or nullptr: every scenario of the slice
+    bool keep_prev = false;        // k_keep_prev before the step (hpf_solve with keep_previous_state)
+    bool finalize = false;         // k_finalize behind the mismatch (the device's stop rule; it owns d_active and d_nactive) ...
+    double thresh = 0.0;           // ... and its arguments
+    int max_iter = 0, hist_cap = 1, hist_off = 0;
+    double* hist = nullptr;        // nullptr, with hist_cap 1: no error history (the queue)
+};
+
+template <bool FUND>
+int launch_iteration(hpf_handle* h, const IterSpec& it) {
+    int r;
+    if (it.keep_prev)
+        hipLaunchKernelGGL(k_keep_prev, grid2(h->n * h->Hn, h->cur_S), dim3(TPB), 0, h->cur_stream, h->n * h->Hn, it.active, h->d_Vm, h->d_Va,
+                           h->d_Vmp, h->d_Vap, h->cur_s0);
+    if ((r = newton_step<FUND>(h, it.active))) return r;
+    if (!FUND && h->resid_check && (r = launch_step_residual(h, it.active))) return r;
+    if ((r = launch_update<FUND>(h, it.active))) return r;
+    if ((r = launch_mismatch<FUND>(h, it.active, false))) return r;
+    if (it.finalize)
+        hipLaunchKernelGGL(k_finalize, dim3((unsigned)h->cur_S), dim3(64), 0, h->cur_stream, h->cur_S, 0, it.thresh, it.max_iter, it.hist_cap,
+                           it.hist_off, h->d_errpart, h->errpart_stride, err_parts<FUND>(h), h->d_err, h->d_niter, h->d_active, h->d_nactive,
+                           it.hist, h->cur_s0, (const int*)nullptr);
+    return HPF_OK;
+}
+
+enum GroupOrder {
+    GROUP_MAJOR,           // every iteration of a group before the next group's first (the chunks of hpf_solve and of the queue)
+    ITERATION_MAJOR        // all groups' step i before any group's step i + 1: keeps the group pipelines in phase (hpf_iterate)
+};
+
+// `iters` iterations of slots [0, slots) of the active list / of the batch, split over the scenario groups (hpf_groups.hpp), each group on its
+// own stream between a fork and a join with the handle's stream.  One group, as the fundamental pass always is, runs on the handle's stream
+// without any event call.  An error ends the launches but not the joins: what was forked is joined, then the first error comes back.
+template <bool FUND>
+int enqueue_iterations(hpf_handle* h, int slots, int iters, const IterSpec& it, GroupOrder order) {
+    const int G = FUND ? 1 : group_count(h->solver == HPF_SOLVER_BLOCK_TREE && h->n_ties == 0, h->n_groups, slots);
+    if (G > 1) HIPCHK(hipEventRecord(h->fork_ev, h->stream));
+    int rc = HPF_OK;
+    auto ev = [&](hipError_t e) {
+        if (e != hipSuccess && rc == HPF_OK) {
+            h->last_detail = (int)e;
+            rc = HPF_E_HIP;
+        }
+    };
+    auto fork = [&](int g) { if (G > 1) ev(hipStreamWaitEvent(group_stream(h, g), h->fork_ev, 0)); };
+    auto join = [&](int g) { if (G > 1) ev(hipEventRecord(h->join_ev[g], group_stream(h, g))); };
+    auto iteration = [&](int g) {
+        if (rc != HPF_OK) return;
+        const int s0 = group_bound(slots, G, g);
+        set_ctx(h, group_stream(h, g), s0, group_bound(slots, G, g + 1) - s0);
+        rc = launch_iteration<FUND>(h, it);
+    };
+    if (order == GROUP_MAJOR) {
+        for (int g = 0; g < G; ++g) {
+            fork(g);
+            for (int i = 0; i < iters; ++i) iteration(g);
+            join(g);
+        }
+    } else {
+        for (int g = 0; g < G; ++g) fork(g);
+        for (int i = 0; i < iters; ++i)
+            for (int g = 0; g < G; ++g) iteration(g);
+        for (int g = 0; g < G; ++g) join(g);
+    }
+    for (int g = 0; G > 1 && g < G; ++g) ev(hipStreamWaitEvent(h->stream, h->join_ev[g], 0));
+    full_ctx(h);
+    return rc;
+}
+
 int check_info(hpf_handle* h, const std::vector<int>& was_active) {
     if (!h->d_info) return HPF_OK;
     std::vector<int> info(2 * (size_t)h->S);
@@ -1539,6 +1575,22 @@ int ensure_poll_buffers(hpf_handle* h) {
     return HPF_OK;
 }
 
+// device counters `src` -> words 0, 1, .. of the pinned buffer `buf`, behind everything the handle's stream holds so far
+int poll_post(hpf_handle* h, int buf, std::initializer_list<const int*> src) {
+    int* dst = h->h_act[buf];
+    for (const int* d : src) HIPCHK(hipMemcpyAsync(dst++, d, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipEventRecord(h->poll_ev[buf], h->stream));
+    return HPF_OK;
+}
+
+// the words of poll_post(buf), once they have arrived; nullptr: the wait failed (last_detail)
+const int* poll_wait(hpf_handle* h, int buf) {
+    const hipError_t e = hipEventSynchronize(h->poll_ev[buf]);
+    if (e == hipSuccess) return h->h_act[buf];
+    h->last_detail = (int)e;
+    return nullptr;
+}
+
 // One pass of the NR loop (HG:530-542 / HG:257-265) from the current state over the scenarios selected by `mask` (nullptr: all).
 template <bool FUND>
 int nr_pass(hpf_handle* h, double thresh, int max_iter, const int* mask) {
@@ -1559,29 +1611,7 @@ int nr_pass(hpf_handle* h, double thresh, int max_iter, const int* mask) {
     // c - 1 while chunk c is already queued (pinned double buffer + events), so the device never drains between chunks.
     const bool pipelined = !FUND && h->solver == HPF_SOLVER_BLOCK_TREE && !trace && h->n_ties == 0;
     const int chunk = pipelined ? (S >= 8 ? 4 : 2) : 1;
-    auto enqueue = [&](int todo, int slots) -> int {
-        auto body = [&]() -> int {
-            int rr;
-            for (int j = 0; j < todo; ++j) {
-                if (!FUND && h->keep_prev && h->d_Vmp)
-                    hipLaunchKernelGGL(k_keep_prev, grid2(h->n * h->Hn, h->cur_S), dim3(TPB), 0, h->cur_stream, h->n * h->Hn,
-                                       h->d_active, h->d_Vm, h->d_Va, h->d_Vmp, h->d_Vap, h->cur_s0);
-                if ((rr = newton_step<FUND>(h, h->d_active))) return rr;
-                if (!FUND && h->resid_check && (rr = launch_step_residual(h, h->d_active))) return rr;
-                if ((rr = launch_update<FUND>(h, h->d_active))) return rr;
-                if ((rr = launch_mismatch<FUND>(h, h->d_active, false))) return rr;
-                hipLaunchKernelGGL(k_finalize, dim3((unsigned)h->cur_S), dim3(64), 0, h->cur_stream, h->cur_S, 0, thresh,
-                                   max_iter, h->hist_cap, hist_off, h->d_errpart, h->errpart_stride, err_parts<FUND>(h), h->d_err, h->d_niter, h->d_active,
-                                   h->d_nactive, h->d_hist, h->cur_s0, (const int*)nullptr);
-            }
-            return HPF_OK;
-        };
-        if (FUND) {
-            full_ctx(h);
-            return body();
-        }
-        return for_groups(h, slots, body);
-    };
+    const IterSpec spec = {h->d_active, !FUND && h->keep_prev && h->d_Vmp, true, thresh, max_iter, h->hist_cap, hist_off, h->d_hist};
     if (pipelined) {
         if ((r = ensure_poll_buffers(h))) return r;
         // Between two chunks the slot list is compacted on the device (running scenarios first) and their count goes to the
@@ -1589,9 +1619,7 @@ int nr_pass(hpf_handle* h, double thresh, int max_iter, const int* mask) {
         // the scenario groups of the next chunk.  Slots behind the true count hold -1 and their workgroups exit at once.
         auto compact_and_post = [&](int buf) -> int {
             hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, h->stream, S, h->d_active, h->d_nactive);
-            HIPCHK(hipMemcpyAsync(h->h_act[buf], h->d_nactive, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipEventRecord(h->poll_ev[buf], h->stream));
-            return HPF_OK;
+            return poll_post(h, buf, {h->d_nactive});
         };
         int it = 0, c = 0, n_ub = S;
         if ((r = compact_and_post(0))) return r;
@@ -1602,14 +1630,14 @@ int nr_pass(hpf_handle* h, double thresh, int max_iter, const int* mask) {
             const bool lagged = n_ub > 8 || S <= 8;      // (a handle of a few scenarios keeps the queue fed: its chunks are short anyway)
             const int ch = lagged ? chunk : 2;
             if (!lagged) {
-                HIPCHK(hipEventSynchronize(h->poll_ev[c & 1]));
-                const int cnt0 = h->h_act[c & 1][0];
-                if (cnt0 == 0 || it >= max_iter) break;
-                n_ub = cnt0;
+                const int* left = poll_wait(h, c & 1);
+                if (!left) return HPF_E_HIP;
+                if (left[0] == 0 || it >= max_iter) break;
+                n_ub = left[0];
             }
             const int todo = (max_iter - it) < ch ? (max_iter - it) : ch;
             if (todo > 0) {
-                if ((r = enqueue(todo, n_ub))) return r;
+                if ((r = enqueue_iterations<FUND>(h, n_ub, todo, spec, GROUP_MAJOR))) return r;
                 if ((r = compact_and_post((c + 1) & 1))) return r;
                 it += todo;
             }
@@ -1617,10 +1645,10 @@ int nr_pass(hpf_handle* h, double thresh, int max_iter, const int* mask) {
                 ++c;
                 continue;
             }
-            HIPCHK(hipEventSynchronize(h->poll_ev[c & 1]));
-            const int cnt = h->h_act[c & 1][0];
-            if (cnt == 0 || todo == 0) break;
-            n_ub = cnt;
+            const int* left = poll_wait(h, c & 1);
+            if (!left) return HPF_E_HIP;
+            if (left[0] == 0 || todo == 0) break;
+            n_ub = left[0];
             ++c;
         }
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -1639,7 +1667,7 @@ int nr_pass(hpf_handle* h, double thresh, int max_iter, const int* mask) {
     while (nactive > 0 && it < max_iter) {
         was = act;                        // (no compaction on this path: slot i runs scenario i)
         h->host_act = act;                // (the bordered step of a meshed network walks the running scenarios on the host)
-        if ((r = enqueue(1, S))) return r;
+        if ((r = enqueue_iterations<FUND>(h, S, 1, spec, GROUP_MAJOR))) return r;
         HIPCHK(hipMemcpyAsync(act.data(), h->d_active, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         nactive = count_active(act.data());
@@ -1792,6 +1820,9 @@ int branch_add_launch(hpf_handle* h, int L, const int* slots, const int* gids, i
     return launch_status(h);
 }
 
+// mode bits of hpf_stat.flags (include/hpf.h): begun at the handle's start state, rectangular update, per-scenario sources
+inline int stat_mode_flags(const hpf_handle* h, bool from_start) { return (from_start ? 256 : 0) | (h->rect_update ? 512 : 0) | (h->src_set ? 1024 : 0); }
+
 template <bool FUND>
 int nr_loop(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* err, double* err_hist) {
     if (!h->loads_set || !h->state_set || h->S < 1) return HPF_E_STATE;
@@ -1860,7 +1891,7 @@ int nr_loop(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* err
     }
     if (!FUND) {
         hipLaunchKernelGGL(k_stats, dim3(S), dim3(TPB), 0, h->stream, h->n, h->Hn, thresh, max_iter, h->d_Vm, h->d_err,
-                           h->d_niter, h->d_pivflag, (h->from_start ? 256 : 0) | (h->rect_update ? 512 : 0) | (h->src_set ? 1024 : 0), h->d_stats);
+                           h->d_niter, h->d_pivflag, stat_mode_flags(h, h->from_start), h->d_stats);
         std::vector<int> pf(S);
         HIPCHK(hipMemcpyAsync(pf.data(), h->d_pivflag, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -1947,7 +1978,7 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
         hipLaunchKernelGGL(k_queue_refill, dim3(1), dim3(1024), q_lds, h->stream, S_max, n_total, h->d_active, h->d_nactive, slot_scen, next,
                            hlist, hg, newlist, base);
         hipLaunchKernelGGL(k_queue_harvest, dim3((unsigned)S_max), dim3(TPB), 0, h->stream, n, Hn, thresh, max_iter, hlist, hg, h->d_Vm,
-                           h->d_Va, h->d_err, h->d_niter, h->d_pivflag, (warm ? 256 : 0) | (h->rect_update ? 512 : 0) | (h->src_set ? 1024 : 0), qst, qVm, qVa);
+                           h->d_Va, h->d_err, h->d_niter, h->d_pivflag, stat_mode_flags(h, warm), qst, qVm, qVa);
         if (h->dist_open && distortion_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;   // (before the storages are refilled)
         if (h->bstat_open && branch_add_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;
         if (warm)
@@ -1972,36 +2003,20 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
         hipLaunchKernelGGL(k_queue_first, dim3((unsigned)S_max), dim3(64), 0, h->stream, S_max, thresh, max_iter, newlist, base,
                            h->d_errpart, h->errpart_stride, err_parts<false>(h), h->d_err, h->d_active);
         if (launch_status(h)) return HPF_E_HIP;
-        HIPCHK(hipMemcpyAsync(h->h_act[buf], h->d_nactive, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(h->h_act[buf] + 1, next, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipEventRecord(h->poll_ev[buf], h->stream));
-        return HPF_OK;
+        return poll_post(h, buf, {h->d_nactive, next});
     };
-    auto enqueue = [&](int todo, int slots) -> int {
-        auto body = [&]() -> int {
-            int rr;
-            for (int j = 0; j < todo; ++j) {
-                if ((rr = newton_step<false>(h, h->d_active))) return rr;
-                if (h->resid_check && (rr = launch_step_residual(h, h->d_active))) return rr;
-                if ((rr = launch_update<false>(h, h->d_active))) return rr;
-                if ((rr = launch_mismatch<false>(h, h->d_active, false))) return rr;
-                hipLaunchKernelGGL(k_finalize, dim3((unsigned)h->cur_S), dim3(64), 0, h->cur_stream, h->cur_S, 0, thresh, max_iter, 1, 0,
-                                   h->d_errpart, h->errpart_stride, err_parts<false>(h), h->d_err, h->d_niter, h->d_active, h->d_nactive, (double*)nullptr, h->cur_s0, (const int*)nullptr);
-            }
-            return HPF_OK;
-        };
-        return for_groups(h, slots, body);
-    };
+    const IterSpec spec = {h->d_active, false, true, thresh, max_iter};       // (no error history, no previous state: nothing could read either after a sweep)
     const int chunk = h->queue_chunk > 0 ? h->queue_chunk : 4;
     int c = 0, n_ub = S_used;
     if ((r = round(0))) return cleanup(r);
     const long long max_rounds = ((long long)(n_total + S_used - 1) / S_used + 2) * ((max_iter + chunk - 1) / chunk + 2) + 8;
     for (long long rd = 0; rd < max_rounds; ++rd) {
         // queue the next chunk BEFORE looking at what the previous round left (the device never drains between chunks)
-        if (n_ub > 0 && (r = enqueue(chunk, n_ub))) return cleanup(r);
+        if (n_ub > 0 && (r = enqueue_iterations<false>(h, n_ub, chunk, spec, GROUP_MAJOR))) return cleanup(r);
         if ((r = round((c + 1) & 1))) return cleanup(r);
-        if (hipEventSynchronize(h->poll_ev[c & 1]) != hipSuccess) return cleanup(HPF_E_HIP);
-        const int cnt = h->h_act[c & 1][0], nxt = h->h_act[c & 1][1];
+        const int* left = poll_wait(h, c & 1);
+        if (!left) return cleanup(HPF_E_HIP);
+        const int cnt = left[0], nxt = left[1];
         ++c;
         if (cnt == 0 && nxt >= n_total) break;           // nothing was running and nothing was pending: every scenario is harvested
         n_ub = nxt < n_total ? S_used : cnt;             // pending scenarios: every storage may be running after the next refill
@@ -2632,45 +2647,13 @@ int hpf_solve_queue(hpf_handle* h, int n_total, const double* P, const double* Q
     return rq;
 }
 
-// `iters` unconditional iterations of every scenario, enqueued group by group on the group streams (fork / join with h->stream)
-static int iterate_enqueue(hpf_handle* h, int iters) {
-    // iteration-major enqueue order (all groups' step i before any group's step i+1) keeps the group pipelines in phase
-    const int G = groups_for(h);
-    int r = HPF_OK;
-    if (G > 1) {
-        HIPCHK(hipEventRecord(h->fork_ev, h->stream));
-        for (int g = 0; g < G; ++g) HIPCHK(hipStreamWaitEvent(group_stream(h, g), h->fork_ev, 0));
-    }
-    auto bound = [&](int g) { return g >= G ? h->S : (int)(16 * (((long long)h->S * g / G + 8) / 16)); };   // (tile-aligned groups, for_groups)
-    for (int it = 0; it < iters && r == HPF_OK; ++it) {
-        for (int g = 0; g < G && r == HPF_OK; ++g) {
-            if (G > 1)
-                set_ctx(h, group_stream(h, g), bound(g), bound(g + 1) - bound(g));
-            else
-                full_ctx(h);
-            if ((r = newton_step<false>(h, nullptr))) break;
-            if (h->resid_check && (r = launch_step_residual(h, nullptr))) break;
-            if ((r = launch_update<false>(h, nullptr))) break;
-            r = launch_mismatch<false>(h, nullptr, false);
-        }
-    }
-    if (G > 1) {
-        for (int g = 0; g < G; ++g) {
-            HIPCHK(hipEventRecord(h->join_ev[g], group_stream(h, g)));
-            HIPCHK(hipStreamWaitEvent(h->stream, h->join_ev[g], 0));
-        }
-    }
-    full_ctx(h);
-    return r;
-}
-
 int hpf_iterate(hpf_handle* h, int iters) {
     if (!h || iters < 0) return HPF_E_ARG;
     if (!h->loads_set || !h->state_set || !h->mismatch_valid) return HPF_E_STATE;
     h->solve_done = false;
     // (replaying a captured hipGraph of several iterations was measured again in round 2, with 3 / 4 / 6 / 8 scenario groups at
     //  128 and 1 024 scenarios: 0..-6 % -- the step is not bound by the host's launch rate)
-    return iterate_enqueue(h, iters);
+    return enqueue_iterations<false>(h, h->S, iters, IterSpec{}, ITERATION_MAJOR);       // (every scenario, unconditionally: no stop rule)
 }
 
 int hpf_get_stats(hpf_handle* h, hpf_stat* stats) {
@@ -3167,7 +3150,7 @@ int hpf_setup_times(const hpf_handle* h, double* ms, int n_ms) {
 
 int hpf_scenario_groups(const hpf_handle* h, int live) {
     if (!h || live < 0) return HPF_E_ARG;
-    return groups_for(h, live);
+    return group_count(h->solver == HPF_SOLVER_BLOCK_TREE && h->n_ties == 0, h->n_groups, live);
 }
 
 int hpf_tree_plan(const hpf_desc* d, const char* path) {

@@ -72,6 +72,12 @@ SYMBOLS = {
     "hpf_branch_stats_add": (C.c_int, [_H, C.c_int]),
     "hpf_branch_stats_get": (C.c_int, [_H] + [C.c_void_p] * 14),
     "hpf_branch_stats_end": (C.c_int, [_H]),
+    "hpf_waveform_table": (C.c_int, [C.c_int, c_dbl_p, c_dbl_p]),
+    "hpf_waveform": (C.c_int, [_H, c_int_p, C.c_int, C.c_int, c_int_p, c_dbl_p, c_dbl_p, c_int_p, c_dbl_p, c_dbl_p]),
+    "hpf_waveform_stats_begin": (C.c_int, [_H, c_int_p, C.c_int, c_dbl_p, C.c_double]),
+    "hpf_waveform_stats_add": (C.c_int, [_H, C.c_int]),
+    "hpf_waveform_stats_get": (C.c_int, [_H] + [C.c_void_p] * 11),
+    "hpf_waveform_stats_end": (C.c_int, [_H]),
     "hpf_start_set": (C.c_int, [_H, c_dbl_p, c_dbl_p]),
     "hpf_start_capture": (C.c_int, [_H, C.c_int]),
     "hpf_start_get": (C.c_int, [_H, c_dbl_p, c_dbl_p]),

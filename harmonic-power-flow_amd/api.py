@@ -556,10 +556,31 @@ def line_summary(V, lines, buses, settings=None):
                         index=lines.index)
 
 
+def waveforms(V, buses, harmonics=None, samples=1024, at=None):
+    """Time-domain bus voltages of the voltage frame `V` over one fundamental period (not in the reference), evaluated on the GPU (hpf_waveform; a
+    borrowed assembly-only handle whose admittance pattern is the diagonal alone: the waveforms need the voltages only) -> (table, v):
+    table = DataFrame per bus (index = the "bus" level of V) with peak (largest |v| over the `samples` samples, p.u. of the nominal peak voltage),
+    kpeak (its sample), crest (peak / rms; sqrt 2 for a pure sine) and slack (the continuous peak lies in [peak, peak + slack]);
+    v = DataFrame [len(at)][samples] of the samples of the buses in `at` -- POSITIONS 0 .. n-1 in V's bus order; its rows carry the bus labels of
+    those positions (None: no samples, v is None).
+    harmonics: the orders of V's harmonic level (None: read from V); samples: a power of two, 64 .. 4096."""
+    n = len(buses)
+    harmonics = list(dict.fromkeys(V.index.get_level_values(0))) if harmonics is None else [int(h) for h in harmonics]
+    Y = AdmittanceSet(np.arange(n + 1, dtype=np.int32), np.arange(n, dtype=np.int32), np.ones((len(harmonics), n), dtype=np.complex128), harmonics, n)
+    with _borrow_model(buses, Y, None, False, harmonics, solver="dense", assembly_only=True) as dm:
+        dm.set_state(*_state_arrays(V))
+        w = dm.waveform(samples, at)
+    labels = pd.Index(list(dict.fromkeys(V.index.get_level_values(1))), name="bus")          # the bus labels of V, like get_THD's rows
+    table = pd.DataFrame({k: w[k][0] for k in ("peak", "kpeak", "crest", "slack")}, index=labels)
+    v = None if w["v"] is None else pd.DataFrame(w["v"][0], index=labels[w["buses"]], columns=pd.Index(range(int(samples)), name="sample"))
+    return table, v
+
+
 def solve(filename_buses, filename_lines, coupled=True, settings=None, ne_dir=None, solver="auto", verbose=False, extra_iters=0,
-          check_steps=False, line_flows=False, update="polar", sources=None):
+          check_steps=False, line_flows=False, update="polar", sources=None, waveforms=False):
     """Convenience wrapper (= init_network + hpf + get_THD) -> dict(V, err_h, n_iter_h, THD, details).  check_steps, update, sources: see hpf.
-    line_flows=True adds the keys "line_flows" and "line_summary" (the two functions of that name on the result)."""
+    line_flows=True adds the keys "line_flows" and "line_summary" (the two functions of that name on the result); waveforms=True (or a number of
+    samples) adds the key "waveforms": the per-bus table of the function of that name."""
     st = settings or globals()["settings"]
     buses, lines, m, n, c = init_network(filename_buses, filename_lines, settings=st)
     details = {}
@@ -572,4 +593,6 @@ def solve(filename_buses, filename_lines, coupled=True, settings=None, ne_dir=No
     if line_flows:
         out["line_flows"] = globals()["line_flows"](V, lines, buses, st)
         out["line_summary"] = line_summary(V, lines, buses, st)
+    if waveforms:
+        out["waveforms"] = globals()["waveforms"](V, buses, list(st.HARMONICS), 1024 if waveforms is True else int(waveforms))[0]
     return out

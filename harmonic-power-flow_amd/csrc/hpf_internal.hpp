@@ -300,6 +300,18 @@ struct hpf_handle {
     uint32_t* d_bs_over = nullptr;    // [nb] scenarios with irms above the rating
     long long* d_bs_cnt = nullptr;    // [3] added, skipped, deferred
     double* d_bs_rating = nullptr;    // [nb]
+    // waveform statistics accumulator (hpf_waveform_stats_*, hpf_waveform.hpp; allocated while open only)
+    bool wstat_open = false;
+    int ws_T = 0;                     // samples per fundamental period
+    double ws_crest_limit = 0.0;
+    double *d_ws_ct = nullptr, *d_ws_st = nullptr;   // [T] twiddle table (wave_table)
+    int* d_ws_orders = nullptr;       // [Hn] harmonic orders
+    double *d_ws_peak = nullptr, *d_ws_crest = nullptr;   // [S_max][n] scratch: k_wave_peaks -> k_wave_add
+    double* d_ws_f = nullptr;         // [6][n] peak max | sum | sumsq, crest max | sum | sumsq
+    int* d_ws_arg = nullptr;          // [2][n] scenario id of the two maxima (-1: nothing added)
+    uint32_t* d_ws_over = nullptr;    // [2][n] scenarios with the peak above peak_limit[i] | the crest factor above crest_limit
+    long long* d_ws_cnt = nullptr;    // [3] added, skipped, deferred
+    double* d_ws_limit = nullptr;     // [n] peak limits
     // start state (hpf_start_*; allocated while set only): one scenario's Vm, Va, U, E [n*Hn], bus-major like the state
     bool start_set = false;
     bool from_start = false;          // the current batch came from hpf_start_apply (until the next hpf_set_state): hpf_stat.flags bit 8
@@ -381,6 +393,7 @@ struct hpf_handle {
     hpf::DevMem dist_mem{&last_detail};   // d_dist_*
     hpf::DevMem bstat_mem{&last_detail};  // d_bs_*
     hpf::DevMem br_mem{&last_detail};     // d_br_*
+    hpf::DevMem wstat_mem{&last_detail};  // d_ws_*
     hpf::DevMem start_mem{&last_detail};  // d_sVm, d_sVa, d_sU, d_sE
     hpf::DevMem src_mem{&last_detail};    // d_src
     hpf::DevMem qsrc_mem{&last_detail};   // d_qsrc, d_qorders

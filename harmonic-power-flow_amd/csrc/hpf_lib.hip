@@ -26,6 +26,7 @@
 #include "hpf_internal.hpp"
 #include "hpf_sources.hpp"
 #include "hpf_update.hpp"
+#include "hpf_waveform.hpp"
 
 using namespace hpf;
 
@@ -1110,6 +1111,140 @@ __global__ __launch_bounds__(BR_TPB) void k_branch_add(int nb, int Hn, int n, in
     acc_over[t] = over;
 }
 
+// Voltage waveforms (hpf_waveform.hpp): the T samples of v(t) at a bus, their peak (value, sample), crest factor and sampling slack.
+// Workgroup (4 buses, list entry): one wavefront per (scenario, bus).  The scenario list is the one of k_distortion_add (slots NULL: entry l is
+// storage l; a negative slot: nothing to do -- the lists of hpf_solve_queue are -1 from their end on, as k_queue_harvest relies on); with `stats`
+// given, a scenario the accumulator would not add (dist_classify_start) is not evaluated either.  buslist NULL: buses 0 .. nbus - 1.
+// The table ct | st is staged in LDS once per workgroup: 16 T bytes, and LDS decides the occupancy -- T <= 1024: 16 KiB or less, the 8 workgroups
+// (32 waves) a CU can hold fit; T = 2048: 32 KiB -> 5 workgroups; T = 4096: 64 KiB -> 2 workgroups = 2 waves per SIMD.
+// Lane l evaluates the samples k = l, l + 64, ... in chunks of C per lane (C accumulators in registers), the harmonics in the OUTER loop, so each
+// sample's sum still runs over ascending q from 0.0 and the bus's U[q] and orders[q] are wave-uniform loads, once per chunk.  The 32 lanes of
+// an LDS lane group read the table at stride orders[q] doubles: a permutation of the 32 eight-byte banks for every ODD order (all orders of this
+// project's harmonic sets are odd) -- conflict-free; an even order 2^e m maps 2^e lanes onto one bank: correct, 2^e times slower on that term.
+// Reduction of (|v| key, k) over the wave by shuffles with the total order of wave_peak_combine; lane 0 writes.  v (optional): every lane stores
+// its samples, [list entry's storage][b][T].  No atomics.
+constexpr int WV_TPB = 256, WV_BUSES = WV_TPB / 64;
+template <int C>
+__global__ __launch_bounds__(WV_TPB) void k_wave_peaks(int n, int Hn, int T, int nbus, const int* __restrict__ buslist, const int* __restrict__ slots,
+                                                       const int* __restrict__ gids, int queue, const hpf_stat* __restrict__ stats,
+                                                       const cplx* __restrict__ U, const int* __restrict__ orders, const double* __restrict__ ct,
+                                                       const double* __restrict__ st, double* __restrict__ v, double* __restrict__ peak,
+                                                       int* __restrict__ kpeak, double* __restrict__ crest, double* __restrict__ slack) {
+    extern __shared__ __align__(16) unsigned char wv_lds[];
+    double* lc = reinterpret_cast<double*>(wv_lds);
+    double* ls = lc + T;
+    const int l = blockIdx.y;
+    const int s = slots ? slots[l] : l;
+    if (s < 0) return;                                   // (the whole workgroup: before the barrier)
+    if (stats) {
+        const hpf_stat rec = stats[gids ? gids[l] : l];
+        if (dist_classify_start(rec.flags, rec.thd_max, queue != 0) != DIST_ADD) return;
+    }
+    for (int j = threadIdx.x; j < T; j += WV_TPB) {
+        lc[j] = ct[j];
+        ls[j] = st[j];
+    }
+    __syncthreads();
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int b = blockIdx.x * WV_BUSES + w;
+    if (b >= nbus) return;
+    const int bus = buslist ? buslist[b] : b;
+    const cplx* Ub = U + ((size_t)s * n + bus) * Hn;
+    const int mask = T - 1;
+    uint64_t key = 0;                                    // (|v| = 0 at k = lane: never beats the lane's first sample)
+    int kbest = lane;
+    for (int c0 = 0; c0 < T / 64; c0 += C) {
+        double acc[C];
+#pragma unroll
+        for (int i = 0; i < C; ++i) acc[i] = 0.0;
+        const int k0 = lane + 64 * c0;
+        for (int q = 0; q < Hn; ++q) {
+            const cplx u = Ub[q];
+            const int h = orders[q];
+            int j = h * k0;                              // (h <= 32767, k < 4096: below 2^27)
+            const int step = h * 64;
+#pragma unroll
+            for (int i = 0; i < C; ++i) {
+                const int jj = j & mask;                 // = wave_phase(h, k0 + 64 i, T)
+                acc[i] = acc[i] + wave_term(u, lc[jj], ls[jj]);
+                j += step;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < C; ++i) {
+            const int k = k0 + 64 * i;
+            if (v) v[((size_t)s * nbus + b) * T + k] = acc[i];
+            wave_peak_combine(key, kbest, wave_key(acc[i]), k);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long key2 = __shfl_xor((unsigned long long)key, off, 64);
+        const int k2 = __shfl_xor(kbest, off, 64);
+        wave_peak_combine(key, kbest, (uint64_t)key2, k2);
+    }
+    if (lane != 0) return;
+    const size_t o = (size_t)s * n + bus;
+    const double pk = wave_key_value(key);
+    if (peak) peak[o] = pk;
+    if (kpeak) kpeak[o] = kbest;
+    if (crest) crest[o] = wave_crest(pk, wave_sumsq(Ub, Hn));
+    if (slack) slack[o] = wave_slack(Ub, orders, Hn, T);
+}
+
+// Waveform statistics accumulator, the twin of k_branch_add: one thread owns bus t (t = n: the three scenario counters), walks the list in order
+// and folds the peak and the crest factor k_wave_peaks left in the handle's scratch [storage][n] (same list, same classification, same ids):
+// plain loads and stores, no atomics.  acc_f [6][n]: peak max | sum | sumsq, crest max | sum | sumsq; acc_arg, acc_over [2][n].
+__global__ __launch_bounds__(BR_TPB) void k_wave_add(int n, int L, const int* __restrict__ slots, const int* __restrict__ gids, int id_base, int queue,
+                                                     const hpf_stat* __restrict__ stats, const double* __restrict__ peak,
+                                                     const double* __restrict__ crest, const double* __restrict__ peak_limit, double crest_limit,
+                                                     double* __restrict__ acc_f, int* __restrict__ acc_arg, uint32_t* __restrict__ acc_over,
+                                                     long long* __restrict__ cnt) {
+    const int t = blockIdx.x * BR_TPB + threadIdx.x;
+    if (t > n) return;
+    if (t == n) {
+        long long c[3] = {0, 0, 0};
+        for (int l = 0; l < L; ++l) {
+            if (slots && slots[l] < 0) break;
+            const hpf_stat st = stats[gids ? gids[l] : l];
+            c[dist_classify_start(st.flags, st.thd_max, queue != 0)] += 1;
+        }
+        for (int k = 0; k < 3; ++k) cnt[k] = cnt[k] + c[k];
+        return;
+    }
+    double mx[2], sum[2], sumsq[2];
+    int arg[2];
+    uint32_t over[2];
+    for (int k = 0; k < 2; ++k) {
+        mx[k] = acc_f[(size_t)(3 * k) * n + t];
+        sum[k] = acc_f[(size_t)(3 * k + 1) * n + t];
+        sumsq[k] = acc_f[(size_t)(3 * k + 2) * n + t];
+        arg[k] = acc_arg[(size_t)k * n + t];
+        over[k] = acc_over[(size_t)k * n + t];
+    }
+    const double lim = peak_limit[t];
+    bool any = false;
+    for (int l = 0; l < L; ++l) {
+        const int s = slots ? slots[l] : l;
+        if (s < 0) break;
+        const int g = gids ? gids[l] : l;
+        const hpf_stat st = stats[g];
+        if (dist_classify_start(st.flags, st.thd_max, queue != 0) != DIST_ADD) continue;
+        const size_t o = (size_t)s * n + t;
+        dist_fold(peak[o], id_base + g, lim, mx[0], arg[0], sum[0], sumsq[0], over[0]);
+        dist_fold(crest[o], id_base + g, crest_limit, mx[1], arg[1], sum[1], sumsq[1], over[1]);
+        any = true;
+    }
+    if (!any) return;
+    for (int k = 0; k < 2; ++k) {
+        acc_f[(size_t)(3 * k) * n + t] = mx[k];
+        acc_f[(size_t)(3 * k + 1) * n + t] = sum[k];
+        acc_f[(size_t)(3 * k + 2) * n + t] = sumsq[k];
+        acc_arg[(size_t)k * n + t] = arg[k];
+        acc_over[(size_t)k * n + t] = over[k];
+    }
+}
+
 // a new scenario moves into every storage of the new list: loads, the reference's start (HG:174-184) with the fundamental entries from
 // its power-flow seed, U / E, counters
 __global__ void k_queue_init(int n, int Hn, const int* __restrict__ newlist, const int* __restrict__ slot_scen, const double* __restrict__ qP,
@@ -1820,6 +1955,40 @@ int branch_add_launch(hpf_handle* h, int L, const int* slots, const int* gids, i
     return launch_status(h);
 }
 
+void wave_stats_free(hpf_handle* h) {
+    h->wstat_mem.clear();
+    h->wstat_open = false;
+}
+
+// one k_wave_peaks launch on the handle's stream: T samples (a valid T), the list of L entries, nbus buses per entry
+void wave_peaks_launch(hpf_handle* h, int T, int L, int nbus, const int* buslist, const int* slots, const int* gids, bool queue, const hpf_stat* stats,
+                       const int* orders, const double* ct, const double* st, double* v, double* peak, int* kpeak, double* crest, double* slack) {
+    if (L < 1 || nbus < 1) return;
+    const dim3 grid((unsigned)((nbus + WV_BUSES - 1) / WV_BUSES), (unsigned)L);
+    const size_t lds = 2 * sizeof(double) * (size_t)T;               // (at most 64 KiB: no attribute needed)
+#define HPF_WAVE_LAUNCH(C)                                                                                                                       \
+    hipLaunchKernelGGL((k_wave_peaks<C>), grid, dim3(WV_TPB), lds, h->stream, h->n, h->Hn, T, nbus, buslist, slots, gids, queue ? 1 : 0, stats, \
+                       (const cplx*)h->d_U, orders, ct, st, v, peak, kpeak, crest, slack)
+    switch (T / 64) {
+        case 1: HPF_WAVE_LAUNCH(1); break;
+        case 2: HPF_WAVE_LAUNCH(2); break;
+        case 4: HPF_WAVE_LAUNCH(4); break;
+        case 8: HPF_WAVE_LAUNCH(8); break;
+        default: HPF_WAVE_LAUNCH(16); break;
+    }
+#undef HPF_WAVE_LAUNCH
+}
+
+// the open waveform accumulator of h takes a list: k_wave_peaks into the scratch, then k_wave_add (list, records and id rule as k_distortion_add)
+int wave_add_launch(hpf_handle* h, int L, const int* slots, const int* gids, int id_base, bool queue, const hpf_stat* stats) {
+    wave_peaks_launch(h, h->ws_T, L, h->n, nullptr, slots, gids, queue, stats, h->d_ws_orders, h->d_ws_ct, h->d_ws_st, nullptr, h->d_ws_peak, nullptr,
+                      h->d_ws_crest, nullptr);
+    hipLaunchKernelGGL(k_wave_add, dim3((unsigned)((h->n + 1 + BR_TPB - 1) / BR_TPB)), dim3(BR_TPB), 0, h->stream, h->n, L, slots, gids, id_base,
+                       queue ? 1 : 0, stats, h->d_ws_peak, h->d_ws_crest, h->d_ws_limit, h->ws_crest_limit, h->d_ws_f, h->d_ws_arg, h->d_ws_over,
+                       h->d_ws_cnt);
+    return launch_status(h);
+}
+
 // mode bits of hpf_stat.flags (include/hpf.h): begun at the handle's start state, rectangular update, per-scenario sources
 inline int stat_mode_flags(const hpf_handle* h, bool from_start) { return (from_start ? 256 : 0) | (h->rect_update ? 512 : 0) | (h->src_set ? 1024 : 0); }
 
@@ -1981,6 +2150,7 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
                            h->d_Va, h->d_err, h->d_niter, h->d_pivflag, stat_mode_flags(h, warm), qst, qVm, qVa);
         if (h->dist_open && distortion_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;   // (before the storages are refilled)
         if (h->bstat_open && branch_add_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;
+        if (h->wstat_open && wave_add_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;
         if (warm)
             hipLaunchKernelGGL(k_queue_init_start, grid2((int)count, S_max), dim3(TPB), 0, h->stream, n, Hn, newlist, slot_scen, qP, qQ, h->d_sVm,
                                h->d_sVa, h->d_sU, h->d_sE, h->d_P, h->d_Q, h->d_Vm, h->d_Va, h->d_U, h->d_E, h->d_niter, h->d_pivflag);
@@ -2626,6 +2796,7 @@ static int solve_queue_any(hpf_handle* h, int n_total, const double* P, const do
         if ((r = hpf_solve(h, thresh, max_iter, nullptr, nullptr, nullptr))) return r;
         if (h->dist_open && (r = distortion_launch(h, S, nullptr, nullptr, h->dist_id_base + g0, true, h->d_stats))) return r;
         if (h->bstat_open && (r = branch_add_launch(h, S, nullptr, nullptr, h->dist_id_base + g0, true, h->d_stats))) return r;
+        if (h->wstat_open && (r = wave_add_launch(h, S, nullptr, nullptr, h->dist_id_base + g0, true, h->d_stats))) return r;
         if (stats && (r = hpf_get_stats(h, stats + g0))) return r;
         if (Vm && (r = hpf_get_state(h, Vm + (size_t)g0 * cnt, Va + (size_t)g0 * cnt))) return r;
     }
@@ -2880,6 +3051,135 @@ int hpf_branch_stats_end(hpf_handle* h) {
     if (!h->bstat_open) return HPF_OK;
     HIPCHK(hipStreamSynchronize(h->stream));
     branch_stats_free(h);
+    return HPF_OK;
+}
+
+// ---- voltage waveforms (hpf_waveform.hpp) ------------------------------------------------------------------------------------------------
+int hpf_waveform_table(int T, double* ct, double* st) {
+    if (!wave_T_ok(T) || !ct || !st) return HPF_E_ARG;
+    wave_table(T, ct, st);
+    return HPF_OK;
+}
+
+// T and the Hn orders of a waveform call, checked on the host
+static bool wave_args_ok(const hpf_handle* h, const int32_t* orders, int T) {
+    if (!orders || !wave_T_ok(T)) return false;
+    for (int q = 0; q < h->Hn; ++q)
+        if (!wave_order_ok(orders[q])) return false;
+    return true;
+}
+
+int hpf_waveform(hpf_handle* h, const int32_t* orders, int T, int n_sel, const int32_t* sel, double* v, double* peak, int32_t* kpeak, double* crest,
+                 double* slack) {
+    if (!h) return HPF_E_ARG;
+    if (!wave_args_ok(h, orders, T) || n_sel < 0 || (n_sel > 0 && !sel)) return HPF_E_ARG;
+    for (int k = 0; k < n_sel; ++k)
+        if (sel[k] < 0 || sel[k] >= h->n) return HPF_E_ARG;
+    if (!h->state_set || h->S < 1) return HPF_E_STATE;
+    const int S = h->S, n = h->n, Hn = h->Hn;
+    const size_t count = (size_t)n * Hn, sn = (size_t)S * n;
+    std::vector<double> tab(2 * (size_t)T);
+    wave_table(T, tab.data(), tab.data() + T);
+    double *d_tab = nullptr, *d_v = nullptr, *d_f[3] = {nullptr, nullptr, nullptr};          // peak, crest, slack
+    int *d_orders = nullptr, *d_sel = nullptr, *d_k = nullptr;
+    double* host[3] = {peak, crest, slack};
+    const bool per_bus = peak || kpeak || crest || slack, samples = v && n_sel > 0;
+    DevMem tmp(&h->last_detail);
+    auto cleanup = [&](int code) {
+        hipStreamSynchronize(h->stream);
+        tmp.clear();
+        return code;
+    };
+    int r;
+    if ((r = tmp.upload(&d_tab, tab)) || (r = tmp.upload(&d_orders, (const int*)orders, (size_t)Hn))) return cleanup(r);
+    for (int k = 0; k < 3; ++k)
+        if (host[k] && (r = tmp.alloc(&d_f[k], sn))) return cleanup(r);
+    if (kpeak && (r = tmp.alloc(&d_k, sn))) return cleanup(r);
+    if (samples && ((r = tmp.upload(&d_sel, (const int*)sel, (size_t)n_sel)) || (r = tmp.alloc(&d_v, (size_t)S * n_sel * T)))) return cleanup(r);
+    hipLaunchKernelGGL(k_branch_refresh_u, grid2((int)count, S), dim3(TPB), 0, h->stream, (int)count, h->d_Vm, h->d_Va, h->d_U);
+    // every bus for the per-bus outputs; the selected buses (in the caller's order, repeats allowed) once more for their samples
+    if (per_bus)
+        wave_peaks_launch(h, T, S, n, nullptr, nullptr, nullptr, false, nullptr, d_orders, d_tab, d_tab + T, nullptr, d_f[0], d_k, d_f[1], d_f[2]);
+    if (samples)
+        wave_peaks_launch(h, T, S, n_sel, d_sel, nullptr, nullptr, false, nullptr, d_orders, d_tab, d_tab + T, d_v, nullptr, nullptr, nullptr, nullptr);
+    if (launch_status(h)) return cleanup(HPF_E_HIP);
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return cleanup(HPF_E_HIP);
+    for (int k = 0; k < 3; ++k)
+        if (host[k] && hipMemcpy(host[k], d_f[k], sizeof(double) * sn, hipMemcpyDeviceToHost) != hipSuccess) return cleanup(HPF_E_HIP);
+    if (kpeak && hipMemcpy(kpeak, d_k, sizeof(int32_t) * sn, hipMemcpyDeviceToHost) != hipSuccess) return cleanup(HPF_E_HIP);
+    if (samples && hipMemcpy(v, d_v, sizeof(double) * (size_t)S * n_sel * T, hipMemcpyDeviceToHost) != hipSuccess) return cleanup(HPF_E_HIP);
+    return cleanup(HPF_OK);
+}
+
+int hpf_waveform_stats_begin(hpf_handle* h, const int32_t* orders, int T, const double* peak_limit, double crest_limit) {
+    if (!h) return HPF_E_ARG;
+    if (!wave_args_ok(h, orders, T) || crest_limit != crest_limit) return HPF_E_ARG;
+    const size_t n = (size_t)h->n;
+    std::vector<double> lim(n, (double)INFINITY);
+    for (size_t i = 0; peak_limit && i < n; ++i) {
+        if (peak_limit[i] != peak_limit[i]) return HPF_E_ARG;
+        lim[i] = peak_limit[i];
+    }
+    std::vector<double> ct((size_t)T), st((size_t)T);
+    wave_table(T, ct.data(), st.data());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    wave_stats_free(h);                                  // (an open accumulator is reset; T may differ)
+    int r;
+    DevMem& mem = h->wstat_mem;
+    if ((r = mem.upload(&h->d_ws_ct, ct)) || (r = mem.upload(&h->d_ws_st, st)) || (r = mem.upload(&h->d_ws_orders, (const int*)orders, (size_t)h->Hn)) ||
+        (r = mem.alloc(&h->d_ws_peak, (size_t)h->S_max * n)) || (r = mem.alloc(&h->d_ws_crest, (size_t)h->S_max * n)) ||
+        (r = mem.alloc(&h->d_ws_f, 6 * n)) || (r = mem.alloc(&h->d_ws_arg, 2 * n)) || (r = mem.alloc(&h->d_ws_over, 2 * n)) ||
+        (r = mem.alloc(&h->d_ws_cnt, (size_t)3)) || (r = mem.upload(&h->d_ws_limit, lim))) {
+        wave_stats_free(h);
+        return r;
+    }
+    HIPCHK(hipMemsetAsync(h->d_ws_f, 0, sizeof(double) * 6 * n, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_ws_arg, 0xff, sizeof(int) * 2 * n, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_ws_over, 0, sizeof(uint32_t) * 2 * n, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_ws_cnt, 0, sizeof(long long) * 3, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->ws_T = T;
+    h->ws_crest_limit = crest_limit;
+    h->wstat_open = true;
+    return HPF_OK;
+}
+
+int hpf_waveform_stats_add(hpf_handle* h, int first_id) {
+    if (!h || first_id < 0) return HPF_E_ARG;
+    if (!h->wstat_open || !h->loads_set || !h->state_set || h->S < 1 || !h->solve_done) return HPF_E_STATE;
+    int r;
+    if ((r = wave_add_launch(h, h->S, nullptr, nullptr, first_id, false, h->d_stats))) return r;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return HPF_OK;
+}
+
+int hpf_waveform_stats_get(hpf_handle* h, int64_t* counts, double* peak_max, int32_t* peak_arg, double* peak_sum, double* peak_sumsq,
+                           uint32_t* peak_over, double* crest_max, int32_t* crest_arg, double* crest_sum, double* crest_sumsq,
+                           uint32_t* crest_over) {
+    if (!h) return HPF_E_ARG;
+    if (!h->wstat_open) return HPF_E_STATE;
+    const size_t n = (size_t)h->n;
+    long long cnt[3];
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(cnt, h->d_ws_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
+    for (int k = 0; counts && k < 3; ++k) counts[k] = cnt[k];
+    double* f[6] = {peak_max, peak_sum, peak_sumsq, crest_max, crest_sum, crest_sumsq};
+    int32_t* a[2] = {peak_arg, crest_arg};
+    uint32_t* o[2] = {peak_over, crest_over};
+    for (int k = 0; k < 6; ++k)
+        if (f[k]) HIPCHK(hipMemcpy(f[k], h->d_ws_f + k * n, sizeof(double) * n, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 2; ++k) {
+        if (a[k]) HIPCHK(hipMemcpy(a[k], h->d_ws_arg + k * n, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+        if (o[k]) HIPCHK(hipMemcpy(o[k], h->d_ws_over + k * n, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    }
+    return HPF_OK;
+}
+
+int hpf_waveform_stats_end(hpf_handle* h) {
+    if (!h) return HPF_E_ARG;
+    if (!h->wstat_open) return HPF_OK;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    wave_stats_free(h);
     return HPF_OK;
 }
 

@@ -442,6 +442,52 @@ class DeviceModel:
         self._chk(self.lib.hpf_branch_stats_end(self._h), "hpf_branch_stats_end")
         self._brating = None
 
+    # -- voltage waveforms and waveform statistics (hpf_waveform*) -------------------------------------------
+    def _orders(self):
+        return np.ascontiguousarray(self.harmonics, dtype=np.int32)
+
+    def waveform(self, T=1024, buses=None):
+        """Time-domain bus voltages over one fundamental period at the handle's current state (after solve(), or after set_state() alone), T samples
+        (a power of two, 64..4096), orders = self.harmonics -> dict: peak, crest, slack [S][n] (p.u. of the nominal peak voltage; the continuous
+        peak lies in [peak, peak + slack]), kpeak [S][n] int32 (sample of the peak), and for buses = a list of bus indices: buses, v [S][len][T]
+        (None without it) (include/hpf.h, hpf_waveform)."""
+        S = self._batch("hpf_waveform")
+        sel = None if buses is None else np.ascontiguousarray(buses, dtype=np.int32).reshape(-1)
+        out = {k: np.empty((S, self.n)) for k in ("peak", "crest", "slack")}
+        out["kpeak"] = np.empty((S, self.n), dtype=np.int32)
+        n_sel = 0 if sel is None else len(sel)
+        out["buses"], out["v"] = sel, (np.empty((S, n_sel, max(int(T), 0))) if n_sel else None)
+        self._chk(self.lib.hpf_waveform(self._h, _ip(self._orders()), int(T), n_sel, _ip(sel) if n_sel else None, _dp(out["v"]) if n_sel else None,
+                                        _dp(out["peak"]), _ip(out["kpeak"]), _dp(out["crest"]), _dp(out["slack"])), "hpf_waveform")
+        return out
+
+    def waveform_stats_begin(self, T=1024, peak_limit=None, crest_limit=np.inf):
+        """Open (or reset) the handle's waveform statistics: from now on every converged scenario hpf_solve_queue harvests, and every batch handed to
+        waveform_stats_add, has the peak and the crest factor of every bus's voltage waveform (T samples per period) folded into per-bus statistics
+        on the device.  peak_limit [n] in p.u. (None: no limits) and crest_limit: the `over` arrays count the scenarios strictly above them."""
+        lim = None if peak_limit is None else np.ascontiguousarray(peak_limit, dtype=np.float64)
+        assert lim is None or lim.shape == (self.n,)
+        self._chk(self.lib.hpf_waveform_stats_begin(self._h, _ip(self._orders()), int(T), _dp(lim) if lim is not None else None, float(crest_limit)),
+                  "hpf_waveform_stats_begin")
+        self._wstat = (int(T), lim, float(crest_limit))
+
+    def waveform_stats_add(self, first_id=0):
+        """Fold the current batch (after solve()) into the waveform statistics, scenario s under id first_id + s."""
+        self._chk(self.lib.hpf_waveform_stats_add(self._h, int(first_id)), "hpf_waveform_stats_add")
+
+    def waveform_stats_get(self):
+        """-> sweep.WaveformStats of everything added since waveform_stats_begin; the accumulator stays open."""
+        from .sweep import WaveformStats
+        a = {name: np.zeros((3,) if name == "counts" else (self.n,), dtype=dt) for name, dt in zip(WaveformStats.ARRAYS, WaveformStats.DTYPES)}
+        self._chk(self.lib.hpf_waveform_stats_get(self._h, *[a[name].ctypes.data_as(C.c_void_p) for name in WaveformStats.ARRAYS]),
+                  "hpf_waveform_stats_get")
+        T, lim, crest_limit = getattr(self, "_wstat", None) or (0, None, np.inf)
+        return WaveformStats(T, lim, crest_limit, **a)
+
+    def waveform_stats_end(self):
+        self._chk(self.lib.hpf_waveform_stats_end(self._h), "hpf_waveform_stats_end")
+        self._wstat = None
+
     def set_option(self, name, value):
         self._chk(self.lib.hpf_set_option(self._h, name.encode(), int(value)), "hpf_set_option")
         self.__dict__.setdefault("_options", {})[name] = int(value)

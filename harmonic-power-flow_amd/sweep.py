@@ -243,6 +243,97 @@ def gather_branch_stats(stats, world, ids=None):
     return _gather_merge(stats, world, ids)
 
 
+class WaveformStats:
+    """Per-bus statistics of the voltage waveforms of a sweep, as the device accumulated them (hpf_waveform_stats_*, include/hpf.h) -- a plain
+    container of NumPy arrays [n] over the buses.  Two quantities per scenario and bus: peak (largest |v(t)| over the `samples` samples of one
+    fundamental period, p.u. of the nominal peak voltage) and crest (peak / rms; sqrt 2 for a pure sine).
+    counts [3] int64: scenarios added, skipped, deferred (the rules of DistortionStats); x_max / x_arg: largest value and the scenario id it came
+    from (ties: the smallest id; -1: nothing added); x_sum / x_sumsq: sums over the added scenarios; peak_over / crest_over: scenarios strictly
+    above `peak_limit[i]` / `crest_limit`."""
+    ARRAYS = ("counts", "peak_max", "peak_arg", "peak_sum", "peak_sumsq", "peak_over", "crest_max", "crest_arg", "crest_sum", "crest_sumsq",
+              "crest_over")
+    DTYPES = (np.int64, np.float64, np.int32, np.float64, np.float64, np.uint32, np.float64, np.int32, np.float64, np.float64, np.uint32)
+    QUANTITIES = ("peak", "crest")
+
+    def __init__(self, samples, peak_limit, crest_limit, **arrays):
+        for name, dt in zip(self.ARRAYS, self.DTYPES):
+            setattr(self, name, np.ascontiguousarray(arrays[name], dtype=dt))
+        n = self.peak_max.shape[0]
+        self.samples, self.crest_limit = int(samples), float(crest_limit)
+        self.peak_limit = np.full(n, np.inf) if peak_limit is None else np.array(peak_limit, dtype=np.float64)
+        assert self.counts.shape == (3,) and self.peak_limit.shape == (n,) and all(getattr(self, a).shape == (n,) for a in self.ARRAYS[1:])
+
+    @property
+    def added(self):
+        return int(self.counts[0])
+
+    def _same(self, **arrays):
+        return WaveformStats(self.samples, self.peak_limit, self.crest_limit, **arrays)
+
+    def mean(self, what="peak"):
+        """-> mean [n] of peak / crest over the added scenarios (NaN when nothing was added)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return getattr(self, what + "_sum") / self.added
+
+    def std(self, what="peak"):
+        """-> population standard deviation [n] from sum and sum of squares."""
+        m = self.mean(what)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.sqrt(np.maximum(getattr(self, what + "_sumsq") / self.added - m * m, 0.0))
+
+    def worst(self, k=1, what="peak"):
+        """The k buses with the largest maximum of `what` -> list of (bus, scenario id, value), largest first."""
+        v = getattr(self, what + "_max")
+        order = np.argsort(-v, kind="stable")[:k]
+        return [(int(i), int(getattr(self, what + "_arg")[i]), float(v[i])) for i in order]
+
+    def merge(self, other):
+        """Statistics of the union of two disjoint sets of scenarios: max with the smaller-id tie rule, integer adds, float adds.  Refuses
+        different samples / limits / shapes."""
+        if (self.peak_max.shape != other.peak_max.shape or self.samples != other.samples or self.crest_limit != other.crest_limit or
+                not np.array_equal(self.peak_limit, other.peak_limit)):
+            raise ValueError("WaveformStats.merge: the two accumulators were opened with different settings or shapes")
+        out = {"counts": self.counts + other.counts}
+        for pre in self.QUANTITIES:
+            ma, aa, mb, ab = (getattr(o, pre + f) for o in (self, other) for f in ("_max", "_arg"))
+            take = (ab >= 0) & ((aa < 0) | (mb > ma) | ((mb == ma) & (ab < aa)))
+            out[pre + "_max"], out[pre + "_arg"] = np.where(take, mb, ma), np.where(take, ab, aa)
+            for f in ("_sum", "_sumsq", "_over"):
+                out[pre + f] = getattr(self, pre + f) + getattr(other, pre + f)
+        return self._same(**out)
+
+    def with_ids(self, ids):
+        """The same statistics with every scenario id k in the arg arrays replaced by ids[k] (-1 stays)."""
+        ids = np.asarray(ids)
+        out = {name: getattr(self, name) for name in self.ARRAYS}
+        for pre in self.QUANTITIES:
+            a = out[pre + "_arg"]
+            out[pre + "_arg"] = np.where(a >= 0, ids[np.maximum(a, 0)], -1)
+        return self._same(**out)
+
+    def pack(self):
+        """-> one uint8 array holding every array (the payload of gather_waveform_stats)."""
+        return np.concatenate([getattr(self, name).reshape(-1).view(np.uint8) for name in self.ARRAYS])
+
+    def unpack(self, raw):
+        """A WaveformStats with this one's settings and shapes and the arrays of `raw` (what pack() of a peer produced)."""
+        raw = np.ascontiguousarray(raw, dtype=np.uint8)
+        out, o = {}, 0
+        for name in self.ARRAYS:
+            a = getattr(self, name)
+            out[name] = raw[o:o + a.nbytes].view(a.dtype).reshape(a.shape).copy()
+            o += a.nbytes
+        assert o == raw.size
+        return self._same(**out)
+
+
+def gather_waveform_stats(stats, world, ids=None):
+    """Waveform statistics of a multi-GPU sweep, like gather_distortion: `ids[k]` = global id of local scenario k is applied to the arg arrays on
+    the host, then ONE all_gather of the packed arrays (64 bytes per bus and rank) and a merge in rank order -- every rank returns the same
+    statistics, bit for bit.  world == 1 returns its argument (ids applied).  Every rank must have opened its accumulator with the same settings."""
+    return _gather_merge(stats, world, ids)
+
+
 def source_currents(I_N_bus, scale, shift, orders, cs=None):
     """Host expansion of the scale-and-shift form of the source currents (include/hpf.h "Source currents", csrc/hpf_sources.hpp):
     I_src[..., b, q] = (scale[..., b] e^(j orders[q] shift[..., b])) I_N_bus[b, q] -- scale units of the device of nonlinear bus b, their waveform
@@ -289,7 +380,7 @@ def sources_argument(sources, n_scen, nnl, Hn, where="solve_scenarios"):
 
 
 def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_iter_h=50, want_voltages=False, refill=True, distortion=None,
-                    branches=None, start=None, update="polar", sources=None):
+                    branches=None, start=None, update="polar", sources=None, waveform=None):
     """Monte-Carlo / what-if sweep on ONE GPU: every row of P, Q [n_scen][n] (p.u. loads, HG:197,372) is one scenario of the
     network `dm` (a DeviceModel) holds -- the reference's counterpart is one hpf() call per load case (HG:511).  Per scenario:
     reference start (HG:174-184), fundamental pf (HG:244), harmonic NR with the reference's stop rule (HG:536).
@@ -311,6 +402,10 @@ def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_i
     branches: None (default), or a dict {"rating": [nb] or None}: likewise for the handle's branch statistics (hpf_branch_stats_*: per line
     the RMS current over all harmonics against its rating, series loss, harmonic loss); the BranchStats are returned as a further last element,
     after the DistortionStats when both are asked for.
+    waveform: None (default), or a dict {"samples": T, "peak_limit": [n] or None, "crest_limit": x} (missing keys: 1024 samples, no limits):
+    likewise for the handle's waveform statistics (hpf_waveform_stats_*: per bus the peak of the time-domain voltage over one fundamental
+    period and its crest factor, the quantities that depend on the harmonics' phase angles); the WaveformStats are returned as a further last
+    element, after the DistortionStats and the BranchStats.
     start: None (default): the reference's flat start + pf for every scenario, today's behaviour bit for bit (a handle on which the caller
     has set a start state of its own is refused with ValueError: clear it, or pass it as `start`).  Otherwise a WARM START -- every
     scenario begins at one solved state of the feeder (the handle's start state, hpf_start_*), the pf phase is skipped (thresh_f / max_iter_f
@@ -345,11 +440,11 @@ def solve_scenarios(dm, P, Q, thresh_f=1e-6, max_iter_f=30, thresh_h=1e-4, max_i
         sources_argument(start["sources"], 1, dm.n - dm.m, dm.Hn, "solve_scenarios: start")
     with dm.update_mode(update):
         return _solve_scenarios_started(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion, branches, start,
-                                        update == "rectangular", src)
+                                        update == "rectangular", src, waveform)
 
 
 def _solve_scenarios_started(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion, branches, start, rect,
-                             src=None):
+                             src=None, waveform=None):
     """solve_scenarios inside the scope of its update mode: start state, accumulators, the sweep"""
     if start is None:
         if dm.has_start():
@@ -357,7 +452,7 @@ def _solve_scenarios_started(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_
     else:
         _set_start(dm, P, Q, start, thresh_f, max_iter_f, thresh_h, max_iter_h)
     try:
-        if distortion is None and branches is None:
+        if distortion is None and branches is None and waveform is None:
             return _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, False, False, start is not None,
                                     rect, src)
         if distortion is not None:
@@ -366,15 +461,20 @@ def _solve_scenarios_started(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_
         try:
             if branches is not None:
                 dm.branch_stats_begin(branches.get("rating"))
+            if waveform is not None:
+                dm.waveform_stats_begin(waveform.get("samples", 1024), waveform.get("peak_limit"), waveform.get("crest_limit", np.inf))
             res = _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion is not None,
-                                   branches is not None, start is not None, rect, src)
-            extra = (() if distortion is None else (dm.distortion_get(),)) + (() if branches is None else (dm.branch_stats_get(),))
+                                   branches is not None, start is not None, rect, src, waveform is not None)
+            extra = ((() if distortion is None else (dm.distortion_get(),)) + (() if branches is None else (dm.branch_stats_get(),)) +
+                     (() if waveform is None else (dm.waveform_stats_get(),)))
         finally:
             dm.set_option("distortion_id_base", 0)
             if distortion is not None:
                 dm.distortion_end()
             if branches is not None:
                 dm.branch_stats_end()
+            if waveform is not None:
+                dm.waveform_stats_end()
         return (res if want_voltages else (res,)) + extra
     finally:
         if start is not None:
@@ -406,7 +506,7 @@ def _set_start(dm, P, Q, start, thresh_f, max_iter_f, thresh_h, max_iter_h):
 
 
 def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_voltages, refill, distortion, branches, warm=False, rect=False,
-                     src=None):
+                     src=None, waveform=False):
     P = np.ascontiguousarray(np.atleast_2d(P), dtype=np.float64)
     Q = np.ascontiguousarray(np.atleast_2d(Q), dtype=np.float64)
     n_scen = P.shape[0]
@@ -435,6 +535,8 @@ def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_
             dm.distortion_add(a)
         if branches:
             dm.branch_stats_add(a)
+        if waveform:
+            dm.waveform_stats_add(a)
         for k in STAT_DTYPE.names:
             out[k][a:b] = st[k]
         if want_voltages:
@@ -484,7 +586,7 @@ def _solve_scenarios(dm, P, Q, thresh_f, max_iter_f, thresh_h, max_iter_h, want_
     per_call = n_scen if not want_voltages else max(dm.S_max, int(8e9 // (16 * dm.n * dm.Hn)))
     for a in range(0, n_scen, per_call):
         b = min(a + per_call, n_scen)
-        if distortion or branches:
+        if distortion or branches or waveform:
             dm.set_option("distortion_id_base", a)
         if src:
             dm.queue_sources(src[1][a:b], src[0])

@@ -301,6 +301,53 @@ int  hpf_branch_stats_get(hpf_handle* h, int64_t* counts, double* irms_max, int3
                           int32_t* lossh_arg, double* lossh_sum, double* lossh_sumsq);
 int  hpf_branch_stats_end(hpf_handle* h);
 
+/* Voltage waveforms: the time-domain voltage v(t) of every bus over one fundamental period, on the device -- its peak (insulation and capacitor
+ * stress) and crest factor, the one family of quantities here that depends on the harmonics' phase angles.  The reference has no counterpart.
+ * The handle does not know the harmonic orders: orders [Hn] (int32, 1 <= order <= 32767) come with the call, as for hpf_set_sources.  T = samples
+ * per fundamental period, a power of two, 64 <= T <= 4096.  U[i][q] = the rectangular voltage of bus i at harmonic position q (p.u. of the nominal
+ * PEAK voltage: |U[i][0]| is the amplitude of the fundamental).
+ *   table:   ct[j] = cos(j w), st[j] = sin(j w), w = 6.283185307179586 / T, j < T: the host libm's values of (double)j * w, the quadrant points
+ *            j = 0, T/4, T/2, 3T/4 set exactly to 0 and +-1; formed on the host, uploaded (hpf_waveform_table returns the same table)
+ *   sample:  k = 0 .. T-1:  j = (orders[q] k) & (T - 1)  (integer phase: no argument reduction),
+ *            v[k] = sum_q (U[q].re ct[j] - U[q].im st[j]),  sequentially over ascending q from 0.0; every product, difference and sum rounded on its own
+ *   peak  = max_k |v[k]|,  kpeak = its sample, ties to the SMALLEST k (inside a lane and across the wave reduction alike: the result does not
+ *           depend on the lane mapping); a NaN sample is the peak (numpy's max / argmax)
+ *   rms   = sqrt(0.5 s),  s = sum_q (U[q].re^2 + U[q].im^2) sequentially over ascending q
+ *   crest = peak / rms, formed as 1.4142135623730951 * (peak / sqrt(s)): sqrt 2 to the last bit for a pure sine of any amplitude (peak / sqrt(0.5 s)
+ *           misses that by an ulp for amplitudes such as 1.0); NaN or inf where s = 0
+ *   slack = (0.5 (pi/T)^2) sum_q orders[q]^2 |U[q]|,  |U| = sqrt(re^2 + im^2), pi = 3.141592653589793: the continuous peak lies in
+ *           [peak, peak + slack]  (at a true maximum v' = 0 and |v''| <= sum h^2 |U|)
+ * One wavefront per (scenario, bus) evaluates the T samples from the table in LDS (k_wave_peaks); no atomics.
+ * hpf_waveform_table: host only; HPF_E_ARG for a bad T or a NULL pointer.
+ * hpf_waveform: evaluates at the handle's CURRENT STATE under the rules of hpf_branch_flows (after hpf_solve, or after hpf_set_state alone: the
+ *   rectangular voltages are refreshed from the state first); every solver.  sel [n_sel]: bus indices whose samples go to v [S][n_sel][T], in the
+ *   caller's order (n_sel may be 0, v may be NULL).  peak, crest, slack [S][n] double, kpeak [S][n] int32; any of them may be NULL.  HPF_E_ARG,
+ *   checked on the host first, for a bad T, an order outside 1 .. 32767, a sel entry outside 0 .. n-1; HPF_E_STATE without a batch.
+ * Waveform statistics of a sweep (the third accumulator beside hpf_distortion_* and hpf_branch_stats_*: same state rules, same scenario lists, same
+ *   rule for who is added / skipped / deferred, same ids through "distortion_id_base"): per bus the peak against peak_limit[i] and the crest factor
+ *   against crest_limit.  k_wave_peaks writes both into a per-handle scratch [max_scenarios][n], one thread per bus folds them (k_wave_add, launched
+ *   where k_branch_add is -- every solver, the queue's harvest rounds, the waves of dense / meshed / pivoted handles): max, arg, over and counts do
+ *   not depend on slot count, queue chunk, scenario groups or number of GPUs; the four sum arrays do by rounding alone.  Closed (the default):
+ *   nothing is allocated or launched, every output of every entry point is unchanged; open: records and voltages are unchanged too (it only reads).
+ * hpf_waveform_stats_begin: allocate, zero, open (on an open one: reset).  peak_limit [n] (NULL: +inf); HPF_E_ARG for a NaN limit, a bad T or order.
+ * hpf_waveform_stats_add: fold the current batch in, scenario s under id first_id + s (first_id >= 0); HPF_E_STATE unless hpf_solve was the last
+ *   call that touched the batch, or with the accumulator closed.
+ * hpf_waveform_stats_get: copies out whichever arrays are non-NULL; leaves the accumulator open.  HPF_E_STATE when closed.
+ *   counts [3] int64: scenarios added, skipped, deferred
+ *   peak_max [n] double, peak_arg [n] int32 (ties: the smallest id; 0 / -1 before the first add), peak_sum, peak_sumsq [n] double,
+ *   peak_over [n] uint32: scenarios with peak[i] > peak_limit[i] (strictly);  crest_max .. crest_over: the same five against crest_limit
+ * hpf_waveform_stats_end: free (HPF_OK when already closed: a begin / end pair leaves hpf_debug_device_memory as it was); hpf_destroy frees an open
+ *   one.  All of them: HPF_E_ARG for a NULL handle, before any HIP call. */
+int  hpf_waveform_table(int T, double* ct, double* st);
+int  hpf_waveform(hpf_handle* h, const int32_t* orders, int T, int n_sel, const int32_t* sel, double* v, double* peak, int32_t* kpeak,
+                  double* crest, double* slack);
+int  hpf_waveform_stats_begin(hpf_handle* h, const int32_t* orders, int T, const double* peak_limit, double crest_limit);
+int  hpf_waveform_stats_add(hpf_handle* h, int first_id);
+int  hpf_waveform_stats_get(hpf_handle* h, int64_t* counts, double* peak_max, int32_t* peak_arg, double* peak_sum, double* peak_sumsq,
+                            uint32_t* peak_over, double* crest_max, int32_t* crest_arg, double* crest_sum, double* crest_sumsq,
+                            uint32_t* crest_over);
+int  hpf_waveform_stats_end(hpf_handle* h);
+
 /* Start state: warm-start the scenarios of a sweep from one solved case instead of the reference's flat start (HG:174-184) + pf (HG:244-275).  The
  * reference has no counterpart (hpf() always starts flat, HG:511-529).  The scenarios of a Monte-Carlo sweep sit close to each other: from the whole
  * raw state of the feeder solved at its nominal loads the harmonic NR needs 2 - 3 iterations where the flat start needs 20 - 30.

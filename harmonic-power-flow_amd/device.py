@@ -16,6 +16,9 @@ def _ip(a):
     return a.ctypes.data_as(_lib.c_int_p)
 
 
+BLOCK_TREE_MAX_B = 112       # widest bus block 2 Hn of the block tree (7 register tiles of 16 rows: tree_build_into of hpf_tree_plan.hpp)
+
+
 def is_radial(n, rowptr, col):
     """True if the admittance pattern is a tree spanning all buses (n-1 undirected edges, connected from bus 0)."""
     nnz = len(col)
@@ -65,6 +68,7 @@ class DeviceModel:
         self.Y_N = np.ascontiguousarray(Y_N, dtype=np.complex128)
         self.I_N = np.ascontiguousarray(I_N, dtype=np.complex128)
         N = 2 * self.n * self.Hn - 1 - self.c
+        auto = solver == "auto"
         if solver == "auto":
             # radial feeders: block-tree elimination; meshed networks (spanning tree + loop-closing lines) of 32 buses and more: the block-tree
             # path's bordered step (tried first, dense if the library refuses the topology: border beyond 16 384 unknowns) -- 0.3 - 1.1 ms per
@@ -74,6 +78,17 @@ class DeviceModel:
                 solver = "block_tree" if self.n >= 32 else "dense"
             else:
                 solver = "block_tree_or_dense" if self.n >= 32 else "dense"
+        if solver in ("block_tree", "block_tree_or_dense") and 2 * self.Hn > BLOCK_TREE_MAX_B:
+            # bus blocks wider than the block tree's kernels take (tree_build_into; hpf_create answers HPF_E_ARG): "auto" goes to the dense GPU
+            # path where the Jacobians fit, as it does for a meshed feeder the bordered step refuses; an explicit request is an error that
+            # names the limit
+            fits = assembly_only or 8 * N * N * int(max_scenarios) <= 240e9
+            if not (auto and fits):
+                raise ValueError("solver='block_tree': bus blocks of 2*Hn = %d rows (%d harmonics); the block tree takes 2*Hn <= %d%s"
+                                 % (2 * self.Hn, self.Hn, BLOCK_TREE_MAX_B,
+                                    (", and the dense path would need %.0f GB for the Jacobians of N = %d unknowns x %d scenarios"
+                                     % (8e-9 * N * N * max_scenarios, N, max_scenarios)) if auto else "; solver='dense' has no such limit"))
+            solver = "dense"
         self._solver_request = solver
         if solver == "block_tree_or_dense":
             solver = "block_tree"

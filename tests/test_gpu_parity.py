@@ -172,6 +172,11 @@ def test_fundamental_pf_kernels(name):
         mis = V_vec * np.conj(Y1.dot(V_vec)) + (net.P + 1j * net.Q)
         f_o = np.r_[mis.real[1:], mis.imag[c:]]
         assert np.abs(f[0] - f_o).max() <= 1e-13 * max(1.0, np.abs(f_o).max())
+        # hpf_fund_jacobian at the same state against the analytic Jacobian of tests/pf_ref.py (pinned to the oracle's pf on the host); every
+        # other state, batch and solver: tests/test_gpu_fund_pf.py
+        import pf_ref
+        J_o = np.asarray(pf_ref.jacobian(pf_ref.dense_Y1(rowptr, col, Yval[0], n), np.ones(n), np.zeros(n), c), dtype=float)
+        assert np.abs(dm.jacobian(0, fund=True) - J_o).max() <= 1e-12 * np.abs(J_o).max()
         n_iter, e, hist = dm.fund_pf(1e-6, 30)
         Vm, Va = dm.get_state()
         assert int(n_iter[0]) == int(g["n_iter_f"])

@@ -26,6 +26,19 @@ struct HipBackend {
 };
 using DevMem = DevOwner<HipBackend>;
 
+// One sweep accumulator of a handle (hpf_accum.hpp): everything is allocated from `mem` while open and goes in one clear().
+struct Accum {
+    explicit Accum(int* detail) : mem(detail) {}
+    bool open = false;
+    double* f = nullptr;              // [nf] max | sum | sum of squares of every quantity (AccumSlot)
+    int* arg = nullptr;               // [narg] scenario id of every maximum (-1: nothing added)
+    uint32_t* over = nullptr;         // [nover] scenarios over the limit (and whatever the feature keeps behind them)
+    long long* cnt = nullptr;         // [3] added, skipped, deferred
+    double* limit = nullptr;          // the per-owner limits
+    size_t nf = 0, narg = 0, nover = 0;
+    DevMem mem;                       // (last: it goes first)
+};
+
 // form of the 2x2 algebra of the all-linear subtrees in a block-tree Newton step (Tree::lin_form, decided by the planner)
 enum LinForm {
     LIN_ROOTS = 0,                    // uncontracted tree: one thread per (linear root, harmonic) walks its subtree (k_lin_factor / k_lin_back)
@@ -273,18 +286,12 @@ struct hpf_handle {
     double *d_Vmp = nullptr, *d_Vap = nullptr;   // [S][Hn*n] option "keep_previous_state": the state each scenario's LAST Newton step started from
     double *d_swapVm = nullptr, *d_swapVa = nullptr;   // [S][Hn*n] hpf_jacobian(_csr)_last: the current state while the kept one stands in its place
     int queue_chunk = 4;              // option "queue_chunk": iterations between two harvest / refill rounds of hpf_solve_queue
-    // distortion accumulator (hpf_distortion_*, hpf_distortion.hpp; allocated while open only).  Entries bus-major like the state: t = i*Hn + q for
-    // x of (bus i, harmonic position q), t = n*Hn + i for the THD of bus i
-    bool dist_open = false;
+    // distortion accumulator `dist` (hpf_distortion_*, hpf_distortion.hpp).  Entries bus-major like the state: t = i*Hn + q for x of (bus i,
+    // harmonic position q), t = n*Hn + i for the THD of bus i; f [3][n*Hn + n], arg [n*Hn + n], over [n*Hn + n] | [n][bins + 1] THD histogram
     bool solve_done = false;          // d_stats / the state belong to a finished hpf_solve of the current batch (hpf_distortion_add)
     int dist_bins = 0;
     int dist_id_base = 0;             // option "distortion_id_base": hpf_solve_queue adds scenario g of a call under id base + g
     double dist_thd_limit = 0.0, dist_hist_max = 0.0, dist_inv_w = 0.0;
-    double* d_dist_f = nullptr;       // [3][n*Hn + n] max | sum | sum of squares
-    int* d_dist_arg = nullptr;        // [n*Hn + n] scenario id of the max (-1: nothing added)
-    uint32_t* d_dist_u = nullptr;     // [n*Hn + n] scenarios over the limit | [n][bins + 1] THD histogram
-    long long* d_dist_cnt = nullptr;  // [3] added, skipped, deferred
-    double* d_dist_limit = nullptr;   // [Hn]
     // branch table (hpf_branch.hpp; built by the first call that needs it, absent otherwise): branch e = stored pair (i, j), i < j, numbered in
     // CSR order of its upper-triangle entry
     bool br_built = false;
@@ -293,25 +300,13 @@ struct hpf_handle {
     int *d_br_from = nullptr, *d_br_to = nullptr;
     hpf::cplx* d_br_y = nullptr;      // [nb][Hn] series admittances y = -Y, branch-major
     double* d_br_part = nullptr;      // [S_max][tiles][Hn] per-tile sums of loss[q][e] (k_branch_flows -> k_branch_loss_h)
-    // branch statistics accumulator (hpf_branch_stats_*; allocated while open only)
-    bool bstat_open = false;
-    double* d_bs_f = nullptr;         // [9][nb] irms max | sum | sumsq, loss the same three, harmonic loss the same three
-    int* d_bs_arg = nullptr;          // [3][nb] scenario id of the three maxima (-1: nothing added)
-    uint32_t* d_bs_over = nullptr;    // [nb] scenarios with irms above the rating
-    long long* d_bs_cnt = nullptr;    // [3] added, skipped, deferred
-    double* d_bs_rating = nullptr;    // [nb]
-    // waveform statistics accumulator (hpf_waveform_stats_*, hpf_waveform.hpp; allocated while open only)
-    bool wstat_open = false;
+    // branch statistics accumulator `bstat` (hpf_branch_stats_*): f [9][nb] irms, loss, harmonic loss; arg [3][nb]; over [nb] irms above the rating
+    // waveform statistics accumulator `wstat` (hpf_waveform_stats_*, hpf_waveform.hpp): f [6][n] peak, crest; arg, over [2][n]
     int ws_T = 0;                     // samples per fundamental period
     double ws_crest_limit = 0.0;
     double *d_ws_ct = nullptr, *d_ws_st = nullptr;   // [T] twiddle table (wave_table)
     int* d_ws_orders = nullptr;       // [Hn] harmonic orders
     double *d_ws_peak = nullptr, *d_ws_crest = nullptr;   // [S_max][n] scratch: k_wave_peaks -> k_wave_add
-    double* d_ws_f = nullptr;         // [6][n] peak max | sum | sumsq, crest max | sum | sumsq
-    int* d_ws_arg = nullptr;          // [2][n] scenario id of the two maxima (-1: nothing added)
-    uint32_t* d_ws_over = nullptr;    // [2][n] scenarios with the peak above peak_limit[i] | the crest factor above crest_limit
-    long long* d_ws_cnt = nullptr;    // [3] added, skipped, deferred
-    double* d_ws_limit = nullptr;     // [n] peak limits
     // start state (hpf_start_*; allocated while set only): one scenario's Vm, Va, U, E [n*Hn], bus-major like the state
     bool start_set = false;
     bool from_start = false;          // the current batch came from hpf_start_apply (until the next hpf_set_state): hpf_stat.flags bit 8
@@ -390,10 +385,7 @@ struct hpf_handle {
     // Owners of every device block above (hpf_devmem.hpp; declared last: they go first, and null the pointers they hold).  What lives as long as
     // the handle is in `mem`; buffers that come and go share one owner per group, allocated all-or-nothing and released by its clear().
     hpf::DevMem mem{&last_detail};        // model, per-scenario state, both trees, tree scratch, mesh / selected inversion / border, stamps, CSR export, swap, d_hist
-    hpf::DevMem dist_mem{&last_detail};   // d_dist_*
-    hpf::DevMem bstat_mem{&last_detail};  // d_bs_*
     hpf::DevMem br_mem{&last_detail};     // d_br_*
-    hpf::DevMem wstat_mem{&last_detail};  // d_ws_*
     hpf::DevMem start_mem{&last_detail};  // d_sVm, d_sVa, d_sU, d_sE
     hpf::DevMem src_mem{&last_detail};    // d_src
     hpf::DevMem qsrc_mem{&last_detail};   // d_qsrc, d_qorders
@@ -401,6 +393,7 @@ struct hpf_handle {
     hpf::DevMem prev_mem{&last_detail};   // d_Vmp, d_Vap
     hpf::DevMem resid_mem{&last_detail};  // d_respart, d_eta
     hpf::DevMem dense_mem{&last_detail};  // d_J, d_ipiv, d_info
+    hpf::Accum dist{&last_detail}, bstat{&last_detail}, wstat{&last_detail};   // the sweep accumulators (wstat.mem: d_ws_* too)
 };
 
 namespace hpf {

@@ -20,6 +20,7 @@
 
 #include <rocsolver/rocsolver.h>
 
+#include "hpf_accum.hpp"
 #include "hpf_branch.hpp"
 #include "hpf_distortion.hpp"
 #include "hpf_groups.hpp"
@@ -932,57 +933,33 @@ __global__ void k_queue_harvest(int n, int Hn, double thresh, int max_iter, cons
     }
 }
 
-// Distortion accumulator: the finished scenarios of a list are folded into the per-entry statistics (hpf_distortion.hpp).  One thread owns one
-// entry -- t < n*Hn: x of (bus, harmonic position) = t (bus-major like the state: consecutive threads read consecutive doubles and share the
-// bus's fundamental), t < n*Hn + n: the THD of a bus and its histogram row, t = n*Hn + n: the three scenario counters -- and walks the list in
-// order: plain loads and stores, no atomics, max / arg / counters independent of the order in which scenarios arrive.
-// List entry l: storage slots[l] (NULL: l; a negative slot ends the list), scenario number gids[l] (NULL: l) -> record stats[number], id
-// id_base + number.  queue: the caller is hpf_solve_queue (a scenario it only reports is deferred, dist_classify).
-__global__ void k_distortion_add(int n, int Hn, int L, const int* __restrict__ slots, const int* __restrict__ gids, int id_base, int queue,
-                                 const hpf_stat* __restrict__ stats, const double* __restrict__ Vm, const double* __restrict__ limit,
-                                 double thd_limit, double hist_max, double inv_w, int B, double* __restrict__ acc_f, int* __restrict__ acc_arg,
+// Distortion accumulator: the finished scenarios of a list (hpf_accum.hpp: the list, id and classification rules) are folded into the per-entry
+// statistics (hpf_distortion.hpp).  One thread owns one entry -- t < n*Hn: x of (bus, harmonic position) = t (bus-major like the state:
+// consecutive threads read consecutive doubles and share the bus's fundamental), t < n*Hn + n: the THD of a bus and its histogram row,
+// t = n*Hn + n: the three scenario counters -- and walks the list in order: plain loads and stores, no atomics, max / arg / counters independent
+// of the order in which scenarios arrive.  acc_f [3][T] max | sum | sumsq, acc_arg [T], acc_u [T] over | [n][B + 1] histogram.
+__global__ void k_distortion_add(int n, int Hn, AccumList list, const double* __restrict__ Vm, const double* __restrict__ limit, double thd_limit,
+                                 double hist_max, double inv_w, int B, double* __restrict__ acc_f, int* __restrict__ acc_arg,
                                  uint32_t* __restrict__ acc_u, long long* __restrict__ cnt) {
     const int E = n * Hn, T = E + n;
     const int t = blockIdx.x * TPB + threadIdx.x;
     if (t > T) return;
-    if (t == T) {
-        long long c[3] = {0, 0, 0};
-        for (int l = 0; l < L; ++l) {
-            if (slots && slots[l] < 0) break;
-            const hpf_stat st = stats[gids ? gids[l] : l];
-            c[dist_classify_start(st.flags, st.thd_max, queue != 0)] += 1;
-        }
-        for (int k = 0; k < 3; ++k) cnt[k] = cnt[k] + c[k];
-        return;
-    }
+    if (t == T) return accum_count(list, cnt);
     const int bus = t < E ? t / Hn : t - E, q = t < E ? t - bus * Hn : 0;
     const double lim = t < E ? limit[q] : thd_limit;
-    double mx = acc_f[t], sum = acc_f[(size_t)T + t], sumsq = acc_f[2 * (size_t)T + t];
-    int arg = acc_arg[t];
-    uint32_t over = acc_u[t];
+    AccumSlot st;
+    st.load(acc_f, acc_arg, acc_u, 0, T, t);
     uint32_t* hist = acc_u + (size_t)T + (size_t)bus * (B + 1);
-    bool any = false;
-    for (int l = 0; l < L; ++l) {
-        const int s = slots ? slots[l] : l;
-        if (s < 0) break;
-        const int g = gids ? gids[l] : l;
-        const hpf_stat st = stats[g];
-        if (dist_classify_start(st.flags, st.thd_max, queue != 0) != DIST_ADD) continue;
+    const bool any = accum_walk(list, [&](int s, int id) {
         const double* Vbus = Vm + (size_t)s * E + (size_t)bus * Hn;
         const double x = t < E ? dist_x(Vbus, q) : dist_thd(Vbus, Hn);
-        dist_fold(x, id_base + g, lim, mx, arg, sum, sumsq, over);
+        st.fold(x, id, lim);
         if (t >= E) {
             const int b = dist_bin(x, hist_max, inv_w, B);
             hist[b] = hist[b] + 1u;
         }
-        any = true;
-    }
-    if (!any) return;
-    acc_f[t] = mx;
-    acc_f[(size_t)T + t] = sum;
-    acc_f[2 * (size_t)T + t] = sumsq;
-    acc_arg[t] = arg;
-    acc_u[t] = over;
+    });
+    if (any) st.store(acc_f, acc_arg, acc_u, 0, T, t);
 }
 
 // U alone from (Vm, Va): hpf_branch_flows evaluates at the handle's current state, and hpf_set_state uploads Vm / Va only (E is left as the
@@ -1052,69 +1029,40 @@ __global__ void k_branch_loss_h(int Hn, int tiles, const double* __restrict__ pa
     loss_h[(size_t)s * Hn + q] = a;
 }
 
-// Branch statistics accumulator: the finished scenarios of a list (the list, id and classification rules of k_distortion_add) are folded into the
+// Branch statistics accumulator: the finished scenarios of a list (hpf_accum.hpp: the list, id and classification rules) are folded into the
 // per-branch statistics of irms, loss and harmonic loss.  One thread owns branch t (t = nb: the three scenario counters), walks the list in order
 // and forms each scenario's ascending-q sums itself (branch_fold): plain loads and stores, no atomics, so max / arg / over / counters do not
 // depend on the order in which scenarios arrive.  Workgroups of 64: the nb owners spread over nb / 64 compute units.
+// acc_f [9][nb], acc_arg [3][nb]: quantities irms, loss, harmonic loss; acc_over [nb]: irms alone has a limit, the rating.
 constexpr int BR_TPB = 64;
-__global__ __launch_bounds__(BR_TPB) void k_branch_add(int nb, int Hn, int n, int L, const int* __restrict__ slots, const int* __restrict__ gids,
-                                                       int id_base, int queue, const hpf_stat* __restrict__ stats, const cplx* __restrict__ U,
-                                                       const int* __restrict__ from, const int* __restrict__ to, const cplx* __restrict__ yb,
-                                                       const double* __restrict__ rating, double* __restrict__ acc_f, int* __restrict__ acc_arg,
-                                                       uint32_t* __restrict__ acc_over, long long* __restrict__ cnt) {
+__global__ __launch_bounds__(BR_TPB) void k_branch_add(int nb, int Hn, int n, AccumList list, const cplx* __restrict__ U, const int* __restrict__ from,
+                                                       const int* __restrict__ to, const cplx* __restrict__ yb, const double* __restrict__ rating,
+                                                       double* __restrict__ acc_f, int* __restrict__ acc_arg, uint32_t* __restrict__ acc_over,
+                                                       long long* __restrict__ cnt) {
     const int t = blockIdx.x * BR_TPB + threadIdx.x;
     if (t > nb) return;
-    if (t == nb) {
-        long long c[3] = {0, 0, 0};
-        for (int l = 0; l < L; ++l) {
-            if (slots && slots[l] < 0) break;
-            const hpf_stat st = stats[gids ? gids[l] : l];
-            c[dist_classify_start(st.flags, st.thd_max, queue != 0)] += 1;
-        }
-        for (int k = 0; k < 3; ++k) cnt[k] = cnt[k] + c[k];
-        return;
-    }
-    double mx[3], sum[3], sumsq[3];
-    int arg[3];
-    for (int k = 0; k < 3; ++k) {
-        mx[k] = acc_f[(size_t)(3 * k) * nb + t];
-        sum[k] = acc_f[(size_t)(3 * k + 1) * nb + t];
-        sumsq[k] = acc_f[(size_t)(3 * k + 2) * nb + t];
-        arg[k] = acc_arg[(size_t)k * nb + t];
-    }
-    uint32_t over = acc_over[t];
+    if (t == nb) return accum_count(list, cnt);
+    AccumSlot st[3];
+    for (int k = 0; k < 3; ++k) st[k].load(acc_f, acc_arg, k == 0 ? acc_over : nullptr, k, nb, t);
     const double lim = rating[t];
     const cplx* y = yb + (size_t)t * Hn;
     const size_t oi = (size_t)from[t] * Hn, oj = (size_t)to[t] * Hn;
-    bool any = false;
-    for (int l = 0; l < L; ++l) {
-        const int s = slots ? slots[l] : l;
-        if (s < 0) break;
-        const int g = gids ? gids[l] : l;
-        const hpf_stat st = stats[g];
-        if (dist_classify_start(st.flags, st.thd_max, queue != 0) != DIST_ADD) continue;
+    const bool any = accum_walk(list, [&](int s, int id) {
         const cplx* Us = U + (size_t)s * n * Hn;
         double irms, thd_i, loss_e, loss_harm;
         branch_fold(y, Us + oi, Us + oj, Hn, irms, thd_i, loss_e, loss_harm);
-        dist_fold(irms, id_base + g, lim, mx[0], arg[0], sum[0], sumsq[0], over);
-        branch_stat_fold(loss_e, id_base + g, mx[1], arg[1], sum[1], sumsq[1]);
-        branch_stat_fold(loss_harm, id_base + g, mx[2], arg[2], sum[2], sumsq[2]);
-        any = true;
-    }
+        st[0].fold(irms, id, lim);
+        branch_stat_fold(loss_e, id, st[1].max, st[1].arg, st[1].sum, st[1].sumsq);
+        branch_stat_fold(loss_harm, id, st[2].max, st[2].arg, st[2].sum, st[2].sumsq);
+    });
     if (!any) return;
-    for (int k = 0; k < 3; ++k) {
-        acc_f[(size_t)(3 * k) * nb + t] = mx[k];
-        acc_f[(size_t)(3 * k + 1) * nb + t] = sum[k];
-        acc_f[(size_t)(3 * k + 2) * nb + t] = sumsq[k];
-        acc_arg[(size_t)k * nb + t] = arg[k];
-    }
-    acc_over[t] = over;
+    for (int k = 0; k < 3; ++k) st[k].store(acc_f, acc_arg, k == 0 ? acc_over : nullptr, k, nb, t);
 }
 
 // Voltage waveforms (hpf_waveform.hpp): the T samples of v(t) at a bus, their peak (value, sample), crest factor and sampling slack.
-// Workgroup (4 buses, list entry): one wavefront per (scenario, bus).  The scenario list is the one of k_distortion_add (slots NULL: entry l is
-// storage l; a negative slot: nothing to do -- the lists of hpf_solve_queue are -1 from their end on, as k_queue_harvest relies on); with `stats`
-// given, a scenario the accumulator would not add (dist_classify_start) is not evaluated either.  buslist NULL: buses 0 .. nbus - 1.
+// Workgroup (4 buses, list entry): one wavefront per (scenario, bus).  The scenario list is the accumulators' (hpf_accum.hpp; id_base unused): a
+// negative slot: nothing to do (as k_queue_harvest relies on); with `stats` given, a scenario the accumulator would not add is not evaluated
+// either.  buslist NULL: buses 0 .. nbus - 1.
 // The table ct | st is staged in LDS once per workgroup: 16 T bytes, and LDS decides the occupancy -- T <= 1024: 16 KiB or less, the 8 workgroups
 // (32 waves) a CU can hold fit; T = 2048: 32 KiB -> 5 workgroups; T = 4096: 64 KiB -> 2 workgroups = 2 waves per SIMD.
 // Lane l evaluates the samples k = l, l + 64, ... in chunks of C per lane (C accumulators in registers), the harmonics in the OUTER loop, so each
@@ -1125,21 +1073,16 @@ __global__ __launch_bounds__(BR_TPB) void k_branch_add(int nb, int Hn, int n, in
 // its samples, [list entry's storage][b][T].  No atomics.
 constexpr int WV_TPB = 256, WV_BUSES = WV_TPB / 64;
 template <int C>
-__global__ __launch_bounds__(WV_TPB) void k_wave_peaks(int n, int Hn, int T, int nbus, const int* __restrict__ buslist, const int* __restrict__ slots,
-                                                       const int* __restrict__ gids, int queue, const hpf_stat* __restrict__ stats,
+__global__ __launch_bounds__(WV_TPB) void k_wave_peaks(int n, int Hn, int T, int nbus, const int* __restrict__ buslist, AccumList list,
                                                        const cplx* __restrict__ U, const int* __restrict__ orders, const double* __restrict__ ct,
                                                        const double* __restrict__ st, double* __restrict__ v, double* __restrict__ peak,
                                                        int* __restrict__ kpeak, double* __restrict__ crest, double* __restrict__ slack) {
     extern __shared__ __align__(16) unsigned char wv_lds[];
     double* lc = reinterpret_cast<double*>(wv_lds);
     double* ls = lc + T;
-    const int l = blockIdx.y;
-    const int s = slots ? slots[l] : l;
-    if (s < 0) return;                                   // (the whole workgroup: before the barrier)
-    if (stats) {
-        const hpf_stat rec = stats[gids ? gids[l] : l];
-        if (dist_classify_start(rec.flags, rec.thd_max, queue != 0) != DIST_ADD) return;
-    }
+    const AccumEntry e = list.entry(blockIdx.y);
+    const int s = e.slot;
+    if (s < 0 || e.cls != DIST_ADD) return;              // (the whole workgroup: before the barrier)
     for (int j = threadIdx.x; j < T; j += WV_TPB) {
         lc[j] = ct[j];
         ls[j] = st[j];
@@ -1193,56 +1136,24 @@ __global__ __launch_bounds__(WV_TPB) void k_wave_peaks(int n, int Hn, int T, int
 }
 
 // Waveform statistics accumulator, the twin of k_branch_add: one thread owns bus t (t = n: the three scenario counters), walks the list in order
-// and folds the peak and the crest factor k_wave_peaks left in the handle's scratch [storage][n] (same list, same classification, same ids):
-// plain loads and stores, no atomics.  acc_f [6][n]: peak max | sum | sumsq, crest max | sum | sumsq; acc_arg, acc_over [2][n].
-__global__ __launch_bounds__(BR_TPB) void k_wave_add(int n, int L, const int* __restrict__ slots, const int* __restrict__ gids, int id_base, int queue,
-                                                     const hpf_stat* __restrict__ stats, const double* __restrict__ peak,
-                                                     const double* __restrict__ crest, const double* __restrict__ peak_limit, double crest_limit,
-                                                     double* __restrict__ acc_f, int* __restrict__ acc_arg, uint32_t* __restrict__ acc_over,
-                                                     long long* __restrict__ cnt) {
+// and folds the peak and the crest factor k_wave_peaks left in the handle's scratch [storage][n] (same list, hpf_accum.hpp): plain loads and
+// stores, no atomics.  acc_f [6][n], acc_arg, acc_over [2][n]: quantities peak, crest.
+__global__ __launch_bounds__(BR_TPB) void k_wave_add(int n, AccumList list, const double* __restrict__ peak, const double* __restrict__ crest,
+                                                     const double* __restrict__ peak_limit, double crest_limit, double* __restrict__ acc_f,
+                                                     int* __restrict__ acc_arg, uint32_t* __restrict__ acc_over, long long* __restrict__ cnt) {
     const int t = blockIdx.x * BR_TPB + threadIdx.x;
     if (t > n) return;
-    if (t == n) {
-        long long c[3] = {0, 0, 0};
-        for (int l = 0; l < L; ++l) {
-            if (slots && slots[l] < 0) break;
-            const hpf_stat st = stats[gids ? gids[l] : l];
-            c[dist_classify_start(st.flags, st.thd_max, queue != 0)] += 1;
-        }
-        for (int k = 0; k < 3; ++k) cnt[k] = cnt[k] + c[k];
-        return;
-    }
-    double mx[2], sum[2], sumsq[2];
-    int arg[2];
-    uint32_t over[2];
-    for (int k = 0; k < 2; ++k) {
-        mx[k] = acc_f[(size_t)(3 * k) * n + t];
-        sum[k] = acc_f[(size_t)(3 * k + 1) * n + t];
-        sumsq[k] = acc_f[(size_t)(3 * k + 2) * n + t];
-        arg[k] = acc_arg[(size_t)k * n + t];
-        over[k] = acc_over[(size_t)k * n + t];
-    }
+    if (t == n) return accum_count(list, cnt);
+    AccumSlot st[2];
+    for (int k = 0; k < 2; ++k) st[k].load(acc_f, acc_arg, acc_over, k, n, t);
     const double lim = peak_limit[t];
-    bool any = false;
-    for (int l = 0; l < L; ++l) {
-        const int s = slots ? slots[l] : l;
-        if (s < 0) break;
-        const int g = gids ? gids[l] : l;
-        const hpf_stat st = stats[g];
-        if (dist_classify_start(st.flags, st.thd_max, queue != 0) != DIST_ADD) continue;
+    const bool any = accum_walk(list, [&](int s, int id) {
         const size_t o = (size_t)s * n + t;
-        dist_fold(peak[o], id_base + g, lim, mx[0], arg[0], sum[0], sumsq[0], over[0]);
-        dist_fold(crest[o], id_base + g, crest_limit, mx[1], arg[1], sum[1], sumsq[1], over[1]);
-        any = true;
-    }
+        st[0].fold(peak[o], id, lim);
+        st[1].fold(crest[o], id, crest_limit);
+    });
     if (!any) return;
-    for (int k = 0; k < 2; ++k) {
-        acc_f[(size_t)(3 * k) * n + t] = mx[k];
-        acc_f[(size_t)(3 * k + 1) * n + t] = sum[k];
-        acc_f[(size_t)(3 * k + 2) * n + t] = sumsq[k];
-        acc_arg[(size_t)k * n + t] = arg[k];
-        acc_over[(size_t)k * n + t] = over[k];
-    }
+    for (int k = 0; k < 2; ++k) st[k].store(acc_f, acc_arg, acc_over, k, n, t);
 }
 
 // a new scenario moves into every storage of the new list: loads, the reference's start (HG:174-184) with the fundamental entries from
@@ -1814,18 +1725,102 @@ int nr_pass(hpf_handle* h, double thresh, int max_iter, const int* mask) {
     return HPF_OK;
 }
 
-// one k_distortion_add launch on the handle's stream (the open accumulator of h): list, records and id rule as the kernel describes them
-int distortion_launch(hpf_handle* h, int L, const int* slots, const int* gids, int id_base, bool queue, const hpf_stat* stats) {
-    const int T = h->n * h->Hn + h->n;
-    hipLaunchKernelGGL(k_distortion_add, dim3((unsigned)((T + 1 + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, h->n, h->Hn, L, slots, gids, id_base,
-                       queue ? 1 : 0, stats, h->d_Vm, h->d_dist_limit, h->dist_thd_limit, h->dist_hist_max, h->dist_inv_w, h->dist_bins,
-                       h->d_dist_f, h->d_dist_arg, h->d_dist_u, h->d_dist_cnt);
-    return launch_status(h);
+// ---- sweep accumulators: the host lifecycle of an Accum, written once (hpf_accum.hpp) ----------------------------------------
+// the limit vector: the caller's `count` values, or +inf each (nothing is ever over); false: a NaN among them
+bool accum_limits(const double* src, size_t count, std::vector<double>& lim) {
+    lim.assign(count, (double)INFINITY);
+    for (size_t k = 0; src && k < count; ++k) {
+        if (src[k] != src[k]) return false;
+        lim[k] = src[k];
+    }
+    return true;
 }
 
-void distortion_free(hpf_handle* h) {
-    h->dist_mem.clear();
-    h->dist_open = false;
+void accum_close(Accum& a) {
+    a.mem.clear();
+    a.open = false;
+}
+
+// a (an open one is reset) <- nf statistics, narg ids, nover counters, all "nothing added yet", and the limits; whatever else the feature keeps
+// in a.mem is allocated by the caller afterwards (accum_close on failure)
+int accum_open(hpf_handle* h, Accum& a, size_t nf, size_t narg, size_t nover, const std::vector<double>& lim) {
+    HIPCHK(hipStreamSynchronize(h->stream));
+    accum_close(a);
+    int r;
+    if ((r = a.mem.alloc(&a.f, nf)) || (r = a.mem.alloc(&a.arg, narg)) || (r = a.mem.alloc(&a.over, nover)) || (r = a.mem.alloc(&a.cnt, (size_t)3)) ||
+        (r = a.mem.upload(&a.limit, lim))) {
+        accum_close(a);
+        return r;
+    }
+    HIPCHK(hipMemsetAsync(a.f, 0, sizeof(double) * (nf ? nf : 1), h->stream));           // (a feeder without branches: blocks of one element)
+    HIPCHK(hipMemsetAsync(a.arg, 0xff, sizeof(int) * (narg ? narg : 1), h->stream));
+    HIPCHK(hipMemsetAsync(a.over, 0, sizeof(uint32_t) * (nover ? nover : 1), h->stream));
+    HIPCHK(hipMemsetAsync(a.cnt, 0, sizeof(long long) * 3, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    a.nf = nf;
+    a.narg = narg;
+    a.nover = nover;
+    a.open = true;
+    return HPF_OK;
+}
+
+// hpf_*_end
+int accum_end(hpf_handle* h, Accum hpf_handle::*which) {
+    if (!h) return HPF_E_ARG;
+    if (!(h->*which).open) return HPF_OK;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    accum_close(h->*which);
+    return HPF_OK;
+}
+
+// hpf_*_add: the finished hpf_solve of the current batch, scenario s under id first_id + s, through the feature's launch
+int accum_add(hpf_handle* h, Accum hpf_handle::*which, int (*launch)(hpf_handle*, const AccumList&), int first_id) {
+    if (!h || first_id < 0) return HPF_E_ARG;
+    if (!(h->*which).open || !h->loads_set || !h->state_set || h->S < 1 || !h->solve_done) return HPF_E_STATE;
+    int r;
+    if ((r = launch(h, AccumList{h->S, nullptr, nullptr, first_id, 0, h->d_stats}))) return r;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return HPF_OK;
+}
+
+// hpf_*_get: the three scenario counters, after everything queued on the handle's stream ...
+int accum_counts(hpf_handle* h, const Accum& a, int64_t* counts) {
+    long long cnt[3];
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(cnt, a.cnt, sizeof(cnt), hipMemcpyDeviceToHost));
+    for (int k = 0; counts && k < 3; ++k) counts[k] = cnt[k];
+    return HPF_OK;
+}
+
+// ... and row k of `count` elements of one of its arrays (dst NULL: not wanted)
+template <class T>
+int accum_row(hpf_handle* h, const T* src, size_t k, size_t count, T* dst) {
+    if (dst && count) HIPCHK(hipMemcpy(dst, src + k * count, sizeof(T) * count, hipMemcpyDeviceToHost));
+    return HPF_OK;
+}
+
+// hpf_*_get of an accumulator whose arrays leave as they lie: the counters and the rows of f (three per quantity), arg and over in layout order
+int accum_get(hpf_handle* h, Accum hpf_handle::*which, size_t count, int64_t* counts, std::initializer_list<double*> f,
+              std::initializer_list<int32_t*> arg, std::initializer_list<uint32_t*> over) {
+    if (!h) return HPF_E_ARG;
+    const Accum& a = h->*which;
+    if (!a.open) return HPF_E_STATE;
+    int r = accum_counts(h, a, counts);
+    size_t k = 0;
+    for (double* dst : f) r = r ? r : accum_row(h, a.f, k++, count, dst);
+    k = 0;
+    for (int32_t* dst : arg) r = r ? r : accum_row(h, a.arg, k++, count, dst);
+    k = 0;
+    for (uint32_t* dst : over) r = r ? r : accum_row(h, a.over, k++, count, dst);
+    return r;
+}
+
+// one k_distortion_add launch on the handle's stream (the open accumulator of h)
+int distortion_launch(hpf_handle* h, const AccumList& list) {
+    const int T = h->n * h->Hn + h->n;
+    hipLaunchKernelGGL(k_distortion_add, dim3((unsigned)((T + 1 + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, h->n, h->Hn, list, h->d_Vm, h->dist.limit,
+                       h->dist_thd_limit, h->dist_hist_max, h->dist_inv_w, h->dist_bins, h->dist.f, h->dist.arg, h->dist.over, h->dist.cnt);
+    return launch_status(h);
 }
 
 void start_free(hpf_handle* h) {
@@ -1906,13 +1901,8 @@ int sources_fill(hpf_handle* h, int S, int form, const void* d_data, const int* 
     return launch_status(h);
 }
 
-void branch_stats_free(hpf_handle* h) {
-    h->bstat_mem.clear();
-    h->bstat_open = false;
-}
-
 void branch_free(hpf_handle* h) {
-    branch_stats_free(h);
+    accum_close(h->bstat);                               // (the statistics are per branch of this table)
     h->br_mem.clear();
     h->br_built = false;
 }
@@ -1947,28 +1937,22 @@ int branch_build(hpf_handle* h) {
     return HPF_OK;
 }
 
-// one k_branch_add launch on the handle's stream (the open accumulator of h): list, records and id rule as k_distortion_add
-int branch_add_launch(hpf_handle* h, int L, const int* slots, const int* gids, int id_base, bool queue, const hpf_stat* stats) {
-    hipLaunchKernelGGL(k_branch_add, dim3((unsigned)((h->nb + 1 + BR_TPB - 1) / BR_TPB)), dim3(BR_TPB), 0, h->stream, h->nb, h->Hn, h->n, L, slots,
-                       gids, id_base, queue ? 1 : 0, stats, h->d_U, h->d_br_from, h->d_br_to, h->d_br_y, h->d_bs_rating, h->d_bs_f, h->d_bs_arg,
-                       h->d_bs_over, h->d_bs_cnt);
+// one k_branch_add launch on the handle's stream (the open accumulator of h)
+int branch_add_launch(hpf_handle* h, const AccumList& list) {
+    hipLaunchKernelGGL(k_branch_add, dim3((unsigned)((h->nb + 1 + BR_TPB - 1) / BR_TPB)), dim3(BR_TPB), 0, h->stream, h->nb, h->Hn, h->n, list, h->d_U,
+                       h->d_br_from, h->d_br_to, h->d_br_y, h->bstat.limit, h->bstat.f, h->bstat.arg, h->bstat.over, h->bstat.cnt);
     return launch_status(h);
 }
 
-void wave_stats_free(hpf_handle* h) {
-    h->wstat_mem.clear();
-    h->wstat_open = false;
-}
-
-// one k_wave_peaks launch on the handle's stream: T samples (a valid T), the list of L entries, nbus buses per entry
-void wave_peaks_launch(hpf_handle* h, int T, int L, int nbus, const int* buslist, const int* slots, const int* gids, bool queue, const hpf_stat* stats,
-                       const int* orders, const double* ct, const double* st, double* v, double* peak, int* kpeak, double* crest, double* slack) {
-    if (L < 1 || nbus < 1) return;
-    const dim3 grid((unsigned)((nbus + WV_BUSES - 1) / WV_BUSES), (unsigned)L);
+// one k_wave_peaks launch on the handle's stream: T samples (a valid T), the list, nbus buses per entry
+void wave_peaks_launch(hpf_handle* h, int T, const AccumList& list, int nbus, const int* buslist, const int* orders, const double* ct, const double* st,
+                       double* v, double* peak, int* kpeak, double* crest, double* slack) {
+    if (list.L < 1 || nbus < 1) return;
+    const dim3 grid((unsigned)((nbus + WV_BUSES - 1) / WV_BUSES), (unsigned)list.L);
     const size_t lds = 2 * sizeof(double) * (size_t)T;               // (at most 64 KiB: no attribute needed)
 #define HPF_WAVE_LAUNCH(C)                                                                                                                       \
-    hipLaunchKernelGGL((k_wave_peaks<C>), grid, dim3(WV_TPB), lds, h->stream, h->n, h->Hn, T, nbus, buslist, slots, gids, queue ? 1 : 0, stats, \
-                       (const cplx*)h->d_U, orders, ct, st, v, peak, kpeak, crest, slack)
+    hipLaunchKernelGGL((k_wave_peaks<C>), grid, dim3(WV_TPB), lds, h->stream, h->n, h->Hn, T, nbus, buslist, list, (const cplx*)h->d_U, orders, ct, \
+                       st, v, peak, kpeak, crest, slack)
     switch (T / 64) {
         case 1: HPF_WAVE_LAUNCH(1); break;
         case 2: HPF_WAVE_LAUNCH(2); break;
@@ -1979,14 +1963,21 @@ void wave_peaks_launch(hpf_handle* h, int T, int L, int nbus, const int* buslist
 #undef HPF_WAVE_LAUNCH
 }
 
-// the open waveform accumulator of h takes a list: k_wave_peaks into the scratch, then k_wave_add (list, records and id rule as k_distortion_add)
-int wave_add_launch(hpf_handle* h, int L, const int* slots, const int* gids, int id_base, bool queue, const hpf_stat* stats) {
-    wave_peaks_launch(h, h->ws_T, L, h->n, nullptr, slots, gids, queue, stats, h->d_ws_orders, h->d_ws_ct, h->d_ws_st, nullptr, h->d_ws_peak, nullptr,
-                      h->d_ws_crest, nullptr);
-    hipLaunchKernelGGL(k_wave_add, dim3((unsigned)((h->n + 1 + BR_TPB - 1) / BR_TPB)), dim3(BR_TPB), 0, h->stream, h->n, L, slots, gids, id_base,
-                       queue ? 1 : 0, stats, h->d_ws_peak, h->d_ws_crest, h->d_ws_limit, h->ws_crest_limit, h->d_ws_f, h->d_ws_arg, h->d_ws_over,
-                       h->d_ws_cnt);
+// the open waveform accumulator of h takes a list: k_wave_peaks into the scratch, then k_wave_add
+int wave_add_launch(hpf_handle* h, const AccumList& list) {
+    wave_peaks_launch(h, h->ws_T, list, h->n, nullptr, h->d_ws_orders, h->d_ws_ct, h->d_ws_st, nullptr, h->d_ws_peak, nullptr, h->d_ws_crest, nullptr);
+    hipLaunchKernelGGL(k_wave_add, dim3((unsigned)((h->n + 1 + BR_TPB - 1) / BR_TPB)), dim3(BR_TPB), 0, h->stream, h->n, list, h->d_ws_peak, h->d_ws_crest,
+                       h->wstat.limit, h->ws_crest_limit, h->wstat.f, h->wstat.arg, h->wstat.over, h->wstat.cnt);
     return launch_status(h);
+}
+
+// every open accumulator of h takes the list (hpf_solve_queue, after a harvest round or a wave)
+int accum_add_open(hpf_handle* h, const AccumList& list) {
+    int r;
+    if (h->dist.open && (r = distortion_launch(h, list))) return r;
+    if (h->bstat.open && (r = branch_add_launch(h, list))) return r;
+    if (h->wstat.open && (r = wave_add_launch(h, list))) return r;
+    return HPF_OK;
 }
 
 // mode bits of hpf_stat.flags (include/hpf.h): begun at the handle's start state, rectangular update, per-scenario sources
@@ -2148,9 +2139,7 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
                            hlist, hg, newlist, base);
         hipLaunchKernelGGL(k_queue_harvest, dim3((unsigned)S_max), dim3(TPB), 0, h->stream, n, Hn, thresh, max_iter, hlist, hg, h->d_Vm,
                            h->d_Va, h->d_err, h->d_niter, h->d_pivflag, stat_mode_flags(h, warm), qst, qVm, qVa);
-        if (h->dist_open && distortion_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;   // (before the storages are refilled)
-        if (h->bstat_open && branch_add_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;
-        if (h->wstat_open && wave_add_launch(h, S_max, hlist, hg, h->dist_id_base, true, qst)) return HPF_E_HIP;
+        if (accum_add_open(h, AccumList{S_max, hlist, hg, h->dist_id_base, 1, qst})) return HPF_E_HIP;   // (before the storages are refilled)
         if (warm)
             hipLaunchKernelGGL(k_queue_init_start, grid2((int)count, S_max), dim3(TPB), 0, h->stream, n, Hn, newlist, slot_scen, qP, qQ, h->d_sVm,
                                h->d_sVa, h->d_sU, h->d_sE, h->d_P, h->d_Q, h->d_Vm, h->d_Va, h->d_U, h->d_E, h->d_niter, h->d_pivflag);
@@ -2794,9 +2783,7 @@ static int solve_queue_any(hpf_handle* h, int n_total, const double* P, const do
             if ((r = hpf_fund_pf(h, thresh_f, max_iter_f, nullptr, nullptr, nullptr))) return r;
         }
         if ((r = hpf_solve(h, thresh, max_iter, nullptr, nullptr, nullptr))) return r;
-        if (h->dist_open && (r = distortion_launch(h, S, nullptr, nullptr, h->dist_id_base + g0, true, h->d_stats))) return r;
-        if (h->bstat_open && (r = branch_add_launch(h, S, nullptr, nullptr, h->dist_id_base + g0, true, h->d_stats))) return r;
-        if (h->wstat_open && (r = wave_add_launch(h, S, nullptr, nullptr, h->dist_id_base + g0, true, h->d_stats))) return r;
+        if ((r = accum_add_open(h, AccumList{S, nullptr, nullptr, h->dist_id_base + g0, 1, h->d_stats}))) return r;
         if (stats && (r = hpf_get_stats(h, stats + g0))) return r;
         if (Vm && (r = hpf_get_state(h, Vm + (size_t)g0 * cnt, Va + (size_t)g0 * cnt))) return r;
     }
@@ -2858,66 +2845,41 @@ int hpf_get_step_residuals(hpf_handle* h, double* eta_last, double* eta_max) {
 
 int hpf_distortion_begin(hpf_handle* h, const double* limit, double thd_limit, double hist_max, int hist_bins) {
     if (!h || hist_bins < 1 || hist_bins > 256 || !(hist_max > 0.0) || isinf(hist_max) || thd_limit != thd_limit) return HPF_E_ARG;
-    std::vector<double> lim((size_t)h->Hn, (double)INFINITY);
-    for (int q = 0; limit && q < h->Hn; ++q) {
-        if (limit[q] != limit[q]) return HPF_E_ARG;
-        lim[q] = limit[q];
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    distortion_free(h);                                  // (an open accumulator is reset; the bin count may differ)
-    const size_t T = (size_t)h->n * h->Hn + h->n, nu = T + (size_t)h->n * (hist_bins + 1);
+    std::vector<double> lim;
+    if (!accum_limits(limit, (size_t)h->Hn, lim)) return HPF_E_ARG;
+    const size_t T = (size_t)h->n * h->Hn + h->n;
     int r;
-    DevMem& mem = h->dist_mem;
-    if ((r = mem.alloc(&h->d_dist_f, 3 * T)) || (r = mem.alloc(&h->d_dist_arg, T)) || (r = mem.alloc(&h->d_dist_u, nu)) ||
-        (r = mem.alloc(&h->d_dist_cnt, (size_t)3)) || (r = mem.upload(&h->d_dist_limit, lim))) {
-        distortion_free(h);
-        return r;
-    }
-    HIPCHK(hipMemsetAsync(h->d_dist_f, 0, sizeof(double) * 3 * T, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_dist_arg, 0xff, sizeof(int) * T, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_dist_u, 0, sizeof(uint32_t) * nu, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_dist_cnt, 0, sizeof(long long) * 3, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((r = accum_open(h, h->dist, 3 * T, T, T + (size_t)h->n * (hist_bins + 1), lim))) return r;   // (the histogram behind the over counters)
     h->dist_bins = hist_bins;
     h->dist_thd_limit = thd_limit;
     h->dist_hist_max = hist_max;
     h->dist_inv_w = (double)hist_bins / hist_max;
-    h->dist_open = true;
     return HPF_OK;
 }
 
-int hpf_distortion_add(hpf_handle* h, int first_id) {
-    if (!h || first_id < 0) return HPF_E_ARG;
-    if (!h->dist_open || !h->loads_set || !h->state_set || h->S < 1 || !h->solve_done) return HPF_E_STATE;
-    int r;
-    if ((r = distortion_launch(h, h->S, nullptr, nullptr, first_id, false, h->d_stats))) return r;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return HPF_OK;
-}
+int hpf_distortion_add(hpf_handle* h, int first_id) { return accum_add(h, &hpf_handle::dist, distortion_launch, first_id); }
 
 int hpf_distortion_get(hpf_handle* h, int64_t* counts, double* x_max, int32_t* x_arg, double* x_sum, double* x_sumsq, uint32_t* x_over,
                        double* thd_max, int32_t* thd_arg, double* thd_sum, double* thd_sumsq, uint32_t* thd_over, uint32_t* thd_hist) {
     if (!h) return HPF_E_ARG;
-    if (!h->dist_open) return HPF_E_STATE;
+    const Accum& a = h->dist;
+    if (!a.open) return HPF_E_STATE;
     const int n = h->n, Hn = h->Hn;
-    const size_t E = (size_t)n * Hn, T = E + n, nu = T + (size_t)n * (h->dist_bins + 1);
-    std::vector<double> f(3 * T);
-    std::vector<int32_t> arg(T);
-    std::vector<uint32_t> u(nu);
-    long long cnt[3];
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(f.data(), h->d_dist_f, sizeof(double) * 3 * T, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(arg.data(), h->d_dist_arg, sizeof(int32_t) * T, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(u.data(), h->d_dist_u, sizeof(uint32_t) * nu, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cnt, h->d_dist_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
-    for (int k = 0; counts && k < 3; ++k) counts[k] = cnt[k];
+    const size_t E = (size_t)n * Hn, T = E + n;
+    std::vector<double> f(a.nf);
+    std::vector<int32_t> arg(a.narg);
+    std::vector<uint32_t> u(a.nover);
+    int r;
+    if ((r = accum_counts(h, a, counts)) || (r = accum_row(h, a.f, 0, a.nf, f.data())) || (r = accum_row(h, a.arg, 0, a.narg, arg.data())) ||
+        (r = accum_row(h, a.over, 0, a.nover, u.data())))
+        return r;
     double* xf[3] = {x_max, x_sum, x_sumsq};
     double* tf[3] = {thd_max, thd_sum, thd_sumsq};
-    for (int a = 0; a < 3; ++a) {
-        if (tf[a]) memcpy(tf[a], f.data() + a * T + E, sizeof(double) * n);
-        if (!xf[a]) continue;
+    for (int k = 0; k < 3; ++k) {
+        if (tf[k]) memcpy(tf[k], f.data() + k * T + E, sizeof(double) * n);
+        if (!xf[k]) continue;
         for (int q = 0; q < Hn; ++q)                         // device bus-major -> ABI stacked order
-            for (int i = 0; i < n; ++i) xf[a][(size_t)q * n + i] = f[a * T + (size_t)i * Hn + q];
+            for (int i = 0; i < n; ++i) xf[k][(size_t)q * n + i] = f[k * T + (size_t)i * Hn + q];
     }
     for (int q = 0; q < Hn; ++q)
         for (int i = 0; i < n; ++i) {
@@ -2930,13 +2892,7 @@ int hpf_distortion_get(hpf_handle* h, int64_t* counts, double* x_max, int32_t* x
     return HPF_OK;
 }
 
-int hpf_distortion_end(hpf_handle* h) {
-    if (!h) return HPF_E_ARG;
-    if (!h->dist_open) return HPF_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    distortion_free(h);
-    return HPF_OK;
-}
+int hpf_distortion_end(hpf_handle* h) { return accum_end(h, &hpf_handle::dist); }
 
 int hpf_num_branches(const hpf_handle* h) { return h ? h->nb : HPF_E_ARG; }
 
@@ -2992,67 +2948,25 @@ int hpf_branch_flows(hpf_handle* h, double* I, double* irms, double* thd_i, doub
 
 int hpf_branch_stats_begin(hpf_handle* h, const double* rating) {
     if (!h) return HPF_E_ARG;
-    std::vector<double> lim((size_t)h->nb, (double)INFINITY);
-    for (int e = 0; rating && e < h->nb; ++e) {
-        if (rating[e] != rating[e]) return HPF_E_ARG;
-        lim[e] = rating[e];
-    }
+    const size_t nb = (size_t)h->nb;
+    std::vector<double> lim;
+    if (!accum_limits(rating, nb, lim)) return HPF_E_ARG;
     int r;
     if ((r = branch_build(h))) return r;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    branch_stats_free(h);                                // (an open accumulator is reset)
-    const size_t nb = (size_t)h->nb;
-    DevMem& mem = h->bstat_mem;
-    if ((r = mem.alloc(&h->d_bs_f, 9 * nb)) || (r = mem.alloc(&h->d_bs_arg, 3 * nb)) || (r = mem.alloc(&h->d_bs_over, nb)) ||
-        (r = mem.alloc(&h->d_bs_cnt, (size_t)3)) || (r = mem.upload(&h->d_bs_rating, lim))) {
-        branch_stats_free(h);
-        return r;
-    }
-    HIPCHK(hipMemsetAsync(h->d_bs_f, 0, sizeof(double) * (9 * nb ? 9 * nb : 1), h->stream));
-    HIPCHK(hipMemsetAsync(h->d_bs_arg, 0xff, sizeof(int) * (3 * nb ? 3 * nb : 1), h->stream));
-    HIPCHK(hipMemsetAsync(h->d_bs_over, 0, sizeof(uint32_t) * (nb ? nb : 1), h->stream));
-    HIPCHK(hipMemsetAsync(h->d_bs_cnt, 0, sizeof(long long) * 3, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->bstat_open = true;
-    return HPF_OK;
+    return accum_open(h, h->bstat, 9 * nb, 3 * nb, nb, lim);
 }
 
-int hpf_branch_stats_add(hpf_handle* h, int first_id) {
-    if (!h || first_id < 0) return HPF_E_ARG;
-    if (!h->bstat_open || !h->loads_set || !h->state_set || h->S < 1 || !h->solve_done) return HPF_E_STATE;
-    int r;
-    if ((r = branch_add_launch(h, h->S, nullptr, nullptr, first_id, false, h->d_stats))) return r;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return HPF_OK;
-}
+int hpf_branch_stats_add(hpf_handle* h, int first_id) { return accum_add(h, &hpf_handle::bstat, branch_add_launch, first_id); }
 
 int hpf_branch_stats_get(hpf_handle* h, int64_t* counts, double* irms_max, int32_t* irms_arg, double* irms_sum, double* irms_sumsq,
                          uint32_t* irms_over, double* loss_max, int32_t* loss_arg, double* loss_sum, double* loss_sumsq, double* lossh_max,
                          int32_t* lossh_arg, double* lossh_sum, double* lossh_sumsq) {
-    if (!h) return HPF_E_ARG;
-    if (!h->bstat_open) return HPF_E_STATE;
-    const size_t nb = (size_t)h->nb;
-    long long cnt[3];
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(cnt, h->d_bs_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
-    for (int k = 0; counts && k < 3; ++k) counts[k] = cnt[k];
-    double* f[9] = {irms_max, irms_sum, irms_sumsq, loss_max, loss_sum, loss_sumsq, lossh_max, lossh_sum, lossh_sumsq};
-    int32_t* a[3] = {irms_arg, loss_arg, lossh_arg};
-    for (int k = 0; k < 9; ++k)
-        if (f[k] && nb) HIPCHK(hipMemcpy(f[k], h->d_bs_f + k * nb, sizeof(double) * nb, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 3; ++k)
-        if (a[k] && nb) HIPCHK(hipMemcpy(a[k], h->d_bs_arg + k * nb, sizeof(int32_t) * nb, hipMemcpyDeviceToHost));
-    if (irms_over && nb) HIPCHK(hipMemcpy(irms_over, h->d_bs_over, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost));
-    return HPF_OK;
+    return accum_get(h, &hpf_handle::bstat, h ? (size_t)h->nb : 0, counts,
+                     {irms_max, irms_sum, irms_sumsq, loss_max, loss_sum, loss_sumsq, lossh_max, lossh_sum, lossh_sumsq}, {irms_arg, loss_arg, lossh_arg},
+                     {irms_over});
 }
 
-int hpf_branch_stats_end(hpf_handle* h) {
-    if (!h) return HPF_E_ARG;
-    if (!h->bstat_open) return HPF_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    branch_stats_free(h);
-    return HPF_OK;
-}
+int hpf_branch_stats_end(hpf_handle* h) { return accum_end(h, &hpf_handle::bstat); }
 
 // ---- voltage waveforms (hpf_waveform.hpp) ------------------------------------------------------------------------------------------------
 int hpf_waveform_table(int T, double* ct, double* st) {
@@ -3098,10 +3012,11 @@ int hpf_waveform(hpf_handle* h, const int32_t* orders, int T, int n_sel, const i
     if (samples && ((r = tmp.upload(&d_sel, (const int*)sel, (size_t)n_sel)) || (r = tmp.alloc(&d_v, (size_t)S * n_sel * T)))) return cleanup(r);
     hipLaunchKernelGGL(k_branch_refresh_u, grid2((int)count, S), dim3(TPB), 0, h->stream, (int)count, h->d_Vm, h->d_Va, h->d_U);
     // every bus for the per-bus outputs; the selected buses (in the caller's order, repeats allowed) once more for their samples
+    const AccumList every{S, nullptr, nullptr, 0, 0, nullptr};         // (the S scenarios of the batch, whatever their records say)
     if (per_bus)
-        wave_peaks_launch(h, T, S, n, nullptr, nullptr, nullptr, false, nullptr, d_orders, d_tab, d_tab + T, nullptr, d_f[0], d_k, d_f[1], d_f[2]);
+        wave_peaks_launch(h, T, every, n, nullptr, d_orders, d_tab, d_tab + T, nullptr, d_f[0], d_k, d_f[1], d_f[2]);
     if (samples)
-        wave_peaks_launch(h, T, S, n_sel, d_sel, nullptr, nullptr, false, nullptr, d_orders, d_tab, d_tab + T, d_v, nullptr, nullptr, nullptr, nullptr);
+        wave_peaks_launch(h, T, every, n_sel, d_sel, d_orders, d_tab, d_tab + T, d_v, nullptr, nullptr, nullptr, nullptr);
     if (launch_status(h)) return cleanup(HPF_E_HIP);
     if (hipStreamSynchronize(h->stream) != hipSuccess) return cleanup(HPF_E_HIP);
     for (int k = 0; k < 3; ++k)
@@ -3115,73 +3030,33 @@ int hpf_waveform_stats_begin(hpf_handle* h, const int32_t* orders, int T, const 
     if (!h) return HPF_E_ARG;
     if (!wave_args_ok(h, orders, T) || crest_limit != crest_limit) return HPF_E_ARG;
     const size_t n = (size_t)h->n;
-    std::vector<double> lim(n, (double)INFINITY);
-    for (size_t i = 0; peak_limit && i < n; ++i) {
-        if (peak_limit[i] != peak_limit[i]) return HPF_E_ARG;
-        lim[i] = peak_limit[i];
-    }
+    std::vector<double> lim;
+    if (!accum_limits(peak_limit, n, lim)) return HPF_E_ARG;
     std::vector<double> ct((size_t)T), st((size_t)T);
     wave_table(T, ct.data(), st.data());
-    HIPCHK(hipStreamSynchronize(h->stream));
-    wave_stats_free(h);                                  // (an open accumulator is reset; T may differ)
     int r;
-    DevMem& mem = h->wstat_mem;
+    if ((r = accum_open(h, h->wstat, 6 * n, 2 * n, 2 * n, lim))) return r;                 // (an open one is reset: T may differ)
+    DevMem& mem = h->wstat.mem;
     if ((r = mem.upload(&h->d_ws_ct, ct)) || (r = mem.upload(&h->d_ws_st, st)) || (r = mem.upload(&h->d_ws_orders, (const int*)orders, (size_t)h->Hn)) ||
-        (r = mem.alloc(&h->d_ws_peak, (size_t)h->S_max * n)) || (r = mem.alloc(&h->d_ws_crest, (size_t)h->S_max * n)) ||
-        (r = mem.alloc(&h->d_ws_f, 6 * n)) || (r = mem.alloc(&h->d_ws_arg, 2 * n)) || (r = mem.alloc(&h->d_ws_over, 2 * n)) ||
-        (r = mem.alloc(&h->d_ws_cnt, (size_t)3)) || (r = mem.upload(&h->d_ws_limit, lim))) {
-        wave_stats_free(h);
+        (r = mem.alloc(&h->d_ws_peak, (size_t)h->S_max * n)) || (r = mem.alloc(&h->d_ws_crest, (size_t)h->S_max * n))) {
+        accum_close(h->wstat);
         return r;
     }
-    HIPCHK(hipMemsetAsync(h->d_ws_f, 0, sizeof(double) * 6 * n, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_ws_arg, 0xff, sizeof(int) * 2 * n, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_ws_over, 0, sizeof(uint32_t) * 2 * n, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_ws_cnt, 0, sizeof(long long) * 3, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
     h->ws_T = T;
     h->ws_crest_limit = crest_limit;
-    h->wstat_open = true;
     return HPF_OK;
 }
 
-int hpf_waveform_stats_add(hpf_handle* h, int first_id) {
-    if (!h || first_id < 0) return HPF_E_ARG;
-    if (!h->wstat_open || !h->loads_set || !h->state_set || h->S < 1 || !h->solve_done) return HPF_E_STATE;
-    int r;
-    if ((r = wave_add_launch(h, h->S, nullptr, nullptr, first_id, false, h->d_stats))) return r;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return HPF_OK;
-}
+int hpf_waveform_stats_add(hpf_handle* h, int first_id) { return accum_add(h, &hpf_handle::wstat, wave_add_launch, first_id); }
 
 int hpf_waveform_stats_get(hpf_handle* h, int64_t* counts, double* peak_max, int32_t* peak_arg, double* peak_sum, double* peak_sumsq,
                            uint32_t* peak_over, double* crest_max, int32_t* crest_arg, double* crest_sum, double* crest_sumsq,
                            uint32_t* crest_over) {
-    if (!h) return HPF_E_ARG;
-    if (!h->wstat_open) return HPF_E_STATE;
-    const size_t n = (size_t)h->n;
-    long long cnt[3];
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(cnt, h->d_ws_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
-    for (int k = 0; counts && k < 3; ++k) counts[k] = cnt[k];
-    double* f[6] = {peak_max, peak_sum, peak_sumsq, crest_max, crest_sum, crest_sumsq};
-    int32_t* a[2] = {peak_arg, crest_arg};
-    uint32_t* o[2] = {peak_over, crest_over};
-    for (int k = 0; k < 6; ++k)
-        if (f[k]) HIPCHK(hipMemcpy(f[k], h->d_ws_f + k * n, sizeof(double) * n, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 2; ++k) {
-        if (a[k]) HIPCHK(hipMemcpy(a[k], h->d_ws_arg + k * n, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-        if (o[k]) HIPCHK(hipMemcpy(o[k], h->d_ws_over + k * n, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-    }
-    return HPF_OK;
+    return accum_get(h, &hpf_handle::wstat, h ? (size_t)h->n : 0, counts, {peak_max, peak_sum, peak_sumsq, crest_max, crest_sum, crest_sumsq},
+                     {peak_arg, crest_arg}, {peak_over, crest_over});
 }
 
-int hpf_waveform_stats_end(hpf_handle* h) {
-    if (!h) return HPF_E_ARG;
-    if (!h->wstat_open) return HPF_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    wave_stats_free(h);
-    return HPF_OK;
-}
+int hpf_waveform_stats_end(hpf_handle* h) { return accum_end(h, &hpf_handle::wstat); }
 
 int hpf_debug_stamps(hpf_handle* h, long long* out, int count) {
     if (!h || !out || !h->d_dbg || count > h->S_max * h->n * 8) return HPF_E_ARG;

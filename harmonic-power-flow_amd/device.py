@@ -375,13 +375,26 @@ class DeviceModel:
         self._chk(self.lib.hpf_get_step_residuals(self._h, _dp(last), _dp(big)), "hpf_get_step_residuals")
         return last, big
 
+    # -- the three sweep accumulators: what their begin / get pairs share ---------------------------------------
+    @staticmethod
+    def _limits(values, count):
+        """limit argument of an accumulator -> contiguous float64 [count], or None (no limits)"""
+        lim = None if values is None else np.ascontiguousarray(values, dtype=np.float64)
+        assert lim is None or lim.shape == (count,)
+        return lim
+
+    def _stats_get(self, cls, call, shapes, *settings):
+        """zeroed arrays of cls.ARRAYS in `shapes` -> filled by the C call -> cls(*settings, **arrays)"""
+        a = {name: np.zeros(shape, dtype=dt) for name, dt, shape in zip(cls.ARRAYS, cls.DTYPES, shapes)}
+        self._chk(getattr(self.lib, call)(self._h, *[a[name].ctypes.data_as(C.c_void_p) for name in cls.ARRAYS]), call)
+        return cls(*settings, **a)
+
     # -- distortion accumulator (hpf_distortion_*) ----------------------------------------------------------
     def distortion_begin(self, limit=None, thd_limit=np.inf, hist_max=1.0, bins=64):
         """Open (or reset) the handle's distortion accumulator: from now on every converged scenario hpf_solve_queue harvests, and every batch
         handed to distortion_add, is folded into per-bus / per-harmonic statistics on the device.  limit [Hn] (None: no limits): x_over counts
         the scenarios with x[q][i] > limit[q]; thd_limit likewise for THD; the THD histogram has `bins` (1..256) uniform bins on [0, hist_max)."""
-        lim = None if limit is None else np.ascontiguousarray(limit, dtype=np.float64)
-        assert lim is None or lim.shape == (self.Hn,)
+        lim = self._limits(limit, self.Hn)
         self._chk(self.lib.hpf_distortion_begin(self._h, _dp(lim) if lim is not None else None, float(thd_limit), float(hist_max), int(bins)),
                   "hpf_distortion_begin")
         self._dist = (lim, float(thd_limit), float(hist_max), int(bins))
@@ -393,14 +406,9 @@ class DeviceModel:
     def distortion_get(self):
         """-> sweep.DistortionStats of everything added since distortion_begin (arrays in the ABI's order [Hn][n]); the accumulator stays open."""
         from .sweep import DistortionStats
-        dist = getattr(self, "_dist", None)
-        bins = dist[3] if dist else 1
-        a = {name: np.zeros(shape, dtype=dt) for name, dt, shape in zip(
-            DistortionStats.ARRAYS, DistortionStats.DTYPES,
-            ((3,),) + ((self.Hn, self.n),) * 5 + ((self.n,),) * 5 + ((self.n, bins + 1),))}
-        self._chk(self.lib.hpf_distortion_get(self._h, *[a[name].ctypes.data_as(C.c_void_p) for name in DistortionStats.ARRAYS]),
-                  "hpf_distortion_get")
-        return DistortionStats(self.harmonics, dist[0], dist[1], dist[2], **a)
+        dist = getattr(self, "_dist", None) or (None, np.inf, 1.0, 1)
+        shapes = ((3,),) + ((self.Hn, self.n),) * 5 + ((self.n,),) * 5 + ((self.n, dist[3] + 1),)
+        return self._stats_get(DistortionStats, "hpf_distortion_get", shapes, self.harmonics, *dist[:3])
 
     def distortion_end(self):
         self._chk(self.lib.hpf_distortion_end(self._h), "hpf_distortion_end")
@@ -435,8 +443,7 @@ class DeviceModel:
         """Open (or reset) the handle's branch statistics: from now on every converged scenario hpf_solve_queue harvests, and every batch handed to
         branch_stats_add, is folded into per-branch statistics of irms, loss and harmonic loss on the device.  rating [nb] in p.u. (None: no
         ratings): irms_over counts the scenarios with irms[e] > rating[e]."""
-        r = None if rating is None else np.ascontiguousarray(rating, dtype=np.float64)
-        assert r is None or r.shape == (self.nb,)
+        r = self._limits(rating, self.nb)
         self._chk(self.lib.hpf_branch_stats_begin(self._h, _dp(r) if r is not None else None), "hpf_branch_stats_begin")
         self._brating = r
 
@@ -447,11 +454,8 @@ class DeviceModel:
     def branch_stats_get(self):
         """-> sweep.BranchStats of everything added since branch_stats_begin; the accumulator stays open."""
         from .sweep import BranchStats
-        nb = self.nb
-        a = {name: np.zeros((3,) if name == "counts" else (nb,), dtype=dt) for name, dt in zip(BranchStats.ARRAYS, BranchStats.DTYPES)}
-        self._chk(self.lib.hpf_branch_stats_get(self._h, *[a[name].ctypes.data_as(C.c_void_p) for name in BranchStats.ARRAYS]),
-                  "hpf_branch_stats_get")
-        return BranchStats(getattr(self, "_brating", None), **a)
+        shapes = ((3,),) + ((self.nb,),) * (len(BranchStats.ARRAYS) - 1)
+        return self._stats_get(BranchStats, "hpf_branch_stats_get", shapes, getattr(self, "_brating", None))
 
     def branch_stats_end(self):
         self._chk(self.lib.hpf_branch_stats_end(self._h), "hpf_branch_stats_end")
@@ -480,8 +484,7 @@ class DeviceModel:
         """Open (or reset) the handle's waveform statistics: from now on every converged scenario hpf_solve_queue harvests, and every batch handed to
         waveform_stats_add, has the peak and the crest factor of every bus's voltage waveform (T samples per period) folded into per-bus statistics
         on the device.  peak_limit [n] in p.u. (None: no limits) and crest_limit: the `over` arrays count the scenarios strictly above them."""
-        lim = None if peak_limit is None else np.ascontiguousarray(peak_limit, dtype=np.float64)
-        assert lim is None or lim.shape == (self.n,)
+        lim = self._limits(peak_limit, self.n)
         self._chk(self.lib.hpf_waveform_stats_begin(self._h, _ip(self._orders()), int(T), _dp(lim) if lim is not None else None, float(crest_limit)),
                   "hpf_waveform_stats_begin")
         self._wstat = (int(T), lim, float(crest_limit))
@@ -493,11 +496,8 @@ class DeviceModel:
     def waveform_stats_get(self):
         """-> sweep.WaveformStats of everything added since waveform_stats_begin; the accumulator stays open."""
         from .sweep import WaveformStats
-        a = {name: np.zeros((3,) if name == "counts" else (self.n,), dtype=dt) for name, dt in zip(WaveformStats.ARRAYS, WaveformStats.DTYPES)}
-        self._chk(self.lib.hpf_waveform_stats_get(self._h, *[a[name].ctypes.data_as(C.c_void_p) for name in WaveformStats.ARRAYS]),
-                  "hpf_waveform_stats_get")
-        T, lim, crest_limit = getattr(self, "_wstat", None) or (0, None, np.inf)
-        return WaveformStats(T, lim, crest_limit, **a)
+        shapes = ((3,),) + ((self.n,),) * (len(WaveformStats.ARRAYS) - 1)
+        return self._stats_get(WaveformStats, "hpf_waveform_stats_get", shapes, *(getattr(self, "_wstat", None) or (0, None, np.inf)))
 
     def waveform_stats_end(self):
         self._chk(self.lib.hpf_waveform_stats_end(self._h), "hpf_waveform_stats_end")

@@ -25,17 +25,82 @@ def gather_stats(rec, world):
     return torch.stack(parts, dim=1).reshape(-1, rec.shape[1])
 
 
-class DistortionStats:
+class _SweepStats:
+    """What the statistics containers of the three device accumulators share: plain NumPy arrays, per quantity `pre` of
+    QUANTITIES the five arrays pre_max / pre_arg / pre_sum / pre_sumsq (/ pre_over) of the device's statistic slot.  A subclass names its ARRAYS
+    and DTYPES (the order is the order of the C call and of pack()), its QUANTITIES, and supplies _settings() -- what two accumulators must have
+    been opened with alike to be merged -- and _same(**arrays): a container with this one's settings."""
+
+    @property
+    def added(self):
+        return int(self.counts[0])
+
+    def _mean(self, what):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return getattr(self, what + "_sum") / self.added
+
+    def _std(self, what):
+        m = self._mean(what)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.sqrt(np.maximum(getattr(self, what + "_sumsq") / self.added - m * m, 0.0))
+
+    def _worst(self, v, what, k):
+        order = np.argsort(-v, kind="stable")[:k]
+        return [(int(i), int(getattr(self, what + "_arg")[i]), float(v[i])) for i in order]
+
+    def merge(self, other):
+        """Statistics of the union of two disjoint sets of scenarios (another GPU's share, another piece of a sweep): max with the smaller-id
+        tie rule, integer adds, float adds.  Refuses different settings (limits, harmonics, samples, bins) or shapes with ValueError."""
+        if (type(other) is not type(self) or any(getattr(self, name).shape != getattr(other, name).shape for name in self.ARRAYS) or
+                not all(np.array_equal(a, b) for a, b in zip(self._settings(), other._settings()))):
+            raise ValueError("%s.merge: the two accumulators were opened with different settings or shapes" % type(self).__name__)
+        out = {}
+        for pre in self.QUANTITIES:
+            ma, aa, mb, ab = (getattr(o, pre + f) for o in (self, other) for f in ("_max", "_arg"))
+            take = (ab >= 0) & ((aa < 0) | (mb > ma) | ((mb == ma) & (ab < aa)))
+            out[pre + "_max"], out[pre + "_arg"] = np.where(take, mb, ma), np.where(take, ab, aa)
+        for name in self.ARRAYS:                             # counts, sums, sums of squares, over, histogram
+            if name not in out:
+                out[name] = getattr(self, name) + getattr(other, name)
+        return self._same(**out)
+
+    def with_ids(self, ids):
+        """The same statistics with every scenario id k in the arg arrays replaced by ids[k] (-1 stays)."""
+        ids = np.asarray(ids)
+        out = {name: getattr(self, name) for name in self.ARRAYS}
+        for pre in self.QUANTITIES:
+            a = out[pre + "_arg"]
+            out[pre + "_arg"] = np.where(a >= 0, ids[np.maximum(a, 0)], -1)
+        return self._same(**out)
+
+    def pack(self):
+        """-> one uint8 array holding every array (the payload of the gather_* functions)."""
+        return np.concatenate([getattr(self, name).reshape(-1).view(np.uint8) for name in self.ARRAYS])
+
+    def unpack(self, raw):
+        """A container with this one's settings and shapes and the arrays of `raw` (what pack() of a peer produced)."""
+        raw = np.ascontiguousarray(raw, dtype=np.uint8)
+        out, o = {}, 0
+        for name in self.ARRAYS:
+            a = getattr(self, name)
+            out[name] = raw[o:o + a.nbytes].view(a.dtype).reshape(a.shape).copy()
+            o += a.nbytes
+        assert o == raw.size
+        return self._same(**out)
+
+
+class DistortionStats(_SweepStats):
     """Per-bus / per-harmonic distortion statistics of a sweep, as the device accumulated them (hpf_distortion_*, include/hpf.h) -- a plain
     container of NumPy arrays.  x [Hn][n]: the fundamental magnitude |V_1| (p.u.) at harmonic position 0, the individual harmonic distortion
     |V_h| / |V_1| above; thd [n]: THD_F per bus.
     counts [3] int64: scenarios added, skipped (not converged, or a non-finite THD), deferred (reported by the queue, added by their re-solve);
     x_max / x_arg, thd_max / thd_arg: largest value and the scenario id it came from (ties: the smallest id; -1: nothing added);
     x_sum / x_sumsq, thd_sum / thd_sumsq: sums over the added scenarios; x_over / thd_over: scenarios above `limit[q]` / `thd_limit`;
-    thd_hist [n][bins + 1]: `bins` uniform bins on [0, hist_max), the last one counts thd >= hist_max."""
+    thd_hist [n][bins + 1]: `bins` uniform bins on [0, hist_max), the last one counts thd >= hist_max (merge adds it)."""
     ARRAYS = ("counts", "x_max", "x_arg", "x_sum", "x_sumsq", "x_over", "thd_max", "thd_arg", "thd_sum", "thd_sumsq", "thd_over", "thd_hist")
     DTYPES = (np.int64, np.float64, np.int32, np.float64, np.float64, np.uint32, np.float64, np.int32, np.float64, np.float64, np.uint32,
               np.uint32)
+    QUANTITIES = ("x", "thd")
 
     def __init__(self, harmonics, limit, thd_limit, hist_max, **arrays):
         self.harmonics = list(harmonics)
@@ -45,9 +110,11 @@ class DistortionStats:
             setattr(self, name, np.ascontiguousarray(arrays[name], dtype=dt))
         assert self.x_max.ndim == 2 and self.x_max.shape[0] == len(self.harmonics) and self.thd_hist.shape[0] == self.x_max.shape[1]
 
-    @property
-    def added(self):
-        return int(self.counts[0])
+    def _settings(self):
+        return self.harmonics, self.limit, self.thd_limit, self.hist_max
+
+    def _same(self, **arrays):
+        return DistortionStats(self.harmonics, self.limit, self.thd_limit, self.hist_max, **arrays)
 
     @property
     def bins(self):
@@ -55,15 +122,11 @@ class DistortionStats:
 
     def mean(self):
         """-> (mean of x [Hn][n], mean of thd [n]) over the added scenarios (NaN when nothing was added)."""
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return self.x_sum / self.added, self.thd_sum / self.added
+        return self._mean("x"), self._mean("thd")
 
     def std(self):
         """-> (population standard deviation of x [Hn][n], of thd [n]) from sum and sum of squares."""
-        mx, mt = self.mean()
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return (np.sqrt(np.maximum(self.x_sumsq / self.added - mx * mx, 0.0)),
-                    np.sqrt(np.maximum(self.thd_sumsq / self.added - mt * mt, 0.0)))
+        return self._std("x"), self._std("thd")
 
     def thd_percentile(self, p):
         """Per bus [n]: an UPPER BOUND of the p-th percentile of THD over the added scenarios, from the histogram -- the upper edge of the bin
@@ -79,60 +142,11 @@ class DistortionStats:
 
     def worst(self, k=1):
         """The k buses with the largest thd_max -> list of (bus, scenario id, value), largest first."""
-        order = np.argsort(-self.thd_max, kind="stable")[:k]
-        return [(int(i), int(self.thd_arg[i]), float(self.thd_max[i])) for i in order]
-
-    def merge(self, other):
-        """Statistics of the union of two disjoint sets of scenarios (another GPU's share, another piece of a sweep): max with the smaller-id
-        tie rule, integer adds, float adds.  Refuses different harmonics / limits / bins / shapes."""
-        if (self.harmonics != other.harmonics or self.x_max.shape != other.x_max.shape or self.thd_hist.shape != other.thd_hist.shape or
-                not np.array_equal(self.limit, other.limit) or self.thd_limit != other.thd_limit or self.hist_max != other.hist_max):
-            raise ValueError("DistortionStats.merge: the two accumulators were opened with different settings or shapes")
-        out = {"counts": self.counts + other.counts, "thd_hist": self.thd_hist + other.thd_hist}
-        for pre in ("x", "thd"):
-            ma, aa, mb, ab = (getattr(o, pre + f) for o in (self, other) for f in ("_max", "_arg"))
-            take = (ab >= 0) & ((aa < 0) | (mb > ma) | ((mb == ma) & (ab < aa)))
-            out[pre + "_max"], out[pre + "_arg"] = np.where(take, mb, ma), np.where(take, ab, aa)
-            for f in ("_sum", "_sumsq", "_over"):
-                out[pre + f] = getattr(self, pre + f) + getattr(other, pre + f)
-        return DistortionStats(self.harmonics, self.limit, self.thd_limit, self.hist_max, **out)
-
-    def with_ids(self, ids):
-        """The same statistics with every scenario id k in x_arg / thd_arg replaced by ids[k] (-1 stays)."""
-        ids = np.asarray(ids)
-        out = {name: getattr(self, name) for name in self.ARRAYS}
-        for f in ("x_arg", "thd_arg"):
-            a = out[f]
-            out[f] = np.where(a >= 0, ids[np.maximum(a, 0)], -1)
-        return DistortionStats(self.harmonics, self.limit, self.thd_limit, self.hist_max, **out)
-
-    def pack(self):
-        """-> one uint8 array holding every array (the payload of gather_distortion)."""
-        return np.concatenate([getattr(self, name).reshape(-1).view(np.uint8) for name in self.ARRAYS])
-
-    def unpack(self, raw):
-        """A DistortionStats with this one's settings and shapes and the arrays of `raw` (what pack() of a peer produced)."""
-        raw = np.ascontiguousarray(raw, dtype=np.uint8)
-        out, o = {}, 0
-        for name in self.ARRAYS:
-            a = getattr(self, name)
-            out[name] = raw[o:o + a.nbytes].view(a.dtype).reshape(a.shape).copy()
-            o += a.nbytes
-        assert o == raw.size
-        return DistortionStats(self.harmonics, self.limit, self.thd_limit, self.hist_max, **out)
-
-
-def gather_distortion(stats, world, ids=None):
-    """Distortion statistics of a multi-GPU sweep.  The device numbers the scenarios of a rank locally (`distortion_id_base` + index in the call,
-    `first_id` + s); `ids[k]` = global id of local scenario k (`scenario_ids(rank, world, per_rank)`) is applied to x_arg / thd_arg on the host
-    first, then ONE all_gather of the packed arrays (a few hundred KB per rank) and a merge in rank order -- every rank returns the same
-    statistics, bit for bit.  world == 1 returns its argument (ids applied), like gather_stats.  Every rank must have opened its accumulator
-    with the same settings."""
-    return _gather_merge(stats, world, ids)
+        return self._worst(self.thd_max, "thd", k)
 
 
 def _gather_merge(stats, world, ids):
-    """ids applied on the host, one all_gather of stats.pack(), unpack + merge in rank order (DistortionStats and BranchStats alike)."""
+    """ids applied on the host, one all_gather of stats.pack(), unpack + merge in rank order (any _SweepStats)."""
     if ids is not None:
         stats = stats.with_ids(ids)
     if world == 1:
@@ -152,7 +166,16 @@ def _gather_merge(stats, world, ids):
     return out
 
 
-class BranchStats:
+def gather_distortion(stats, world, ids=None):
+    """Distortion statistics of a multi-GPU sweep.  The device numbers the scenarios of a rank locally (`distortion_id_base` + index in the call,
+    `first_id` + s); `ids[k]` = global id of local scenario k (`scenario_ids(rank, world, per_rank)`) is applied to x_arg / thd_arg on the host
+    first, then ONE all_gather of the packed arrays (a few hundred KB per rank) and a merge in rank order -- every rank returns the same
+    statistics, bit for bit.  world == 1 returns its argument (ids applied), like gather_stats.  Every rank must have opened its accumulator
+    with the same settings."""
+    return _gather_merge(stats, world, ids)
+
+
+class BranchStats(_SweepStats):
     """Per-branch statistics of a sweep, as the device accumulated them (hpf_branch_stats_*, include/hpf.h) -- a plain container of NumPy arrays
     [nb] over the branches of the handle (DeviceModel.branches()).  Three quantities per scenario and branch: irms (RMS current over all harmonics,
     p.u.: the thermal loading), loss (series loss over all harmonics) and lossh (the harmonics' share, q >= 1).
@@ -172,20 +195,19 @@ class BranchStats:
         self.rating = np.full(nb, np.inf) if rating is None else np.array(rating, dtype=np.float64)
         assert self.counts.shape == (3,) and self.rating.shape == (nb,) and all(getattr(self, a).shape == (nb,) for a in self.ARRAYS[1:])
 
-    @property
-    def added(self):
-        return int(self.counts[0])
+    def _settings(self):
+        return (self.rating,)
+
+    def _same(self, **arrays):
+        return BranchStats(self.rating, **arrays)
 
     def mean(self, what="irms"):
         """-> mean [nb] of irms / loss / lossh over the added scenarios (NaN when nothing was added)."""
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return getattr(self, what + "_sum") / self.added
+        return self._mean(what)
 
     def std(self, what="irms"):
         """-> population standard deviation [nb] from sum and sum of squares."""
-        m = self.mean(what)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return np.sqrt(np.maximum(getattr(self, what + "_sumsq") / self.added - m * m, 0.0))
+        return self._std(what)
 
     def worst(self, k=1, what="irms", relative=False):
         """The k branches with the largest maximum of `what` (relative=True: of irms_max / rating) -> list of (branch, scenario id, value),
@@ -194,46 +216,7 @@ class BranchStats:
         if relative:
             with np.errstate(invalid="ignore", divide="ignore"):
                 v = np.where(np.isfinite(self.rating), v / self.rating, 0.0)
-        order = np.argsort(-v, kind="stable")[:k]
-        return [(int(e), int(getattr(self, what + "_arg")[e]), float(v[e])) for e in order]
-
-    def merge(self, other):
-        """Statistics of the union of two disjoint sets of scenarios: max with the smaller-id tie rule, integer adds, float adds.  Refuses
-        different ratings / shapes."""
-        if self.irms_max.shape != other.irms_max.shape or not np.array_equal(self.rating, other.rating):
-            raise ValueError("BranchStats.merge: the two accumulators were opened with different ratings or shapes")
-        out = {"counts": self.counts + other.counts, "irms_over": self.irms_over + other.irms_over}
-        for pre in self.QUANTITIES:
-            ma, aa, mb, ab = (getattr(o, pre + f) for o in (self, other) for f in ("_max", "_arg"))
-            take = (ab >= 0) & ((aa < 0) | (mb > ma) | ((mb == ma) & (ab < aa)))
-            out[pre + "_max"], out[pre + "_arg"] = np.where(take, mb, ma), np.where(take, ab, aa)
-            for f in ("_sum", "_sumsq"):
-                out[pre + f] = getattr(self, pre + f) + getattr(other, pre + f)
-        return BranchStats(self.rating, **out)
-
-    def with_ids(self, ids):
-        """The same statistics with every scenario id k in the arg arrays replaced by ids[k] (-1 stays)."""
-        ids = np.asarray(ids)
-        out = {name: getattr(self, name) for name in self.ARRAYS}
-        for pre in self.QUANTITIES:
-            a = out[pre + "_arg"]
-            out[pre + "_arg"] = np.where(a >= 0, ids[np.maximum(a, 0)], -1)
-        return BranchStats(self.rating, **out)
-
-    def pack(self):
-        """-> one uint8 array holding every array (the payload of gather_branch_stats)."""
-        return np.concatenate([getattr(self, name).reshape(-1).view(np.uint8) for name in self.ARRAYS])
-
-    def unpack(self, raw):
-        """A BranchStats with this one's rating and shapes and the arrays of `raw` (what pack() of a peer produced)."""
-        raw = np.ascontiguousarray(raw, dtype=np.uint8)
-        out, o = {}, 0
-        for name in self.ARRAYS:
-            a = getattr(self, name)
-            out[name] = raw[o:o + a.nbytes].view(a.dtype).reshape(a.shape).copy()
-            o += a.nbytes
-        assert o == raw.size
-        return BranchStats(self.rating, **out)
+        return self._worst(v, what, k)
 
 
 def gather_branch_stats(stats, world, ids=None):
@@ -243,7 +226,7 @@ def gather_branch_stats(stats, world, ids=None):
     return _gather_merge(stats, world, ids)
 
 
-class WaveformStats:
+class WaveformStats(_SweepStats):
     """Per-bus statistics of the voltage waveforms of a sweep, as the device accumulated them (hpf_waveform_stats_*, include/hpf.h) -- a plain
     container of NumPy arrays [n] over the buses.  Two quantities per scenario and bus: peak (largest |v(t)| over the `samples` samples of one
     fundamental period, p.u. of the nominal peak voltage) and crest (peak / rms; sqrt 2 for a pure sine).
@@ -263,68 +246,23 @@ class WaveformStats:
         self.peak_limit = np.full(n, np.inf) if peak_limit is None else np.array(peak_limit, dtype=np.float64)
         assert self.counts.shape == (3,) and self.peak_limit.shape == (n,) and all(getattr(self, a).shape == (n,) for a in self.ARRAYS[1:])
 
-    @property
-    def added(self):
-        return int(self.counts[0])
+    def _settings(self):
+        return self.samples, self.peak_limit, self.crest_limit
 
     def _same(self, **arrays):
         return WaveformStats(self.samples, self.peak_limit, self.crest_limit, **arrays)
 
     def mean(self, what="peak"):
         """-> mean [n] of peak / crest over the added scenarios (NaN when nothing was added)."""
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return getattr(self, what + "_sum") / self.added
+        return self._mean(what)
 
     def std(self, what="peak"):
         """-> population standard deviation [n] from sum and sum of squares."""
-        m = self.mean(what)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return np.sqrt(np.maximum(getattr(self, what + "_sumsq") / self.added - m * m, 0.0))
+        return self._std(what)
 
     def worst(self, k=1, what="peak"):
         """The k buses with the largest maximum of `what` -> list of (bus, scenario id, value), largest first."""
-        v = getattr(self, what + "_max")
-        order = np.argsort(-v, kind="stable")[:k]
-        return [(int(i), int(getattr(self, what + "_arg")[i]), float(v[i])) for i in order]
-
-    def merge(self, other):
-        """Statistics of the union of two disjoint sets of scenarios: max with the smaller-id tie rule, integer adds, float adds.  Refuses
-        different samples / limits / shapes."""
-        if (self.peak_max.shape != other.peak_max.shape or self.samples != other.samples or self.crest_limit != other.crest_limit or
-                not np.array_equal(self.peak_limit, other.peak_limit)):
-            raise ValueError("WaveformStats.merge: the two accumulators were opened with different settings or shapes")
-        out = {"counts": self.counts + other.counts}
-        for pre in self.QUANTITIES:
-            ma, aa, mb, ab = (getattr(o, pre + f) for o in (self, other) for f in ("_max", "_arg"))
-            take = (ab >= 0) & ((aa < 0) | (mb > ma) | ((mb == ma) & (ab < aa)))
-            out[pre + "_max"], out[pre + "_arg"] = np.where(take, mb, ma), np.where(take, ab, aa)
-            for f in ("_sum", "_sumsq", "_over"):
-                out[pre + f] = getattr(self, pre + f) + getattr(other, pre + f)
-        return self._same(**out)
-
-    def with_ids(self, ids):
-        """The same statistics with every scenario id k in the arg arrays replaced by ids[k] (-1 stays)."""
-        ids = np.asarray(ids)
-        out = {name: getattr(self, name) for name in self.ARRAYS}
-        for pre in self.QUANTITIES:
-            a = out[pre + "_arg"]
-            out[pre + "_arg"] = np.where(a >= 0, ids[np.maximum(a, 0)], -1)
-        return self._same(**out)
-
-    def pack(self):
-        """-> one uint8 array holding every array (the payload of gather_waveform_stats)."""
-        return np.concatenate([getattr(self, name).reshape(-1).view(np.uint8) for name in self.ARRAYS])
-
-    def unpack(self, raw):
-        """A WaveformStats with this one's settings and shapes and the arrays of `raw` (what pack() of a peer produced)."""
-        raw = np.ascontiguousarray(raw, dtype=np.uint8)
-        out, o = {}, 0
-        for name in self.ARRAYS:
-            a = getattr(self, name)
-            out[name] = raw[o:o + a.nbytes].view(a.dtype).reshape(a.shape).copy()
-            o += a.nbytes
-        assert o == raw.size
-        return self._same(**out)
+        return self._worst(getattr(self, what + "_max"), what, k)
 
 
 def gather_waveform_stats(stats, world, ids=None):

@@ -8,12 +8,13 @@ import tempfile
 import numpy as np
 
 import branch_ref as ref
+from distortion_emul import list_args
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "cpu_emul", "branch_emul.cpp")
 LIB = os.path.join(HERE, "cpu_emul", "libhpf_branch_emul.so")
 CSRC = os.path.join(os.path.dirname(HERE), "harmonic-power-flow_amd", "csrc")
-HDRS = [os.path.join(CSRC, f) for f in ("hpf_branch.hpp", "hpf_distortion.hpp", "hpf_assembly.hpp")]
+HDRS = [os.path.join(CSRC, f) for f in ("hpf_branch.hpp", "hpf_distortion.hpp", "hpf_accum.hpp", "hpf_assembly.hpp")]
 GOLD = os.path.join(HERE, "golden")
 INPUTS = os.path.join(GOLD, "inputs")
 
@@ -70,21 +71,20 @@ def empty(nb):
     return out
 
 
-def accumulate(fr, to, y, U, ids, flags, thd_max, rating=None, queue=False, into=None):
-    """The emulated k_branch_add over the scenarios U [S][Hn][n] with records (flags, thd_max) -> dict of the ABI's arrays; `into`: keep going"""
+def accumulate(fr, to, y, U, ids, flags, thd_max, rating=None, queue=False, into=None, slots=None, gids=None, id_base=0):
+    """The emulated k_branch_add over the storages U [S][Hn][n] and the list of distortion_emul.list_args with records (flags, thd_max) -> dict
+    of the ABI's arrays; `into`: keep going"""
     lib = load()
-    S, Hn, n = U.shape
+    _, Hn, n = U.shape
     nb = len(fr)
     fr, to, yb, Ub = _device_layout(fr, to, y, U)
     out = empty(nb) if into is None else into
     f = np.stack([out[k] for k in _F])
     arg = np.stack([out[k] for k in _A])
-    ids = np.ascontiguousarray(ids, dtype=np.int32)
-    flags = np.ascontiguousarray(flags, dtype=np.int32)
-    thd_max = np.ascontiguousarray(thd_max, dtype=np.float64)
+    head, recs = list_args(ids, flags, thd_max, slots, gids, id_base)
     lim = np.ascontiguousarray(np.full(nb, np.inf) if rating is None else rating, dtype=np.float64)
-    lib.emul_branch_add(C.c_int(n), C.c_int(Hn), C.c_int(nb), C.c_int(S), _p(fr), _p(to), _p(yb), _p(Ub), _p(ids), _p(flags), _p(thd_max),
-                        C.c_int(int(queue)), _p(lim), _p(out["counts"]), _p(f), _p(arg), _p(out["irms_over"]))
+    lib.emul_branch_add(C.c_int(n), C.c_int(Hn), C.c_int(nb), *head, _p(fr), _p(to), _p(yb), _p(Ub), *recs, C.c_int(int(queue)), _p(lim),
+                        _p(out["counts"]), _p(f), _p(arg), _p(out["irms_over"]))
     for i, k in enumerate(_F):
         out[k] = f[i].copy()
     for i, k in enumerate(_A):

@@ -3,6 +3,7 @@
 // (tests/branch_ref.py).  It is NOT part of libhpf.so and never on the product path.
 #include <vector>
 
+#include "hpf_accum.hpp"
 #include "hpf_branch.hpp"
 using namespace hpf;
 
@@ -57,20 +58,29 @@ void emul_branch_flows(int n, int Hn, int nb, int S, const int* from, const int*
     }
 }
 
-// the accumulator over a list of S scenarios (ids, flags, thd_max [S]: the records), entry by entry like k_branch_add; arrays accumulated INTO
-// what the caller passes (zeroed, arg = -1, before the first call): f [9][nb] (irms max | sum | sumsq, loss ..., harmonic loss ...), arg [3][nb]
-void emul_branch_add(int n, int Hn, int nb, int S, const int* from, const int* to, const cplx* y, const cplx* U, const int* ids, const int* flags,
-                     const double* thd_max, int queue, const double* rating, long long* counts, double* f, int* arg, uint32_t* over) {
-    for (int s = 0; s < S; ++s) counts[dist_classify(flags[s], thd_max[s], queue != 0)] += 1;
-    for (int e = 0; e < nb; ++e)
-        for (int s = 0; s < S; ++s) {
-            if (dist_classify(flags[s], thd_max[s], queue != 0) != DIST_ADD) continue;
+// the accumulator over a list as on the device (hpf_accum.hpp: L entries, slots / gids [L] or NULL, ids id_base + number; flags, thd_max [nrec]:
+// the records by scenario number), branch by branch like k_branch_add; arrays accumulated INTO what the caller passes (zeroed, arg = -1, before
+// the first call): f [9][nb] (irms max | sum | sumsq, loss ..., harmonic loss ...), arg [3][nb], over [nb]
+void emul_branch_add(int n, int Hn, int nb, int L, const int* slots, const int* gids, int id_base, int nrec, const int* from, const int* to,
+                     const cplx* y, const cplx* U, const int* flags, const double* thd_max, int queue, const double* rating, long long* counts,
+                     double* f, int* arg, uint32_t* over) {
+    std::vector<hpf_stat> stats((size_t)nrec);
+    for (int g = 0; g < nrec; ++g) stats[g].flags = flags[g], stats[g].thd_max = thd_max[g];
+    const AccumList list{L, slots, gids, id_base, queue, stats.data()};
+    accum_count(list, counts);
+    for (int e = 0; e < nb; ++e) {
+        AccumSlot st[3];
+        for (int k = 0; k < 3; ++k) st[k].load(f, arg, k == 0 ? over : nullptr, k, (size_t)nb, (size_t)e);
+        const bool any = accum_walk(list, [&](int s, int id) {
             const cplx* Us = U + (size_t)s * n * Hn;
             double irms, thd_i, loss_e, loss_harm;
             branch_fold(y + (size_t)e * Hn, Us + (size_t)from[e] * Hn, Us + (size_t)to[e] * Hn, Hn, irms, thd_i, loss_e, loss_harm);
-            dist_fold(irms, ids[s], rating[e], f[e], arg[e], f[(size_t)nb + e], f[2 * (size_t)nb + e], over[e]);
-            branch_stat_fold(loss_e, ids[s], f[3 * (size_t)nb + e], arg[(size_t)nb + e], f[4 * (size_t)nb + e], f[5 * (size_t)nb + e]);
-            branch_stat_fold(loss_harm, ids[s], f[6 * (size_t)nb + e], arg[2 * (size_t)nb + e], f[7 * (size_t)nb + e], f[8 * (size_t)nb + e]);
-        }
+            st[0].fold(irms, id, rating[e]);
+            branch_stat_fold(loss_e, id, st[1].max, st[1].arg, st[1].sum, st[1].sumsq);
+            branch_stat_fold(loss_harm, id, st[2].max, st[2].arg, st[2].sum, st[2].sumsq);
+        });
+        if (!any) continue;
+        for (int k = 0; k < 3; ++k) st[k].store(f, arg, k == 0 ? over : nullptr, k, (size_t)nb, (size_t)e);
+    }
 }
 }

@@ -3,6 +3,7 @@
 // tests can compare the device bit for bit.  It is NOT part of libhpf.so and never on the product path.
 #include <vector>
 
+#include "hpf_accum.hpp"
 #include "hpf_waveform.hpp"
 using namespace hpf;
 
@@ -52,17 +53,26 @@ void emul_waveform(int n, int Hn, int S, int T, const int* orders, const cplx* U
 
 double emul_wave_rms(int Hn, const cplx* U_bus) { return wave_rms(U_bus, Hn); }
 
-// the accumulator over a list of S scenarios (ids, flags, thd_max [S]: the records; peak, crest [S][n]), bus by bus like k_wave_add; arrays
-// accumulated INTO what the caller passes (zeroed, arg = -1, before the first call): f [6][n] (peak max | sum | sumsq, crest ...), arg, over [2][n]
-void emul_wave_add(int n, int S, const double* peak, const double* crest, const int* ids, const int* flags, const double* thd_max, int queue,
-                   const double* peak_limit, double crest_limit, long long* counts, double* f, int* arg, uint32_t* over) {
-    for (int s = 0; s < S; ++s) counts[dist_classify_start(flags[s], thd_max[s], queue != 0)] += 1;
-    for (int i = 0; i < n; ++i)
-        for (int s = 0; s < S; ++s) {
-            if (dist_classify_start(flags[s], thd_max[s], queue != 0) != DIST_ADD) continue;
-            const size_t o = (size_t)s * n + i, N = (size_t)n;
-            dist_fold(peak[o], ids[s], peak_limit[i], f[i], arg[i], f[N + i], f[2 * N + i], over[i]);
-            dist_fold(crest[o], ids[s], crest_limit, f[3 * N + i], arg[N + i], f[4 * N + i], f[5 * N + i], over[N + i]);
-        }
+// the accumulator over a list as on the device (hpf_accum.hpp: L entries, slots / gids [L] or NULL, ids id_base + number; flags, thd_max [nrec]:
+// the records by scenario number; peak, crest [storages][n]), bus by bus like k_wave_add; arrays accumulated INTO what the caller passes (zeroed,
+// arg = -1, before the first call): f [6][n] (peak max | sum | sumsq, crest ...), arg, over [2][n]
+void emul_wave_add(int n, int L, const int* slots, const int* gids, int id_base, int nrec, const double* peak, const double* crest, const int* flags,
+                   const double* thd_max, int queue, const double* peak_limit, double crest_limit, long long* counts, double* f, int* arg,
+                   uint32_t* over) {
+    std::vector<hpf_stat> stats((size_t)nrec);
+    for (int g = 0; g < nrec; ++g) stats[g].flags = flags[g], stats[g].thd_max = thd_max[g];
+    const AccumList list{L, slots, gids, id_base, queue, stats.data()};
+    accum_count(list, counts);
+    for (int i = 0; i < n; ++i) {
+        AccumSlot st[2];
+        for (int k = 0; k < 2; ++k) st[k].load(f, arg, over, k, (size_t)n, (size_t)i);
+        const bool any = accum_walk(list, [&](int s, int id) {
+            const size_t o = (size_t)s * n + i;
+            st[0].fold(peak[o], id, peak_limit[i]);
+            st[1].fold(crest[o], id, crest_limit);
+        });
+        if (!any) continue;
+        for (int k = 0; k < 2; ++k) st[k].store(f, arg, over, k, (size_t)n, (size_t)i);
+    }
 }
 }

@@ -9,7 +9,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "cpu_emul", "distortion_emul.cpp")
 LIB = os.path.join(HERE, "cpu_emul", "libhpf_distortion_emul.so")
-HDR = os.path.join(os.path.dirname(HERE), "harmonic-power-flow_amd", "csrc", "hpf_distortion.hpp")
+CSRC = os.path.join(os.path.dirname(HERE), "harmonic-power-flow_amd", "csrc")
+HDRS = [os.path.join(CSRC, f) for f in ("hpf_distortion.hpp", "hpf_accum.hpp")]
 GOLD = os.path.join(HERE, "golden")
 
 SHAPES = (lambda n, Hn, B: (3,),) + (lambda n, Hn, B: (Hn, n),) * 5 + (lambda n, Hn, B: (n,),) * 5 + (lambda n, Hn, B: (n, B + 1),)
@@ -18,9 +19,30 @@ DTYPES = (np.int64, np.float64, np.int32, np.float64, np.float64, np.uint32, np.
 
 
 def load():
-    if (not os.path.exists(LIB)) or os.path.getmtime(LIB) < max(os.path.getmtime(SRC), os.path.getmtime(HDR)):
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I", os.path.dirname(HDR), SRC, "-o", LIB])
+    if (not os.path.exists(LIB)) or os.path.getmtime(LIB) < max(os.path.getmtime(p) for p in [SRC] + HDRS):
+        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-I", CSRC, SRC, "-o", LIB])
     return C.CDLL(LIB)
+
+
+def list_args(ids, flags, thd_max=None, slots=None, gids=None, id_base=0):
+    """The device's scenario list (csrc/hpf_accum.hpp) from per-entry arrays, for the three emulated accumulators: entry l is storage slots[l]
+    (None: l; a negative slot ends the list) with scenario number gids[l] and id id_base + number.  gids None: the numbers are `ids`, the tests'
+    free labels (id_base 0); both None: the number is l, and the emulator gets NULL as the device does.  flags / thd_max [L] are the records of
+    the entries; the emulators index records by number -> (ctypes L, slots, gids, id_base, nrec), (ctypes flags, thd_max by number)."""
+    L = len(flags)
+    g = gids if gids is not None else ids
+    num = np.arange(L) if g is None else np.asarray(g)
+    assert gids is not None or id_base == 0
+    nrec = int(num.max()) + 1 if L else 0
+    fl, th = np.zeros(nrec, dtype=np.int32), np.zeros(nrec)
+    fl[num] = flags
+    if thd_max is not None:
+        th[num] = thd_max
+
+    def ptr(a):
+        return None if a is None else np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(C.c_void_p)
+
+    return ((C.c_int(L), ptr(slots), ptr(g), C.c_int(id_base), C.c_int(nrec)), (fl.ctypes.data_as(C.c_void_p), th.ctypes.data_as(C.c_void_p)))
 
 
 def empty(n, Hn, bins):
@@ -30,17 +52,43 @@ def empty(n, Hn, bins):
     return out
 
 
-def accumulate(Vm, ids, flags, n, Hn, limit=None, thd_limit=np.inf, hist_max=1.0, bins=64, queue=False, into=None):
-    """The emulated accumulator over the scenarios Vm [S][Hn*n] (stacked order) -> dict of the ABI's arrays; `into`: keep accumulating."""
+def accumulate(Vm, ids, flags, n, Hn, limit=None, thd_limit=np.inf, hist_max=1.0, bins=64, queue=False, into=None, slots=None, gids=None,
+               id_base=0):
+    """The emulated accumulator over the storages Vm [S][Hn*n] (stacked order) and the list of list_args -> dict of the ABI's arrays; `into`:
+    keep accumulating."""
     lib = load()
     out = empty(n, Hn, bins) if into is None else into
     Vm = np.ascontiguousarray(Vm, dtype=np.float64)
-    ids = np.ascontiguousarray(ids, dtype=np.int32)
-    flags = np.ascontiguousarray(flags, dtype=np.int32)
+    head, (fl, _) = list_args(ids, flags, None, slots, gids, id_base)
     lim = np.ascontiguousarray(np.full(Hn, np.inf) if limit is None else limit, dtype=np.float64)
-    lib.emul_distortion(C.c_int(n), C.c_int(Hn), C.c_int(len(ids)), Vm.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p),
-                        flags.ctypes.data_as(C.c_void_p), C.c_int(int(queue)), lim.ctypes.data_as(C.c_void_p), C.c_double(thd_limit),
-                        C.c_double(hist_max), C.c_int(bins), *[out[name].ctypes.data_as(C.c_void_p) for name in NAMES])
+    lib.emul_distortion(C.c_int(n), C.c_int(Hn), *head, Vm.ctypes.data_as(C.c_void_p), fl, C.c_int(int(queue)), lim.ctypes.data_as(C.c_void_p),
+                        C.c_double(thd_limit), C.c_double(hist_max), C.c_int(bins), *[out[name].ctypes.data_as(C.c_void_p) for name in NAMES])
+    return out
+
+
+LIST_TIED = (1, 4)       # list_cases: the tests give these two storages the same, largest state
+
+
+def list_cases(S=6):
+    """The list cases the three accumulator tests share, the rules of csrc/hpf_accum.hpp restated in NumPy over S = 6 storages:
+    (a) a -1 at position 3 of the slots: the entries from there on count for nothing (one of them did not converge: not even skipped);
+    (b) gids a permutation, id_base 1000: of the tied storages LIST_TIED the later one carries the smaller id;
+    (c) no slots, no gids (NULL to the emulator); a warm-started (bit 8) and a rectangular-update (bit 9) record that did not converge are
+        deferred whoever asks, one plain non-converged record is skipped.
+    -> [(keywords flags / slots / gids / id_base of accumulate, storages, ids, flags and deferred mask of the entries that count, counts)]"""
+    one = np.ones(S, dtype=np.int32)
+    fa, fc = one.copy(), one.copy()
+    fa[4] = 2
+    fc[[1, 3, 5]] = 256 | 2, 512 | 2, 2
+    out = []
+    for kw, counts in ((dict(flags=fa, slots=np.array([4, 2, 5, -1, 1, 0]), gids=None, id_base=0), [3, 0, 0]),
+                       (dict(flags=one, slots=None, gids=np.array([3, 5, 0, 4, 1, 2]), id_base=1000), [6, 0, 0]),
+                       (dict(flags=fc, slots=None, gids=None, id_base=0), [3, 1, 2])):
+        slots = np.arange(S) if kw["slots"] is None else kw["slots"]
+        k = int(np.argmax(slots < 0)) if (slots < 0).any() else S
+        num = np.arange(S) if kw["gids"] is None else kw["gids"]
+        fl = kw["flags"][:k]
+        out.append((kw, slots[:k], kw["id_base"] + num[:k], fl, ((fl & (256 | 512)) != 0) & ((fl & 1) == 0), counts))
     return out
 
 

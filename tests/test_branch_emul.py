@@ -15,6 +15,7 @@ import pytest
 
 import branch_emul as be
 import branch_ref as ref
+import distortion_emul as de
 
 from harmonic_power_flow_amd import api, sweep
 
@@ -178,6 +179,25 @@ def test_statistics_do_not_depend_on_order_or_splitting_and_the_queue_defers():
     _check(be.accumulate(*a, U, ids, fl2, thd2, rating, queue=False), ref.accumulate(fl, ids, fl2, ok, rating))
     none = be.accumulate(*a, U, ids, np.zeros_like(flags), thd, rating)
     assert none["counts"].tolist() == [0, 20, 0] and (none["irms_arg"] == -1).all() and not none["irms_max"].any() and not none["irms_over"].any()
+    # the list as the device walks it (slots, terminator, gids, id_base; bits 8 and 9): 6 storages of a 5-bus feeder, 3 harmonic positions
+    rng = np.random.default_rng(12)
+    S, n, Hn = 6, 5, 3
+    fr, to = np.array([0, 1, 1, 3], dtype=np.int32), np.array([1, 2, 3, 4], dtype=np.int32)
+    y = rng.uniform(0.5, 2.0, (Hn, 4)) - 1j * rng.uniform(0.5, 2.0, (Hn, 4))
+    U = rng.uniform(0.9, 1.1, (S, Hn, n)) * np.exp(1j * rng.uniform(-0.1, 0.1, (S, Hn, n)))
+    U[de.LIST_TIED[0]] = 1.0 + np.arange(n)                        # voltage differences of 1 and 2: every current and loss the largest ...
+    U[de.LIST_TIED[1]] = U[de.LIST_TIED[0]]                        # ... twice
+    fl = ref.flows(fr, to, y, U)
+    rating = np.array([be.midpoint_limit(fl["irms"][:, e]) for e in range(4)])
+    thd = np.full(S, 0.05)
+    for kw, sel, eids, efl, dfr, counts in de.list_cases(S):
+        for queue in (False, True):
+            got = be.accumulate(fr, to, y, U, None, kw["flags"], thd, rating, queue=queue, slots=kw["slots"], gids=kw["gids"], id_base=kw["id_base"])
+            want = ref.accumulate({k: fl[k][sel] for k in ("irms", "loss", "loss_harm")}, eids, efl, np.ones(len(sel), bool), rating, deferred=dfr)
+            assert got["counts"].tolist() == want["counts"].tolist() == counts
+            _check(got, want)
+        if kw["id_base"]:
+            assert all((got[k] == 1001).all() for k in ("irms_arg", "loss_arg", "lossh_arg"))   # 1000 + gid; the tie: not 1005, which came first
 
 
 def _stats(arrays, rating):

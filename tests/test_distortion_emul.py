@@ -90,6 +90,25 @@ def test_accumulating_in_two_calls_equals_one_and_the_queue_defers_reported_scen
     assert want["counts"].tolist() == [8, 1, 3]
     check(q, want)
     check(de.accumulate(Vm, ids, fl, n, Hn, queue=False, **cfg), ref.accumulate(Vm, ids, fl, n, Hn, **cfg))     # hpf_distortion_add: no deferral
+    # the list as the device walks it (slots, terminator, gids, id_base; bits 8 and 9): 6 storages x 5 buses x 3 harmonic positions
+    rng = np.random.default_rng(12)
+    S, n, Hn = 6, 5, 3
+    V = rng.uniform(-1.0, 1.0, (S, Hn, n))
+    V[:, 0, :] = rng.uniform(0.9, 1.1, (S, n))
+    V[:, 1:, :] *= 0.1
+    V[de.LIST_TIED[0], 0, :] = 1.5                                     # the largest fundamental and, three times the others' harmonics, the
+    V[de.LIST_TIED[0], 1:, :] = 0.3                                    # largest distortion of every bus ...
+    V[de.LIST_TIED[1]] = V[de.LIST_TIED[0]]                            # ... twice
+    Vm = V.reshape(S, Hn * n)
+    cfg = dict(limit=np.array([1.0, 0.05, 0.05]), thd_limit=0.07, hist_max=0.5, bins=7)
+    for kw, sel, eids, efl, dfr, counts in de.list_cases(S):
+        for queue in (False, True):
+            got = de.accumulate(Vm, None, kw["flags"], n, Hn, queue=queue, slots=kw["slots"], gids=kw["gids"], id_base=kw["id_base"], **cfg)
+            want = ref.accumulate(Vm[sel], eids, efl, n, Hn, deferred=dfr, **cfg)
+            assert got["counts"].tolist() == want["counts"].tolist() == counts
+            check(got, want)
+        if kw["id_base"]:
+            assert (got["x_arg"] == 1001).all() and (got["thd_arg"] == 1001).all()      # 1000 + gid; the tie: not 1005, which came first
 
 
 def test_nothing_added_leaves_the_initial_values():

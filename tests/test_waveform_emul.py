@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import distortion_emul as de
 import waveform_emul as we
 import waveform_ref as ref
 
@@ -160,6 +161,24 @@ def test_emulated_accumulator_matches_numpy_and_merge_of_halves_equals_the_whole
     pk = np.repeat(w["peak"][:1], 4, axis=0)
     a = we.accumulate(pk, pk, [40, 30, 20, 50], np.ones(4, np.int32), np.zeros(4))
     assert (a["peak_arg"] == 20).all() and (a["crest_arg"] == 20).all() and a["counts"].tolist() == [4, 0, 0]
+    # the list as the device walks it (slots, terminator, gids, id_base; bits 8 and 9): 6 storages x 5 buses
+    rng = np.random.default_rng(12)
+    S, n = 6, 5
+    pk, cr = rng.uniform(0.9, 1.1, (S, n)), rng.uniform(1.3, 1.5, (S, n))
+    pk[de.LIST_TIED[0]], cr[de.LIST_TIED[0]] = 1.2, 1.6             # the largest of every bus ...
+    pk[de.LIST_TIED[1]], cr[de.LIST_TIED[1]] = 1.2, 1.6             # ... twice
+    lim, thd = np.full(n, 1.0), np.full(S, 0.05)
+    for kw, sel, eids, efl, dfr, counts in de.list_cases(S):
+        for queue in (False, True):
+            got = we.accumulate(pk, cr, None, kw["flags"], thd, lim, 1.4, queue=queue, slots=kw["slots"], gids=kw["gids"], id_base=kw["id_base"])
+            want = ref.accumulate(pk[sel], cr[sel], eids, efl, np.ones(len(sel), bool), lim, 1.4, deferred=dfr)
+            assert got["counts"].tolist() == want["counts"].tolist() == counts
+            for f in ref.EXACT:
+                assert _same(got[f], want[f]), f
+            for f in ref.SUMS:
+                assert np.allclose(got[f], want[f], rtol=S * 2.0 ** -52, atol=0), f
+        if kw["id_base"]:
+            assert (got["peak_arg"] == 1001).all() and (got["crest_arg"] == 1001).all()     # 1000 + gid; the tie: not 1005, which came first
 
 
 def test_waveformstats_container_round_trips():

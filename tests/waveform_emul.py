@@ -6,11 +6,13 @@ import subprocess
 
 import numpy as np
 
+from distortion_emul import list_args
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "cpu_emul", "waveform_emul.cpp")
 LIB = os.path.join(HERE, "cpu_emul", "libhpf_waveform_emul.so")
 CSRC = os.path.join(os.path.dirname(HERE), "harmonic-power-flow_amd", "csrc")
-HDRS = [os.path.join(CSRC, f) for f in ("hpf_waveform.hpp", "hpf_distortion.hpp", "hpf_assembly.hpp")]
+HDRS = [os.path.join(CSRC, f) for f in ("hpf_waveform.hpp", "hpf_distortion.hpp", "hpf_accum.hpp", "hpf_assembly.hpp")]
 
 NAMES = ("counts", "peak_max", "peak_arg", "peak_sum", "peak_sumsq", "peak_over", "crest_max", "crest_arg", "crest_sum", "crest_sumsq",
          "crest_over")
@@ -66,21 +68,20 @@ def empty(n):
     return out
 
 
-def accumulate(peak, crest, ids, flags, thd_max, peak_limit=None, crest_limit=np.inf, queue=False, into=None):
-    """The emulated k_wave_add over the scenarios peak, crest [S][n] with records (flags, thd_max) -> dict of the ABI's arrays; `into`: keep going"""
+def accumulate(peak, crest, ids, flags, thd_max, peak_limit=None, crest_limit=np.inf, queue=False, into=None, slots=None, gids=None, id_base=0):
+    """The emulated k_wave_add over the storages peak, crest [S][n] and the list of distortion_emul.list_args with records (flags, thd_max) -> dict
+    of the ABI's arrays; `into`: keep going"""
     lib = load()
     peak, crest = np.ascontiguousarray(peak, dtype=np.float64), np.ascontiguousarray(crest, dtype=np.float64)
-    S, n = peak.shape
+    n = peak.shape[1]
     out = empty(n) if into is None else into
     f = np.stack([out[k] for k in _F])
     arg = np.stack([out[k] for k in _A])
     over = np.stack([out[k] for k in _O])
-    ids = np.ascontiguousarray(ids, dtype=np.int32)
-    flags = np.ascontiguousarray(flags, dtype=np.int32)
-    thd_max = np.ascontiguousarray(thd_max, dtype=np.float64)
+    head, recs = list_args(ids, flags, thd_max, slots, gids, id_base)
     lim = np.ascontiguousarray(np.full(n, np.inf) if peak_limit is None else peak_limit, dtype=np.float64)
-    lib.emul_wave_add(C.c_int(n), C.c_int(S), _p(peak), _p(crest), _p(ids), _p(flags), _p(thd_max), C.c_int(int(queue)), _p(lim),
-                      C.c_double(float(crest_limit)), _p(out["counts"]), _p(f), _p(arg), _p(over))
+    lib.emul_wave_add(C.c_int(n), *head, _p(peak), _p(crest), *recs, C.c_int(int(queue)), _p(lim), C.c_double(float(crest_limit)),
+                      _p(out["counts"]), _p(f), _p(arg), _p(over))
     for group, names in ((f, _F), (arg, _A), (over, _O)):
         for i, k in enumerate(names):
             out[k] = group[i].copy()

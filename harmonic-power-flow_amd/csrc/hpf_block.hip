@@ -26,6 +26,7 @@
 #include <thread>
 
 #include "hpf_internal.hpp"
+#include "hpf_batch_tile.hpp"
 #include "hpf_gj.hpp"
 #include "hpf_blk_jobs.hpp"
 #include "hpf_blk_invert_mfma.hpp"
@@ -719,7 +720,8 @@ int launch_back_w(hpf_handle* h, const TreeDev& T, const int* nodes, int count, 
 // at level 0, vector-only bordered buses above: 16 scenarios each) and its Gauss-Jordan / leaf workgroups (one per bus and scenario)
 // are independent of each other, so they share ONE grid -- batched workgroups first (they live longest) -- instead of two
 // dependent launches in the stream: the level costs the longer of the two lives, not their sum.  The three bodies carve their LDS
-// from one buffer (the largest of the three).  kind: 0 no batched workgroups, 1 k_leaf_batch's, 2 k_sleaf_batch's.
+// from one buffer (the largest of the three).  kind: 0 no batched workgroups, 1 k_leaf_batch's, 2 k_sleaf_batch's.  SB: scenarios per
+// batched workgroup (16, or 8 for narrow launches: HPF_BATCH_TILE8_MAX); both tiles carve the same LDS (the need of the larger).
 #ifndef HPF_BATCH_XCD
 #define HPF_BATCH_XCD 1    // k_level: the scenario-batched workgroups of a bus on one XCD (0: bus-fastest ids; A/B)
 #endif
@@ -729,7 +731,14 @@ constexpr int level_lds() {
     return a > b2 ? (a > c2 ? a : c2) : (b2 > c2 ? b2 : c2);
 }
 
-template <int B>
+// the scenario tile of a launch's batched workgroups (kind 1: lazy leaves, 2: bordered buses -- each with its own bound); hpf_tree_census[17] /
+// [18] report the last one taken
+inline int batch_tile(hpf_handle* h, int kind) {
+    if (kind == 1) return h->last_leaf_tile = batch_tile_of(h->cur_S, h->sw.leaf_tile8_max);
+    return h->last_batch_tile = batch_tile_of(h->cur_S, h->sw.batch_tile8_max);
+}
+
+template <int B, int SB>
 __global__ __launch_bounds__(256, HPF_Q_OCC) void k_level(
     Model M, TreeDev T, const int* __restrict__ nodes, int kind, int nbatch, int ngen, int b, int N, int Nc,
     const int* __restrict__ active, int S_cnt, const cplx* __restrict__ Uall, const cplx* __restrict__ Eall,
@@ -744,7 +753,7 @@ __global__ __launch_bounds__(256, HPF_Q_OCC) void k_level(
     // surviving wavefronts only).
     static_assert(64 * ((B + 16) / 16) <= 256, "k_level: blocks of up to 52 rows");
     __shared__ __attribute__((aligned(16))) double smem[level_lds<B>()];
-    const int ytiles = (S_cnt + LB_SB - 1) / LB_SB;
+    const int ytiles = BatchTile<SB>::tiles(S_cnt);
 #if HPF_BATCH_XCD
     // scenario-batched workgroups (homogeneous within a level): id -> (bus mod 8, scenario tile, bus / 8) -- every scenario tile of bus k on XCD
     // k mod 8, one after the other, in every scenario group alike: the bus's per-model operand images (27 - 33 KB) are fetched into ONE L2
@@ -760,11 +769,11 @@ __global__ __launch_bounds__(256, HPF_Q_OCC) void k_level(
 #endif
         if (tstamp && threadIdx.x == 0) atomicMin(tstamp, (unsigned long long)wall_clock64());
         if (kind == 1)
-            leaf_batch_body<B>(smem, bx, by, M, T, nodes, b, active, S_cnt, Uall, Eall, fall, wall, linAall, Call, Hall, chG, chH, chD, chy,
-                               lbimg, lfK, lfS, s0);
+            leaf_batch_body<B, SB>(smem, bx, by, M, T, nodes, b, active, S_cnt, Uall, Eall, fall, wall, linAall, Call, Hall, chG, chH, chD, chy,
+                                   lbimg, lfK, lfS, s0);
         else
-            sleaf_batch_body<B>(smem, bx, by, M, T, nodes, b, active, S_cnt, Uall, Eall, fall, wall, linAall, Call, Hall, I0all, chG, chH,
-                                chD, chy, sbimg, Zall, lfK, lfS, s0, dbg, ablate);
+            sleaf_batch_body<B, SB>(smem, bx, by, M, T, nodes, b, active, S_cnt, Uall, Eall, fall, wall, linAall, Call, Hall, I0all, chG, chH,
+                                    chD, chy, sbimg, Zall, lfK, lfS, s0, dbg, ablate);
         if (tstamp) {
             __syncthreads();
             if (threadIdx.x == 0) atomicMax(tstamp + 1, (unsigned long long)wall_clock64());
@@ -782,24 +791,31 @@ __global__ __launch_bounds__(256, HPF_Q_OCC) void k_level(
     }
 }
 
-template <int B>
-int launch_level(hpf_handle* h, const TreeDev& T, const int* nodes, int kind, int nbatch, int ngen, const int* active) {
+template <int B, int SB>
+int launch_level_tile(hpf_handle* h, const TreeDev& T, const int* nodes, int kind, int nbatch, int ngen, const int* active) {
     ScopedTimer t(h, T_GJ);
     unsigned long long* ts = nullptr;                   // device-clock stamps of this launch (timing leg)
     if (h->timing && h->d_tstamp && h->ts_next < hpf_handle::TS_CAP) ts = h->d_tstamp + 2 * (size_t)(h->ts_next++);
     const Tree& tr = active_tree(h);
-    const unsigned ytiles = (unsigned)((h->cur_S + LB_SB - 1) / LB_SB);
+    const unsigned ytiles = (unsigned)BatchTile<SB>::tiles(h->cur_S);
 #if HPF_BATCH_XCD
     const unsigned grid = (kind ? (unsigned)(((nbatch + 7) / 8) * 8) * ytiles : 0u) + (unsigned)ngen * (unsigned)h->cur_S;
 #else
     const unsigned grid = (kind ? (unsigned)nbatch * ytiles : 0u) + (unsigned)ngen * (unsigned)h->cur_S;
 #endif
     if (grid == 0) return HPF_OK;
-    hipLaunchKernelGGL((k_level<B>), dim3(grid), dim3(256), 0, h->cur_stream, h->M, T, nodes, kind, nbatch, ngen, 2 * h->Hn,
+    hipLaunchKernelGGL((k_level<B, SB>), dim3(grid), dim3(256), 0, h->cur_stream, h->M, T, nodes, kind, nbatch, ngen, 2 * h->Hn,
                        h->N, h->Nc, active, h->cur_S, h->d_U, h->d_E, h->d_fb, h->d_Z, h->d_w, h->d_linA, h->d_C, h->d_H, h->d_I0, h->d_chG,
                        h->d_chH, h->d_chD, h->d_chy, tr.d_Minv, tr.d_lbimg, tr.d_sbimg, h->d_lfK, h->d_lfS, h->d_dbg, h->sw.debug_ablate,
                        h->cur_s0, h->d_pivflag, h->piv_limit, ts);
     return launch_status(h);
+}
+
+// (a level without batched workgroups has no tile: it takes the kernel of the larger one)
+template <int B>
+int launch_level(hpf_handle* h, const TreeDev& T, const int* nodes, int kind, int nbatch, int ngen, const int* active) {
+    if (kind && batch_tile(h, kind) == 8) return launch_level_tile<B, 8>(h, T, nodes, kind, nbatch, ngen, active);
+    return launch_level_tile<B, LB_SB>(h, T, nodes, kind, nbatch, ngen, active);
 }
 
 // padded block size of the multi-wave MFMA path: 12 / 28 / 52, and 100 for 52 < b <= 100 (K <= 49: BASELINE config 5; the general
@@ -1206,7 +1222,9 @@ static int factor_level(hpf_handle* h, const Tree& T, const TreeDev& td, int l, 
     if (h->gj_mode != 1) return launch_factor_w<BW>(h, td, T.d_lvl_nodes + T.lvl_ptr[l], cnt, active);
     if (nbatch == 0) return launch_factor_q<BW>(h, td, fdesc, cnt, active, T.lvl_all_leaf[l] != 0);
     // the level's batched workgroups first (lazy leaves at level 0, vector-only bordered buses above: 16 scenarios each), then the rest
-    int r = kind == 2 ? launch_sleaf_batch<BW>(h, td, fdesc, nbatch, active) : launch_leaf_batch<BW>(h, td, fdesc, nbatch, active);
+    int r;
+    if (batch_tile(h, kind) == 8) r = kind == 2 ? launch_sleaf_batch<BW, 8>(h, td, fdesc, nbatch, active) : launch_leaf_batch<BW, 8>(h, td, fdesc, nbatch, active);
+    else r = kind == 2 ? launch_sleaf_batch<BW, LB_SB>(h, td, fdesc, nbatch, active) : launch_leaf_batch<BW, LB_SB>(h, td, fdesc, nbatch, active);
     if (!r && cnt > nbatch) r = launch_factor_q<BW>(h, td, fdesc + FDESC * (size_t)nbatch, cnt - nbatch, active, kind != 2);
     return r;
 }

@@ -340,6 +340,8 @@ struct hpf_handle {
     hpf::Tree ctree;                  // the same with pass-through buses contracted (multi-wave kernels, gj_mode 1)
     bool has_ctree = false;
     long long n_back_tails = 0;       // back sweeps whose bordered buses and constant-inverse leaves went through k_back_tail (hpf_tree_census[16])
+    int last_batch_tile = 0;          // scenarios per batched workgroup of the last factor launch with bordered buses (16 or 8; 0: none yet; hpf_tree_census[17])
+    int last_leaf_tile = 0;           // ... with lazy leaves (hpf_tree_census[18])
     long long n_back_walks = 0;       // back sweeps (scenario group x Newton step) whose Gauss-Jordan buses went through k_back_walk (hpf_tree_census[15])
     int auto_repivot = 1;             // hpf_solve repeats scenarios flagged by the static-pivot monitor with partial pivoting
     int* h_act[2] = {nullptr, nullptr};          // pinned copies of the slot counter d_nactive, and of the queue's `next` (poll_post / poll_wait: the host looks at chunk c - 1 while chunk c runs)

@@ -10,7 +10,11 @@
 // (scenario, harmonic) thread.  Results are the same quantities k_factor_q<B, true> leaves for a lazy leaf.
 #pragma once
 
-constexpr int LB_SB = 16;      // scenarios per workgroup
+// The factor bodies (leaf_batch_body / sleaf_batch_body) also come with tiles of SB = 8 scenarios, 32 threads per scenario: each thread then
+// walks half the rows and harmonics in sequence, for launches too narrow to fill the chip (HPF_BATCH_TILE8_MAX).  What a
+// row or a harmonic computes is the same operation for operation; the LDS arrays keep their shape and the MFMAs their 16 B-operand columns
+// (columns 8.. are zero).  The back-sweep bodies below, and every per-scenario HBM layout, know tiles of 16 only.
+constexpr int LB_SB = 16;      // scenarios per workgroup (the larger tile)
 constexpr int LBP = LB_SB + 1; // row stride of the [row][scenario] arrays in LDS (odd: a wave's 16 rows x 4 scenarios spread over the banks
                                // instead of meeting in one bank pair -- LDS bank conflicts per LDS instruction 6.9 -> see profiles/r03)
 
@@ -33,7 +37,7 @@ struct SleafImg {
 
 constexpr int LEAF_BATCH_LDS = 2 * 64 * LBP + LB_SB * 4 + LB_SB * 2;      // doubles
 
-template <int B>
+template <int B, int SB>
 __device__ __forceinline__ void leaf_batch_body(
     double* __restrict__ smem_, const int bx_, const int by_, const Model& M, const TreeDev& T, const int* __restrict__ nodes, int b, const int* __restrict__ active, int S_cnt,
     const cplx* __restrict__ Uall, const cplx* __restrict__ Eall, const double* __restrict__ fall, double* __restrict__ wall,
@@ -52,8 +56,10 @@ __device__ __forceinline__ void leaf_batch_body(
     const int tid = threadIdx.x, lane = tid & 63, lg = lane >> 4, jj = lane & 15;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = M.n, c = M.c, Hn = M.Hn;
-    const int sc = tid >> 4, l16 = tid & 15;                 // role mapping: 16 threads per scenario
-    const int sl = by_ * LB_SB + sc;                  // scenario inside the launch
+    using TL = BatchTile<SB>;                                // role mapping: TL::TPS threads per scenario (hpf_batch_tile.hpp)
+    constexpr int RPT = TL::ROWS;                            // rows per thread
+    const int sc = TL::scenario(tid), lt = TL::lane(tid);
+    const int sl = by_ * SB + sc;                            // scenario inside the launch
     const int ss = sl < S_cnt ? (active ? active[sl + s0] : sl + s0) : -1;      // slot -> scenario (active list; -1: frozen / empty slot)
     const bool live = ss >= 0;
     const int s = live ? ss : 0;
@@ -68,20 +74,20 @@ __device__ __forceinline__ void leaf_batch_body(
     double* V = Y + 64 * LBP;                              // [0 Lr; 0 Ahh^-1] y
     double* DL = V + 64 * LBP;                             // Delta_polar per scenario
     double* UK = DL + LB_SB * 4;                             // u = K (y0 + V0)
-    constexpr int QI = (H2 + 15) / 16;                       // harmonics per thread of a scenario's 16
+    constexpr int QI = TL::harmonics(H2);                    // harmonics per thread
     double sir[QI][4], glr[QI][4];                           // S_q^-1 and A(parent, k) of the thread's harmonics (same mapping in R2, K, F)
 
     // ---- R1. rows: right-hand side and the 2x2 term of the fundamental, the 2x2-algebra children folded in (k_factor_q, wave 0
     //      role + children, here one thread per (scenario, row) and every child of the bus in list order) -------------------------
     {
         // (the thread's four rows side by side: the children loop runs once, with the loads of all four rows in flight)
-        double e0[4] = {0.0, 0.0, 0.0, 0.0}, e1[4] = {0.0, 0.0, 0.0, 0.0}, ey[4] = {0.0, 0.0, 0.0, 0.0};
-        double a0[4] = {0.0, 0.0, 0.0, 0.0}, a1[4] = {0.0, 0.0, 0.0, 0.0}, ay[4] = {0.0, 0.0, 0.0, 0.0}, fy[4] = {0.0, 0.0, 0.0, 0.0};
-        bool ok[4];
-        cplx ukr[4], ekr[4];
+        double e0[RPT] = {}, e1[RPT] = {}, ey[RPT] = {};
+        double a0[RPT] = {}, a1[RPT] = {}, ay[RPT] = {}, fy[RPT] = {};
+        bool ok[RPT];
+        cplx ukr[RPT], ekr[RPT];
 #pragma unroll
-        for (int pz = 0; pz < 4; ++pz) {
-            const int row = l16 + 16 * pz, q = row >> 1, tr_ = row & 1;
+        for (int pz = 0; pz < RPT; ++pz) {
+            const int row = TL::row(tid, pz), q = row >> 1, tr_ = row & 1;
             ok[pz] = live && row < b && loc_valid(n, c, k, row);
             ukr[pz] = cplx{0.0, 0.0};
             ekr[pz] = cplx{0.0, 0.0};
@@ -107,9 +113,9 @@ __device__ __forceinline__ void leaf_batch_body(
             const int4 cr = c3[cp];
             const int ch = cr.x;
 #pragma unroll
-            for (int pz = 0; pz < 4; ++pz) {
+            for (int pz = 0; pz < RPT; ++pz) {
                 if (!ok[pz]) continue;
-                const int row = l16 + 16 * pz, q = row >> 1, tr_ = row & 1;
+                const int row = TL::row(tid, pz), q = row >> 1, tr_ = row & 1;
                 const cplx uk = ukr[pz], ek = ekr[pz];
                 const cplx ydn = M.Y[(size_t)cr.y * Hn + q], yup = M.Y[(size_t)cr.z * Hn + q];
                 const cplx uc = U[(size_t)ch * Hn + q], ec = E[(size_t)ch * Hn + q];
@@ -130,9 +136,10 @@ __device__ __forceinline__ void leaf_batch_body(
             }
         }
 #pragma unroll
-        for (int pz = 0; pz < 4; ++pz) {
-            const int row = l16 + 16 * pz;
+        for (int pz = 0; pz < RPT; ++pz) {
+            const int row = TL::row(tid, pz);
             Y[row * LBP + sc] = ok[pz] ? fy[pz] + ay[pz] - ey[pz] : 0.0;
+            if (SB < BATCH_COLS) Y[row * LBP + SB + sc] = 0.0;      // (the B-operand columns behind the tile)
             if (row < 2) {
                 DL[sc * 4 + row * 2] = ok[pz] ? a0[pz] - e0[pz] : 0.0;
                 DL[sc * 4 + row * 2 + 1] = ok[pz] ? a1[pz] - e1[pz] : 0.0;
@@ -142,7 +149,7 @@ __device__ __forceinline__ void leaf_batch_body(
     // ---- R2. harmonics: S_q^-1, the coupling blocks with the parent (H is kept for the back sweep), the position-0 borders ----
 #pragma unroll
     for (int it = 0; it < QI; ++it) {
-        const int q = l16 + 16 * it;
+        const int q = TL::harmonic(tid, it);
         double si[4] = {1.0, 0.0, 0.0, 1.0}, g4[4] = {0.0, 0.0, 0.0, 0.0}, h4[4] = {0.0, 0.0, 0.0, 0.0};
         if (live && q < Hn) {
             const cplx uk = U[(size_t)k * Hn + q], ek = E[(size_t)k * Hn + q];
@@ -206,7 +213,7 @@ __device__ __forceinline__ void leaf_batch_body(
     }
     __syncthreads();
     // ---- K. per scenario: K = (c0 + Delta_polar S_0^-1)^-1, u = K (y0 + V0) --------------------------------------------------------
-    if (l16 == 0) {
+    if (lt == 0) {
         const double* si = sir[0];                           // (q = 0 belongs to this thread)
         const double* dl = DL + sc * 4;
         const double q00 = c0img[0] + fma(dl[1], si[2], dl[0] * si[0]), q01 = c0img[1] + fma(dl[1], si[3], dl[0] * si[1]);
@@ -229,7 +236,7 @@ __device__ __forceinline__ void leaf_batch_body(
         double* Ck = Call + ((size_t)s * n + k) * CT;
 #pragma unroll
         for (int it = 0; it < QI; ++it) {
-            const int q = l16 + 16 * it;
+            const int q = TL::harmonic(tid, it);
             if (q >= H2) continue;
             double x0 = u0, x1 = u1;
             if (q > 0) {
@@ -249,7 +256,7 @@ __device__ __forceinline__ void leaf_batch_body(
     }
 }
 
-template <int B>
+template <int B, int SB>
 __global__ __launch_bounds__(256, 4) void k_leaf_batch(
     Model M, TreeDev T, const int* __restrict__ nodes, int b, const int* __restrict__ active, int S_cnt,
     const cplx* __restrict__ Uall, const cplx* __restrict__ Eall, const double* __restrict__ fall, double* __restrict__ wall,
@@ -257,15 +264,15 @@ __global__ __launch_bounds__(256, 4) void k_leaf_batch(
     const double* __restrict__ chH, const double* __restrict__ chD, const double* __restrict__ chy,
     const double* __restrict__ lbimg, double* __restrict__ lfK, double* __restrict__ lfS, int s0) {
     __shared__ __attribute__((aligned(16))) double smem[LEAF_BATCH_LDS];
-    leaf_batch_body<B>(smem, blockIdx.x, blockIdx.y, M, T, nodes, b, active, S_cnt, Uall, Eall, fall, wall, linAall, Call, Hall, chG, chH, chD, chy,
-                       lbimg, lfK, lfS, s0);
+    leaf_batch_body<B, SB>(smem, blockIdx.x, blockIdx.y, M, T, nodes, b, active, S_cnt, Uall, Eall, fall, wall, linAall, Call, Hall, chG, chH, chD, chy,
+                           lbimg, lfK, lfS, s0);
 }
 
-template <int B>
+template <int B, int SB>
 int launch_leaf_batch(hpf_handle* h, const TreeDev& T, const int* nodes, int count, const int* active) {
     ScopedTimer t(h, T_SOLVE);
-    const dim3 grid((unsigned)count, (unsigned)((h->cur_S + LB_SB - 1) / LB_SB));
-    hipLaunchKernelGGL((k_leaf_batch<B>), grid, dim3(256), 0, h->cur_stream, h->M, T, nodes, 2 * h->Hn, active, h->cur_S, h->d_U,
+    const dim3 grid((unsigned)count, (unsigned)BatchTile<SB>::tiles(h->cur_S));
+    hipLaunchKernelGGL((k_leaf_batch<B, SB>), grid, dim3(256), 0, h->cur_stream, h->M, T, nodes, 2 * h->Hn, active, h->cur_S, h->d_U,
                        h->d_E, h->d_fb, h->d_w, h->d_linA, h->d_C, h->d_H, h->d_chG, h->d_chH, h->d_chD, h->d_chy,
                        active_tree(h).d_lbimg, h->d_lfK, h->d_lfS, h->cur_s0);
     return launch_status(h);
@@ -757,7 +764,7 @@ int launch_back_tail(hpf_handle* h, const Tree& tr, const int* active) {
 // cores.  nodes: Tree::d_fdesc records (int 39: slot of the bus's image in Tree::d_sbimg).
 constexpr int SLEAF_BATCH_LDS = 2 * 64 * LBP + LB_SB * 100 + LB_SB * 10 + 3 * LB_SB * 4 + 2 * 16 * LBP;      // doubles
 
-template <int B>
+template <int B, int SB>
 __device__ __forceinline__ void sleaf_batch_body(
     double* __restrict__ smem_, const int bx_, const int by_, const Model& M, const TreeDev& T, const int* __restrict__ nodes, int b, const int* __restrict__ active, int S_cnt,
     const cplx* __restrict__ Uall, const cplx* __restrict__ Eall, const double* __restrict__ fall, double* __restrict__ wall,
@@ -774,7 +781,9 @@ __device__ __forceinline__ void sleaf_batch_body(
     HPF_SLSTAMP(0);
     constexpr int NT = (B + 16) / 16;
     constexpr size_t CT = (size_t)NT * NT * 256;
-    constexpr int NTR = SleafImg<B>::NTR, KS = SleafImg<B>::KS, KP = SleafImg<B>::KP, H2 = B / 2, QI = (H2 + 15) / 16;
+    using TL = BatchTile<SB>;                                    // role mapping: TL::TPS threads per scenario (hpf_batch_tile.hpp)
+    constexpr int RPT = TL::ROWS;
+    constexpr int NTR = SleafImg<B>::NTR, KS = SleafImg<B>::KS, KP = SleafImg<B>::KP, H2 = B / 2, QI = TL::harmonics(H2);
     constexpr bool QBR = SleafImg<B>::QB_ROWS;
     const int4* nd = reinterpret_cast<const int4*>(nodes) + (FDESC / 4) * (size_t)bx_;
     const int4 nd0 = nd[0], nd1 = nd[1], nd3 = nd[3], lzA = nd[7], lzB = nd[8], lzC = nd[9];
@@ -791,8 +800,8 @@ __device__ __forceinline__ void sleaf_batch_body(
     const int tid = threadIdx.x, lane = tid & 63, lg = lane >> 4, jj = lane & 15;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = M.n, c = M.c, Hn = M.Hn;
-    const int sc = tid >> 4, l16 = tid & 15;
-    const int sl = by_ * LB_SB + sc;
+    const int sc = TL::scenario(tid), lt = TL::lane(tid);
+    const int sl = by_ * SB + sc;
     const int ss = sl < S_cnt ? (active ? active[sl + s0] : sl + s0) : -1;      // slot -> scenario (active list; -1: frozen / empty slot)
     const bool live = ss >= 0;
     const int s = live ? ss : 0;
@@ -814,13 +823,13 @@ __device__ __forceinline__ void sleaf_batch_body(
 
     // ---- R1. rows --------------------------------------------------------------------------------------------------------------
     {
-        double e0[4] = {0.0, 0.0, 0.0, 0.0}, e1[4] = {0.0, 0.0, 0.0, 0.0}, ey[4] = {0.0, 0.0, 0.0, 0.0};
-        double a0[4] = {0.0, 0.0, 0.0, 0.0}, a1[4] = {0.0, 0.0, 0.0, 0.0}, ay[4] = {0.0, 0.0, 0.0, 0.0}, fy[4] = {0.0, 0.0, 0.0, 0.0};
-        bool ok[4];
-        cplx ukr[4], ekr[4];
+        double e0[RPT] = {}, e1[RPT] = {}, ey[RPT] = {};
+        double a0[RPT] = {}, a1[RPT] = {}, ay[RPT] = {}, fy[RPT] = {};
+        bool ok[RPT];
+        cplx ukr[RPT], ekr[RPT];
 #pragma unroll
-        for (int pz = 0; pz < 4; ++pz) {
-            const int row = l16 + 16 * pz, q = row >> 1, tr_ = row & 1;
+        for (int pz = 0; pz < RPT; ++pz) {
+            const int row = TL::row(tid, pz), q = row >> 1, tr_ = row & 1;
             ok[pz] = live && row < b && loc_valid(n, c, k, row);
             ukr[pz] = cplx{0.0, 0.0};
             ekr[pz] = cplx{0.0, 0.0};
@@ -855,9 +864,9 @@ __device__ __forceinline__ void sleaf_batch_body(
             const int4 cr = c3[cp];
             const int ch = cr.x;
 #pragma unroll
-            for (int pz = 0; pz < 4; ++pz) {
+            for (int pz = 0; pz < RPT; ++pz) {
                 if (!ok[pz]) continue;
-                const int row = l16 + 16 * pz, q = row >> 1, tr_ = row & 1;
+                const int row = TL::row(tid, pz), q = row >> 1, tr_ = row & 1;
                 const cplx uk = ukr[pz], ek = ekr[pz];
                 const cplx ydn = M.Y[(size_t)cr.y * Hn + q], yup = M.Y[(size_t)cr.z * Hn + q];
                 const cplx uc = U[(size_t)ch * Hn + q], ec = E[(size_t)ch * Hn + q];
@@ -878,9 +887,10 @@ __device__ __forceinline__ void sleaf_batch_body(
             }
         }
 #pragma unroll
-        for (int pz = 0; pz < 4; ++pz) {
-            const int row = l16 + 16 * pz;
+        for (int pz = 0; pz < RPT; ++pz) {
+            const int row = TL::row(tid, pz);
             Y[row * LBP + sc] = ok[pz] ? fy[pz] + ay[pz] - ey[pz] : 0.0;
+            if (SB < BATCH_COLS) Y[row * LBP + SB + sc] = 0.0;          // (the B-operand columns behind the tile)
             if (row < 2) {
                 DL[sc * 4 + row * 2] = ok[pz] ? a0[pz] - e0[pz] : 0.0;
                 DL[sc * 4 + row * 2 + 1] = ok[pz] ? a1[pz] - e1[pz] : 0.0;
@@ -892,7 +902,7 @@ __device__ __forceinline__ void sleaf_batch_body(
     double sir[QI][4], glr[QI][4];
 #pragma unroll
     for (int it = 0; it < QI; ++it) {
-        const int q = l16 + 16 * it;
+        const int q = TL::harmonic(tid, it);
         double si[4] = {1.0, 0.0, 0.0, 1.0}, g4[4] = {0.0, 0.0, 0.0, 0.0}, h4[4] = {0.0, 0.0, 0.0, 0.0};
         if (live && q < Hn) {
             const cplx uk = U[(size_t)k * Hn + q], ek = E[(size_t)k * Hn + q];
@@ -954,8 +964,8 @@ __device__ __forceinline__ void sleaf_batch_body(
         }
     }
     // T <- Tc (per scenario copy), rows by the scenario's threads
-    if (l16 < m)
-        for (int c2 = 0; c2 < m; ++c2) AUG[sc * 100 + l16 * 10 + c2] = simg[l16 * m + c2];
+    if (lt < m)
+        for (int c2 = 0; c2 < m; ++c2) AUG[sc * 100 + lt * 10 + c2] = simg[lt * m + c2];
     HPF_SLSTAMP(2);
     __syncthreads();
     HPF_SLSTAMP(3);
@@ -963,7 +973,7 @@ __device__ __forceinline__ void sleaf_batch_body(
     {
         double* aug = AUG + sc * 100;
         const double* wi = WI + sc * 4;
-        if (l16 == 0) {
+        if (lt == 0) {
             const double* si = S0 + sc * 4;
             const double* dl = DL + sc * 4;
             const double e00 = fma(dl[1], si[2], dl[0] * si[0]), e01 = fma(dl[1], si[3], dl[0] * si[1]);
@@ -975,8 +985,8 @@ __device__ __forceinline__ void sleaf_batch_body(
             const double y0 = Y[sc], y1 = Y[LBP + sc];                  // right-hand side rows 0 / 1: W_k^-1
             Y[sc] = fma(wi[1], y1, wi[0] * y0);
             Y[LBP + sc] = fma(wi[3], y1, wi[2] * y0);
-        } else if (l16 <= L && live) {
-            const int i = l16 - 1, bc = 2 + 2 * i;
+        } else if (lt <= L && live) {
+            const int i = lt - 1, bc = 2 + 2 * i;
             const int leaf = i == 0 ? lzA.z : (i == 1 ? lzA.w : (i == 2 ? lzB.x : lzB.y));
             const double* kk = lfK + ((size_t)s * n + leaf) * 12;
             double q00, q01, q10, q11;
@@ -993,10 +1003,10 @@ __device__ __forceinline__ void sleaf_batch_body(
             aug[bc * 10 + 1] -= kk[9];
             aug[(bc + 1) * 10] -= kk[10];
             aug[(bc + 1) * 10 + 1] -= kk[11];
-        } else if (live && l16 - L - 1 < (cs0 >= 0) + (cs1 >= 0)) {
+        } else if (live && lt - L - 1 < (cs0 >= 0) + (cs1 >= 0)) {
             // bordered child: its T_c in the place of K_c^-1; of its border columns only the first (the child's own position 0)
             // reaches position 0 here: -W_k^-1 (G0 S_c^-1) above, -W_c^-1 (H0 S_k^-1) on the left
-            const int zc = l16 - L - 1;
+            const int zc = lt - L - 1;
             const int cb = zc == 0 ? cs0 : cs1, mc = zc == 0 ? mc0 : mc1, bc = 2 + 2 * L + (zc ? mc0 : 0);
             const double* tcd = Zall + ((size_t)s * n + cb) * CT;     // T_c^-1 [10][10] | W_c^-1 [4] | T_c [10][10]
             const double* kk = lfK + ((size_t)s * n + cb) * 12;
@@ -1015,20 +1025,22 @@ __device__ __forceinline__ void sleaf_batch_body(
     }
     __syncthreads();
     HPF_SLSTAMP(4);
-    // ---- I. in-place inversion with partial pivoting, one scenario per 16 threads (thread r = row r; pivot row through LDS) -----
+    // ---- I. in-place inversion with partial pivoting, one scenario per 16 threads (thread r = row r; pivot row through LDS).  With 32 threads
+    //      per scenario the rows of T sit in its first 16 lanes, one DPP row: the upper 16 enter the reduction of their own DPP row as used
+    //      (-1), never own a pivot (pi < 16 <= lt) and store nothing ------------------------------------------------------------------
     {
         double* aug = AUG + sc * 100;
         double* pr = PR + sc * 10;
         double row[10];
 #pragma unroll
-        for (int c2 = 0; c2 < 10; ++c2) row[c2] = (l16 < m && c2 < m) ? aug[l16 * 10 + c2] : 0.0;
-        if (live && l16 < m) {                                   // T itself for a bordered parent (behind T^-1 and W^-1)
-            double* tk = Zall + ((size_t)s * n + k) * CT + 104 + l16 * 10;
+        for (int c2 = 0; c2 < 10; ++c2) row[c2] = (lt < m && c2 < m) ? aug[lt * 10 + c2] : 0.0;
+        if (live && lt < m) {                                   // T itself for a bordered parent (behind T^-1 and W^-1)
+            double* tk = Zall + ((size_t)s * n + k) * CT + 104 + lt * 10;
 #pragma unroll
             for (int c2 = 0; c2 < 10; ++c2)
                 if (c2 < m) tk[c2] = row[c2];
         }
-        bool used = l16 >= m;
+        bool used = lt >= m;
         int mycol = 0, pcol[10];
 #pragma unroll
         for (int j = 0; j < 10; ++j) {
@@ -1043,7 +1055,7 @@ __device__ __forceinline__ void sleaf_batch_body(
                 const unsigned long long bal = __builtin_amdgcn_ballot_w64(!used && cand == mx);
                 const unsigned grp = (unsigned)((bal >> (16 * lg)) & 0xffffull);
                 const int pi = __builtin_ctz(grp | 0x8000u);
-                const bool me = l16 == pi;
+                const bool me = lt == pi;
                 if (me) {
 #pragma unroll
                     for (int c2 = 0; c2 < 10; ++c2) pr[c2] = row[c2];
@@ -1065,7 +1077,7 @@ __device__ __forceinline__ void sleaf_batch_body(
                 pcol[j] = pi;
             }
         }
-        if (l16 < m) {
+        if (lt < m) {
             double* tk = Zall + ((size_t)s * n + k) * CT;
 #pragma unroll
             for (int c2 = 0; c2 < 10; ++c2)
@@ -1095,22 +1107,23 @@ __device__ __forceinline__ void sleaf_batch_body(
             }
         }
     }
-    if (!QBR) {
+    if (!QBR && lt < 16) {
         double r = 0.0;
-        if (l16 < m) {
-            const double* qr = qbm + (size_t)l16 * b;
+        if (lt < m) {
+            const double* qr = qbm + (size_t)lt * b;
             for (int col = 0; col < b; ++col) r = fma(qr[col], Y[col * LBP + sc], r);
         }
-        RR[l16 * LBP + sc] = r;
+        RR[lt * LBP + sc] = r;
     }
     __syncthreads();
-    {
+    if (lt < 16) {
         double y = 0.0;
-        if (l16 < m) {
-            const double* tr = AUG + sc * 100 + l16 * 10;
+        if (lt < m) {
+            const double* tr = AUG + sc * 100 + lt * 10;
             for (int j = 0; j < m; ++j) y = fma(tr[j], RR[j * LBP + sc], y);
         }
-        YY[l16 * LBP + sc] = y;
+        YY[lt * LBP + sc] = y;
+        if (SB < BATCH_COLS) YY[lt * LBP + SB + sc] = 0.0;
     }
     __syncthreads();
     if (wv < NTR) {                                              // ... + Pb y: three more rank-4 steps on the same accumulators
@@ -1132,7 +1145,7 @@ __device__ __forceinline__ void sleaf_batch_body(
         double* Ck = Call + ((size_t)s * n + k) * CT;
 #pragma unroll
         for (int it = 0; it < QI; ++it) {
-            const int q = l16 + 16 * it;
+            const int q = TL::harmonic(tid, it);
             if (q >= H2) continue;
             const double x0 = V[(2 * q) * LBP + sc], x1 = V[(2 * q + 1) * LBP + sc];
             const double* si = sir[it];
@@ -1146,7 +1159,7 @@ __device__ __forceinline__ void sleaf_batch_body(
         }
     }
 #ifdef HPF_FACTOR_STAMPS
-    if ((ablate & 16) && dbg && live && l16 == 0) {     // phases of this scenario's 16 threads (cycles): rows | harmonics | wait | T | inversion | MFMA + Qb v | T^-1 r | tail
+    if ((ablate & 16) && dbg && live && lt == 0) {     // phases of this scenario's 16 threads (cycles): rows | harmonics | wait | T | inversion | MFMA + Qb v | T^-1 r | tail
         HPF_SLSTAMP(7);
         long long* o = dbg + ((size_t)s * n + k) * 8;
         o[0] = tq[1] - tq[0];
@@ -1162,7 +1175,7 @@ __device__ __forceinline__ void sleaf_batch_body(
 #undef HPF_SLSTAMP
 }
 
-template <int B>
+template <int B, int SB>
 __global__ __launch_bounds__(256, 4) void k_sleaf_batch(
     Model M, TreeDev T, const int* __restrict__ nodes, int b, const int* __restrict__ active, int S_cnt,
     const cplx* __restrict__ Uall, const cplx* __restrict__ Eall, const double* __restrict__ fall, double* __restrict__ wall,
@@ -1171,15 +1184,15 @@ __global__ __launch_bounds__(256, 4) void k_sleaf_batch(
     const double* __restrict__ sbimg, double* __restrict__ Zall, double* __restrict__ lfK, double* __restrict__ lfS, int s0,
     long long* __restrict__ dbg, int ablate) {
     __shared__ __attribute__((aligned(16))) double smem[SLEAF_BATCH_LDS];
-    sleaf_batch_body<B>(smem, blockIdx.x, blockIdx.y, M, T, nodes, b, active, S_cnt, Uall, Eall, fall, wall, linAall, Call, Hall, I0all, chG, chH, chD,
-                        chy, sbimg, Zall, lfK, lfS, s0, dbg, ablate);
+    sleaf_batch_body<B, SB>(smem, blockIdx.x, blockIdx.y, M, T, nodes, b, active, S_cnt, Uall, Eall, fall, wall, linAall, Call, Hall, I0all, chG, chH, chD,
+                            chy, sbimg, Zall, lfK, lfS, s0, dbg, ablate);
 }
 
-template <int B>
+template <int B, int SB>
 int launch_sleaf_batch(hpf_handle* h, const TreeDev& T, const int* nodes, int count, const int* active) {
     ScopedTimer t(h, T_SOLVE);
-    const dim3 grid((unsigned)count, (unsigned)((h->cur_S + LB_SB - 1) / LB_SB));
-    hipLaunchKernelGGL((k_sleaf_batch<B>), grid, dim3(256), 0, h->cur_stream, h->M, T, nodes, 2 * h->Hn, active, h->cur_S, h->d_U,
+    const dim3 grid((unsigned)count, (unsigned)BatchTile<SB>::tiles(h->cur_S));
+    hipLaunchKernelGGL((k_sleaf_batch<B, SB>), grid, dim3(256), 0, h->cur_stream, h->M, T, nodes, 2 * h->Hn, active, h->cur_S, h->d_U,
                        h->d_E, h->d_fb, h->d_w, h->d_linA, h->d_C, h->d_H, h->d_I0, h->d_chG, h->d_chH, h->d_chD, h->d_chy,
                        active_tree(h).d_sbimg, h->d_Z, h->d_lfK, h->d_lfS, h->cur_s0, h->d_dbg, h->sw.debug_ablate);
     return launch_status(h);

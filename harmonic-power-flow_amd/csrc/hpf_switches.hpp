@@ -22,6 +22,10 @@ struct Switches {
     bool fuse_levels = true;          // HPF_FUSELEVEL=0: separate launches for the batched and the per-scenario workgroups of a level
     bool fuse_back = true;            // HPF_FUSEBACK=0: the back sweep's batched launches after the last depth instead of inside the depths' launches
     int fuse_back_max = 32;           // HPF_FUSEBACK_MAX: largest scenario group that takes the fused back sweep
+    int batch_tile8_max = 32;         // HPF_BATCH_TILE8_MAX: largest scenario group whose batched bordered buses take tiles of 8 scenarios (32 threads per
+                                      // scenario) instead of 16 in the factor sweep; 0: never (measured: a gain up to 32, a loss from 64)
+    int leaf_tile8_max = 0;           // HPF_LEAF_TILE8_MAX: the same bound for the lazy leaves of level 0 (their launch is the widest of the sweep: level 0
+                                      // of a group of 32 takes 30 us with tiles of 8 against 24 - 26 with tiles of 16)
     bool back_walk = true;            // HPF_BACKWALK=0: the Gauss-Jordan buses of the back sweep in one launch per depth instead of two tree walks
     int back_walk_min = 16;           // HPF_BACKWALK_MIN: smallest scenario group that takes the tree walk (at 1 - 4 its serial per-bus steps lose
                                       // ~8 % of the step to the few short depth launches; at 16 the two tie)
@@ -81,6 +85,8 @@ inline Switches parse_switches(const char* options, bool env_opt_in) {
     flag("HPF_FUSELEVEL", s.fuse_levels);
     flag("HPF_FUSEBACK", s.fuse_back);
     integer("HPF_FUSEBACK_MAX", s.fuse_back_max);
+    integer("HPF_BATCH_TILE8_MAX", s.batch_tile8_max);
+    integer("HPF_LEAF_TILE8_MAX", s.leaf_tile8_max);
     flag("HPF_BACKWALK", s.back_walk);
     integer("HPF_BACKWALK_MIN", s.back_walk_min);
     integer("HPF_BACKWALK_MAX", s.back_walk_max);

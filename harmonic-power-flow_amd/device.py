@@ -560,10 +560,11 @@ class DeviceModel:
 
     def tree_census(self):
         """Which kernel takes which bus of the block tree (hpf_tree_census)."""
-        out = (C.c_int32 * 17)()
-        self._chk(self.lib.hpf_tree_census(self._h, out, 17), "hpf_tree_census")
+        out = (C.c_int32 * 19)()
+        self._chk(self.lib.hpf_tree_census(self._h, out, 19), "hpf_tree_census")
         names = ("dense_buses", "gauss_jordan", "const_leaves", "lazy_leaves", "bordered", "nested_bordered", "levels", "depths", "ties",
-                 "fused_levels", "compress_steps", "border_repivots", "border_unknowns", "root_path_buses", "bordered_form", "back_walks", "back_tails")
+                 "fused_levels", "compress_steps", "border_repivots", "border_unknowns", "root_path_buses", "bordered_form", "back_walks", "back_tails",
+                 "batch_tile", "leaf_batch_tile")
         return dict(zip(names, (int(v) for v in out)))
 
     def solve_bytes(self):

@@ -499,6 +499,8 @@ int  hpf_debug_device_memory(int64_t* blocks, int64_t* bytes);
  * a 4 x 4 pivot block beyond which such a system goes to the pivoted LU, default 1e3; HPF_BORDER_INFO=1 prints every border solve's residual),
  * HPF_FUSEBACK=0 launches the back sweep's scenario-batched workgroups (bordered buses, leaves) after the last depth instead of inside the
  * depths' launches (k_level_back: groups of up to HPF_FUSEBACK_MAX = 32 scenarios, blocks of 52),
+ * HPF_BATCH_TILE8_MAX=n lets the factor sweep's batched bordered buses take 8 scenarios per workgroup (32 threads per scenario) instead of 16 in
+ * scenario groups of up to n (default 32; 0: never), HPF_LEAF_TILE8_MAX=n the same for its lazy leaves (default 0); the results are the same bits,
  * HPF_BACKWALK=0 runs the back sweep's Gauss-Jordan buses in one launch per depth instead of two tree walks (k_back_walk: the trunk,
  * then up to 8 subtree lists, one workgroup per list and scenario; blocks of 52, groups of HPF_BACKWALK_MIN = 16 to HPF_BACKWALK_MAX = 256
  * scenarios: groups of 1 - 4 run faster on the depth launches; the batched workgroups follow the walk),
@@ -558,7 +560,9 @@ int  hpf_kernel_model(const hpf_handle* h, int which, double* bytes, double* flo
  * (kept as plain Gauss-Jordan buses by the factor-once bordered step; 0: virtual-sweep form), [14] form of the bordered step: 0 virtual sweeps,
  * 1 factor-once with rocSOLVER's LU of the border system, 2 factor-once with the block Gauss-Jordan solve, [15] back sweeps (scenario group x
  * Newton step) since hpf_create whose Gauss-Jordan buses went through the tree walk (HPF_BACKWALK), [16] back sweeps since hpf_create whose
- * bordered buses and constant-inverse leaves went through one launch that walks their families (k_back_tail, HPF_BACKTAIL).
+ * bordered buses and constant-inverse leaves went through one launch that walks their families (k_back_tail, HPF_BACKTAIL),
+ * [17] scenarios per batched workgroup of the last factor launch with bordered buses: 16, or 8 where the scenario group is no larger than
+ * HPF_BATCH_TILE8_MAX (0: no such launch yet), [18] the same of the last factor launch with lazy leaves (HPF_LEAF_TILE8_MAX).
  * HPF_E_STATE for DENSE. */
 int  hpf_tree_census(const hpf_handle* h, int* counts, int n_counts);
 /* Wall-clock milliseconds hpf_create spent: ms[0] total, [1] planning the elimination trees on the host (classification of the buses,

@@ -29,7 +29,7 @@ struct BatchTile {
     static HPF_TILE_HD constexpr int tiles(int scenarios) { return (scenarios + SB - 1) / SB; }   // workgroups per bus
 };
 
-// the tile a launch of cur_S scenarios takes: 8 up to tile8_max (0: never), else 16
-HPF_TILE_HD constexpr int batch_tile_of(int cur_S, int tile8_max) { return cur_S <= tile8_max ? 8 : 16; }
+// the tile a launch of S scenarios takes: 8 up to tile8_max (0: never), else 16
+HPF_TILE_HD constexpr int batch_tile_of(int S, int tile8_max) { return S <= tile8_max ? 8 : 16; }
 
 }  // namespace hpf

@@ -24,6 +24,7 @@
 #include <functional>
 #include <rocsolver/rocsolver.h>
 #include <thread>
+#include <type_traits>
 
 #include "hpf_internal.hpp"
 #include "hpf_batch_tile.hpp"
@@ -697,18 +698,18 @@ __device__ __forceinline__ void mul22(const double a[4], const double b[4], doub
 }
 
 template <int B>
-int launch_factor_w(hpf_handle* h, const TreeDev& T, const int* nodes, int count, const int* active) {
-    ScopedTimer t(h, T_SOLVE);
-    hipLaunchKernelGGL((k_factor_w<B>), dim3((unsigned)count, (unsigned)h->cur_S), dim3(64), 0, h->cur_stream, h->M, T, nodes,
-                       2 * h->Hn, h->N, h->Nc, active, h->d_U, h->d_E, h->d_f, h->d_Z, h->d_w, h->d_linA, h->d_pivflag, h->sw.debug_ablate, h->cur_s0);
+int launch_factor_w(hpf_handle* h, const LaunchCtx& ctx, const TreeDev& T, const int* nodes, int count) {
+    ScopedTimer t(h, T_SOLVE, ctx.stream);
+    hipLaunchKernelGGL((k_factor_w<B>), dim3((unsigned)count, (unsigned)ctx.S), dim3(64), 0, ctx.stream, h->M, T, nodes,
+                       2 * h->Hn, h->N, h->Nc, ctx.active, h->d_U, h->d_E, h->d_f, h->d_Z, h->d_w, h->d_linA, h->d_pivflag, h->sw.debug_ablate, ctx.s0);
     return launch_status(h);
 }
 
 template <int B>
-int launch_back_w(hpf_handle* h, const TreeDev& T, const int* nodes, int count, const int* active) {
-    hipLaunchKernelGGL((k_back_w<B>), dim3((unsigned)count, (unsigned)h->cur_S), dim3(64), 0, h->cur_stream, h->M, T, nodes,
-                       2 * h->Hn, h->N, h->Nc, active, h->d_U, h->d_E, h->d_Z, h->d_w, h->d_x, h->d_f,
-                       h->gj_mode ? h->d_H : nullptr, h->cur_s0);
+int launch_back_w(hpf_handle* h, const LaunchCtx& ctx, const TreeDev& T, const int* nodes, int count) {
+    hipLaunchKernelGGL((k_back_w<B>), dim3((unsigned)count, (unsigned)ctx.S), dim3(64), 0, ctx.stream, h->M, T, nodes,
+                       2 * h->Hn, h->N, h->Nc, ctx.active, h->d_U, h->d_E, h->d_Z, h->d_w, h->d_x, h->d_f,
+                       h->gj_mode ? h->d_H : nullptr, ctx.s0);
     return launch_status(h);
 }
 
@@ -731,12 +732,10 @@ constexpr int level_lds() {
     return a > b2 ? (a > c2 ? a : c2) : (b2 > c2 ? b2 : c2);
 }
 
-// the scenario tile of a launch's batched workgroups (kind 1: lazy leaves, 2: bordered buses -- each with its own bound); hpf_tree_census[17] /
-// [18] report the last one taken
-inline int batch_tile(hpf_handle* h, int kind) {
-    if (kind == 1) return h->last_leaf_tile = batch_tile_of(h->cur_S, h->sw.leaf_tile8_max);
-    return h->last_batch_tile = batch_tile_of(h->cur_S, h->sw.batch_tile8_max);
-}
+// the scenario tile of the batched workgroups of a launch of S scenarios (kind 1: lazy leaves, 2: bordered buses -- each with its own bound)
+inline int batch_tile(int S, const Switches& sw, int kind) { return batch_tile_of(S, kind == 1 ? sw.leaf_tile8_max : sw.batch_tile8_max); }
+// ... and the dispatch site that launches with it (launch_level, factor_level) records it for hpf_tree_census: the last one taken
+inline int note_batch_tile(hpf_handle* h, int kind, int tile) { return (kind == 1 ? h->last_leaf_tile : h->last_batch_tile) = tile; }
 
 template <int B, int SB>
 __global__ __launch_bounds__(256, HPF_Q_OCC) void k_level(
@@ -792,30 +791,30 @@ __global__ __launch_bounds__(256, HPF_Q_OCC) void k_level(
 }
 
 template <int B, int SB>
-int launch_level_tile(hpf_handle* h, const TreeDev& T, const int* nodes, int kind, int nbatch, int ngen, const int* active) {
-    ScopedTimer t(h, T_GJ);
+int launch_level_tile(hpf_handle* h, const LaunchCtx& ctx, const TreeDev& T, const int* nodes, int kind, int nbatch, int ngen) {
+    ScopedTimer t(h, T_GJ, ctx.stream);
     unsigned long long* ts = nullptr;                   // device-clock stamps of this launch (timing leg)
     if (h->timing && h->d_tstamp && h->ts_next < hpf_handle::TS_CAP) ts = h->d_tstamp + 2 * (size_t)(h->ts_next++);
     const Tree& tr = active_tree(h);
-    const unsigned ytiles = (unsigned)BatchTile<SB>::tiles(h->cur_S);
+    const unsigned ytiles = (unsigned)BatchTile<SB>::tiles(ctx.S);
 #if HPF_BATCH_XCD
-    const unsigned grid = (kind ? (unsigned)(((nbatch + 7) / 8) * 8) * ytiles : 0u) + (unsigned)ngen * (unsigned)h->cur_S;
+    const unsigned grid = (kind ? (unsigned)(((nbatch + 7) / 8) * 8) * ytiles : 0u) + (unsigned)ngen * (unsigned)ctx.S;
 #else
-    const unsigned grid = (kind ? (unsigned)nbatch * ytiles : 0u) + (unsigned)ngen * (unsigned)h->cur_S;
+    const unsigned grid = (kind ? (unsigned)nbatch * ytiles : 0u) + (unsigned)ngen * (unsigned)ctx.S;
 #endif
     if (grid == 0) return HPF_OK;
-    hipLaunchKernelGGL((k_level<B, SB>), dim3(grid), dim3(256), 0, h->cur_stream, h->M, T, nodes, kind, nbatch, ngen, 2 * h->Hn,
-                       h->N, h->Nc, active, h->cur_S, h->d_U, h->d_E, h->d_fb, h->d_Z, h->d_w, h->d_linA, h->d_C, h->d_H, h->d_I0, h->d_chG,
+    hipLaunchKernelGGL((k_level<B, SB>), dim3(grid), dim3(256), 0, ctx.stream, h->M, T, nodes, kind, nbatch, ngen, 2 * h->Hn,
+                       h->N, h->Nc, ctx.active, ctx.S, h->d_U, h->d_E, h->d_fb, h->d_Z, h->d_w, h->d_linA, h->d_C, h->d_H, h->d_I0, h->d_chG,
                        h->d_chH, h->d_chD, h->d_chy, tr.d_Minv, tr.d_lbimg, tr.d_sbimg, h->d_lfK, h->d_lfS, h->d_dbg, h->sw.debug_ablate,
-                       h->cur_s0, h->d_pivflag, h->piv_limit, ts);
+                       ctx.s0, h->d_pivflag, h->piv_limit, ts);
     return launch_status(h);
 }
 
 // (a level without batched workgroups has no tile: it takes the kernel of the larger one)
 template <int B>
-int launch_level(hpf_handle* h, const TreeDev& T, const int* nodes, int kind, int nbatch, int ngen, const int* active) {
-    if (kind && batch_tile(h, kind) == 8) return launch_level_tile<B, 8>(h, T, nodes, kind, nbatch, ngen, active);
-    return launch_level_tile<B, LB_SB>(h, T, nodes, kind, nbatch, ngen, active);
+int launch_level(hpf_handle* h, const LaunchCtx& ctx, const TreeDev& T, const int* nodes, int kind, int nbatch, int ngen) {
+    if (kind && note_batch_tile(h, kind, batch_tile(ctx.S, h->sw, kind)) == 8) return launch_level_tile<B, 8>(h, ctx, T, nodes, kind, nbatch, ngen);
+    return launch_level_tile<B, LB_SB>(h, ctx, T, nodes, kind, nbatch, ngen);
 }
 
 // padded block size of the multi-wave MFMA path: 12 / 28 / 52, and 100 for 52 < b <= 100 (K <= 49: BASELINE config 5; the general
@@ -825,8 +824,8 @@ int wave_block_size(int b) { return b <= 12 ? 12 : (b <= 28 ? 28 : (b <= 52 ? 52
 size_t factor_lds_bytes(int b) { return gj_dense_lds_bytes(b); }
 
 template <int R>
-int launch_factor(hpf_handle* h, const TreeDev& T, const int* nodes, int count, const int* active) {
-    ScopedTimer t(h, T_SOLVE);
+int launch_factor(hpf_handle* h, const LaunchCtx& ctx, const TreeDev& T, const int* nodes, int count) {
+    ScopedTimer t(h, T_SOLVE, ctx.stream);
     const int b = 2 * h->Hn;
     const size_t lds = factor_lds_bytes(b);
     if (lds > 64 * 1024) {
@@ -839,8 +838,8 @@ int launch_factor(hpf_handle* h, const TreeDev& T, const int* nodes, int count, 
             return HPF_E_HIP;
         }
     }
-    hipLaunchKernelGGL((k_tree_factor<R>), dim3((unsigned)count, (unsigned)h->cur_S), dim3(256), lds, h->cur_stream, h->M, T,
-                       nodes, b, h->N, h->Nc, active, h->d_U, h->d_E, h->d_f, h->d_Z, h->d_w, h->cur_s0);
+    hipLaunchKernelGGL((k_tree_factor<R>), dim3((unsigned)count, (unsigned)ctx.S), dim3(256), lds, ctx.stream, h->M, T,
+                       nodes, b, h->N, h->Nc, ctx.active, h->d_U, h->d_E, h->d_f, h->d_Z, h->d_w, ctx.s0);
     return launch_status(h);
 }
 
@@ -885,19 +884,19 @@ __global__ __launch_bounds__(256) void k_level_back(
 }
 
 template <int B>
-int launch_level_back(hpf_handle* h, const TreeDev& T, const int* sl_nodes, int n_sl, const int* lf_nodes, int n_lf, const int* gj_nodes, int n_gj,
-                      const int* active) {
+int launch_level_back(hpf_handle* h, const LaunchCtx& ctx, const TreeDev& T, const int* sl_nodes, int n_sl, const int* lf_nodes, int n_lf, const int* gj_nodes,
+                      int n_gj) {
     const Tree& tr = active_tree(h);
-    const unsigned ytiles = (unsigned)((h->cur_S + LB_SB - 1) / LB_SB);
+    const unsigned ytiles = (unsigned)((ctx.S + LB_SB - 1) / LB_SB);
 #if HPF_BATCH_XCD
-    const unsigned grid = (unsigned)(((n_sl + 7) / 8) * 8 + ((n_lf + 7) / 8) * 8) * ytiles + (unsigned)n_gj * (unsigned)h->cur_S;
+    const unsigned grid = (unsigned)(((n_sl + 7) / 8) * 8 + ((n_lf + 7) / 8) * 8) * ytiles + (unsigned)n_gj * (unsigned)ctx.S;
 #else
-    const unsigned grid = (unsigned)(n_sl + n_lf) * ytiles + (unsigned)n_gj * (unsigned)h->cur_S;
+    const unsigned grid = (unsigned)(n_sl + n_lf) * ytiles + (unsigned)n_gj * (unsigned)ctx.S;
 #endif
-    if ((unsigned)(n_sl + n_lf) * ytiles + (unsigned)n_gj * (unsigned)h->cur_S == 0) return HPF_OK;
-    hipLaunchKernelGGL((k_level_back<B>), dim3(grid), dim3(256), 0, h->cur_stream, h->M, T, sl_nodes, n_sl, lf_nodes, n_lf, gj_nodes, n_gj, 2 * h->Hn,
-                       h->N, h->Nc, active, h->cur_S, h->d_Z, h->d_w, h->d_x, h->d_H, tr.d_Minv, tr.d_lbimg, tr.d_sbimg, tr.d_lzimg, h->d_lfK, h->d_lfS,
-                       h->cur_s0);
+    if ((unsigned)(n_sl + n_lf) * ytiles + (unsigned)n_gj * (unsigned)ctx.S == 0) return HPF_OK;
+    hipLaunchKernelGGL((k_level_back<B>), dim3(grid), dim3(256), 0, ctx.stream, h->M, T, sl_nodes, n_sl, lf_nodes, n_lf, gj_nodes, n_gj, 2 * h->Hn,
+                       h->N, h->Nc, ctx.active, ctx.S, h->d_Z, h->d_w, h->d_x, h->d_H, tr.d_Minv, tr.d_lbimg, tr.d_sbimg, tr.d_lzimg, h->d_lfK, h->d_lfS,
+                       ctx.s0);
     return launch_status(h);
 }
 
@@ -937,11 +936,11 @@ __global__ __launch_bounds__(64 * ((B + 16) / 16)) void k_back_walk(
 
 // lists list0 .. list0 + count - 1 of the tree's walk
 template <int B>
-int launch_back_walk(hpf_handle* h, const Tree& tr, const TreeDev& T, int list0, int count, const int* active) {
+int launch_back_walk(hpf_handle* h, const LaunchCtx& ctx, const Tree& tr, const TreeDev& T, int list0, int count) {
     constexpr int NT = (B + 16) / 16;
-    hipLaunchKernelGGL((k_back_walk<B>), dim3((unsigned)count, (unsigned)h->cur_S), dim3(64 * NT), 0, h->cur_stream, h->M, T, tr.d_walk_rec,
-                       tr.d_walk_slot, tr.d_walk_ptr + list0, 2 * h->Hn, h->N, h->Nc, active, h->d_Z, h->d_w, h->d_x, h->d_H, tr.d_Minv,
-                       h->d_lfK, h->d_lfS, h->cur_s0);
+    hipLaunchKernelGGL((k_back_walk<B>), dim3((unsigned)count, (unsigned)ctx.S), dim3(64 * NT), 0, ctx.stream, h->M, T, tr.d_walk_rec,
+                       tr.d_walk_slot, tr.d_walk_ptr + list0, 2 * h->Hn, h->N, h->Nc, ctx.active, h->d_Z, h->d_w, h->d_x, h->d_H, tr.d_Minv,
+                       h->d_lfK, h->d_lfS, ctx.s0);
     return launch_status(h);
 }
 
@@ -1085,34 +1084,33 @@ int tree_alloc_scenarios(hpf_handle* h) {
 // Fundamental power-flow Newton step on a radial network (pf, HG:244-275): every bus is a plain power bus there, so the whole
 // tree is one "linear subtree" at harmonic position 0 -> the same 2x2 elimination (fund = 1): level-parallel where the tree has multi-wave
 // kernels, else one thread per scenario walking the post-order.
-int tree_fund_step(hpf_handle* h, bool only_active) {
+int tree_fund_step(hpf_handle* h, const LaunchCtx& ctx) {
     Tree& T = h->tree;
-    const int* active = only_active ? h->d_active : nullptr;
     const TreeDev td{T.d_parent, T.d_child_ptr, T.d_child, T.d_e_up, T.d_e_dn, T.d_child_mid, T.d_all_ptr, T.d_all_post, T.d_child3, T.d_dchild, T.d_chain_ptr, T.d_chain_nodes, T.d_chain_ch};
     const int b = 2 * h->Hn;
     const int BW = wave_block_size(b);
     const int Bst = BW ? BW : b;
-    ScopedTimer t(h, T_SOLVE);
+    ScopedTimer t(h, T_SOLVE, ctx.stream);
     if (BW) {
         // level-parallel: one launch per height of the tree, one thread per (bus, scenario) (k_lin_level_*)
         for (int hh = 0; hh < T.n_all_heights; ++hh) {
             const int cnt = T.ah_ptr[hh + 1] - T.ah_ptr[hh];
-            hipLaunchKernelGGL(k_lin_level_factor, dim3((unsigned)((cnt + 127) / 128), (unsigned)h->cur_S), dim3(128), 0,
-                               h->cur_stream, h->M, td, T.d_arec + 8 * (size_t)T.ah_ptr[hh], cnt, h->Nf, h->n - 1, Bst, active, h->d_U,
-                               h->d_E, h->d_f, h->d_linA, h->d_w, h->d_I0, 1, h->cur_s0);
+            hipLaunchKernelGGL(k_lin_level_factor, dim3((unsigned)((cnt + 127) / 128), (unsigned)ctx.S), dim3(128), 0,
+                               ctx.stream, h->M, td, T.d_arec + 8 * (size_t)T.ah_ptr[hh], cnt, h->Nf, h->n - 1, Bst, ctx.active, h->d_U,
+                               h->d_E, h->d_f, h->d_linA, h->d_w, h->d_I0, 1, ctx.s0);
         }
         for (int hh = T.n_all_heights - 1; hh >= 0; --hh) {
             const int cnt = T.ah_ptr[hh + 1] - T.ah_ptr[hh];
-            hipLaunchKernelGGL(k_lin_level_back, dim3((unsigned)((cnt + 127) / 128), (unsigned)h->cur_S), dim3(128), 0, h->cur_stream,
-                               h->M, td, T.d_arec + 8 * (size_t)T.ah_ptr[hh], cnt, h->Nf, h->n - 1, Bst, active, h->d_U, h->d_E,
-                               h->d_linA, h->d_w, h->d_x, h->d_f, 1, h->cur_s0);
+            hipLaunchKernelGGL(k_lin_level_back, dim3((unsigned)((cnt + 127) / 128), (unsigned)ctx.S), dim3(128), 0, ctx.stream,
+                               h->M, td, T.d_arec + 8 * (size_t)T.ah_ptr[hh], cnt, h->Nf, h->n - 1, Bst, ctx.active, h->d_U, h->d_E,
+                               h->d_linA, h->d_w, h->d_x, h->d_f, 1, ctx.s0);
         }
     } else {
         // one thread per scenario walks the post-order of the whole tree (k_lin_factor / k_lin_back)
-        hipLaunchKernelGGL((k_lin_factor<true>), dim3(1, (unsigned)h->cur_S), dim3(128), 0, h->cur_stream, h->M, td, 1, h->Nf,
-                           h->n - 1, Bst, active, h->d_U, h->d_E, h->d_f, h->d_linA, h->d_w, nullptr, h->cur_s0);
-        hipLaunchKernelGGL((k_lin_back<true>), dim3(1, (unsigned)h->cur_S), dim3(128), 0, h->cur_stream, h->M, td, 1, h->Nf,
-                           h->n - 1, Bst, active, h->d_U, h->d_E, h->d_linA, h->d_w, h->d_x, h->d_f, h->cur_s0);
+        hipLaunchKernelGGL((k_lin_factor<true>), dim3(1, (unsigned)ctx.S), dim3(128), 0, ctx.stream, h->M, td, 1, h->Nf,
+                           h->n - 1, Bst, ctx.active, h->d_U, h->d_E, h->d_f, h->d_linA, h->d_w, nullptr, ctx.s0);
+        hipLaunchKernelGGL((k_lin_back<true>), dim3(1, (unsigned)ctx.S), dim3(128), 0, ctx.stream, h->M, td, 1, h->Nf,
+                           h->n - 1, Bst, ctx.active, h->d_U, h->d_E, h->d_linA, h->d_w, h->d_x, h->d_f, ctx.s0);
     }
     return launch_status(h);
 }
@@ -1122,88 +1120,88 @@ int tree_fund_step(hpf_handle* h, bool only_active) {
 
 // one-round-trip bundles of the linear subtrees (and of the chains with them, Tree::chains_bundled), NP items per thread
 template <int NP>
-static void lin_bundle_launch(hpf_handle* h, const Tree& T, const TreeDev& td, const int* active, int Bst, bool back) {
-    const dim3 grid((unsigned)T.n_lin_bundles2, (unsigned)h->cur_S);
+static void lin_bundle_launch(hpf_handle* h, const LaunchCtx& ctx, const Tree& T, const TreeDev& td, int Bst, bool back) {
+    const dim3 grid((unsigned)T.n_lin_bundles2, (unsigned)ctx.S);
     const int* cptr = T.chains_bundled ? T.d_lb2cptr : (const int*)nullptr;
     if (!back)
-        hipLaunchKernelGGL((k_lin_bundle_factor<NP>), grid, dim3(256), 0, h->cur_stream, h->M, T.d_lb2rec, (const int2*)T.d_lb2x, T.d_lb2ptr,
-                           T.n_lin_heights, Bst, active, h->d_U, h->d_E, h->d_fb, h->d_linA, h->d_w, h->d_I0, h->cur_s0, td, cptr, T.d_lb2clist,
+        hipLaunchKernelGGL((k_lin_bundle_factor<NP>), grid, dim3(256), 0, ctx.stream, h->M, T.d_lb2rec, (const int2*)T.d_lb2x, T.d_lb2ptr,
+                           T.n_lin_heights, Bst, ctx.active, h->d_U, h->d_E, h->d_fb, h->d_linA, h->d_w, h->d_I0, ctx.s0, td, cptr, T.d_lb2clist,
                            T.d_crec, T.d_cnode, h->d_chG, h->d_chH, h->d_chD, h->d_chy, h->d_chZ);
     else
-        hipLaunchKernelGGL((k_lin_bundle_back<NP>), grid, dim3(256), 0, h->cur_stream, h->M, T.d_lb2rec, (const int2*)T.d_lb2x, T.d_lb2ptr,
-                           T.n_lin_heights, Bst, active, h->d_U, h->d_E, h->d_linA, h->d_w, h->d_x, h->cur_s0, cptr, T.d_lb2clist, T.d_crec,
+        hipLaunchKernelGGL((k_lin_bundle_back<NP>), grid, dim3(256), 0, ctx.stream, h->M, T.d_lb2rec, (const int2*)T.d_lb2x, T.d_lb2ptr,
+                           T.n_lin_heights, Bst, ctx.active, h->d_U, h->d_E, h->d_linA, h->d_w, h->d_x, ctx.s0, cptr, T.d_lb2clist, T.d_crec,
                            T.d_cnode, h->d_chZ);
 }
 
-static void lin_bundle(hpf_handle* h, const Tree& T, const TreeDev& td, const int* active, int Bst, bool back) {
-    if (T.lin_np == 1) lin_bundle_launch<1>(h, T, td, active, Bst, back);
-    else if (T.lin_np == 2) lin_bundle_launch<2>(h, T, td, active, Bst, back);
-    else lin_bundle_launch<4>(h, T, td, active, Bst, back);
+static void lin_bundle(hpf_handle* h, const LaunchCtx& ctx, const Tree& T, const TreeDev& td, int Bst, bool back) {
+    if (T.lin_np == 1) lin_bundle_launch<1>(h, ctx, T, td, Bst, back);
+    else if (T.lin_np == 2) lin_bundle_launch<2>(h, ctx, T, td, Bst, back);
+    else lin_bundle_launch<4>(h, ctx, T, td, Bst, back);
 }
 
 // factor part of the 2x2 algebra: the all-linear subtrees in the tree's form, then the contracted chains
-static int lin_factor(hpf_handle* h, const Tree& T, const TreeDev& td, const int* active, int Bst) {
+static int lin_factor(hpf_handle* h, const LaunchCtx& ctx, const Tree& T, const TreeDev& td, int Bst) {
     switch (T.lin_form) {
         case LIN_ROOTS: {
             const int lin_threads = T.n_lin_roots * h->Hn;
             if (lin_threads > 0)
-                hipLaunchKernelGGL((k_lin_factor<false>), dim3((unsigned)((lin_threads + 127) / 128), (unsigned)h->cur_S), dim3(128), 0,
-                                   h->cur_stream, h->M, td, T.n_lin_roots, h->N, h->Nc, Bst, active, h->d_U, h->d_E, h->d_f,
-                                   h->d_linA, h->d_w, h->d_I0, h->cur_s0);
+                hipLaunchKernelGGL((k_lin_factor<false>), dim3((unsigned)((lin_threads + 127) / 128), (unsigned)ctx.S), dim3(128), 0,
+                                   ctx.stream, h->M, td, T.n_lin_roots, h->N, h->Nc, Bst, ctx.active, h->d_U, h->d_E, h->d_f,
+                                   h->d_linA, h->d_w, h->d_I0, ctx.s0);
             break;
         }
-        case LIN_BUNDLE: lin_bundle(h, T, td, active, Bst, false); break;
+        case LIN_BUNDLE: lin_bundle(h, ctx, T, td, Bst, false); break;
         case LIN_TREE:
-            hipLaunchKernelGGL(k_lin_tree_factor, dim3((unsigned)T.n_lin_bundles, (unsigned)h->cur_S), dim3(256), 0, h->cur_stream,
-                               h->M, td, T.d_lbrec, T.d_lbptr, T.n_lin_heights, h->N, h->Nc, Bst, active, h->d_U, h->d_E,
-                               h->d_fb, h->d_linA, h->d_w, h->d_I0, h->cur_s0);
+            hipLaunchKernelGGL(k_lin_tree_factor, dim3((unsigned)T.n_lin_bundles, (unsigned)ctx.S), dim3(256), 0, ctx.stream,
+                               h->M, td, T.d_lbrec, T.d_lbptr, T.n_lin_heights, h->N, h->Nc, Bst, ctx.active, h->d_U, h->d_E,
+                               h->d_fb, h->d_linA, h->d_w, h->d_I0, ctx.s0);
             break;
         case LIN_LEVELS:
             for (int hh = 0; hh < T.n_lin_heights; ++hh) {
                 const int cnt = T.lh_ptr[hh + 1] - T.lh_ptr[hh];
                 if (cnt == 0) continue;
-                hipLaunchKernelGGL(k_lin_level_factor, dim3((unsigned)((cnt * h->Hn + 127) / 128), (unsigned)h->cur_S), dim3(128), 0,
-                                   h->cur_stream, h->M, td, T.d_lrec + 8 * (size_t)T.lh_ptr[hh], cnt, h->N, h->Nc, Bst, active,
-                                   h->d_U, h->d_E, h->d_fb, h->d_linA, h->d_w, h->d_I0, 0, h->cur_s0);
+                hipLaunchKernelGGL(k_lin_level_factor, dim3((unsigned)((cnt * h->Hn + 127) / 128), (unsigned)ctx.S), dim3(128), 0,
+                                   ctx.stream, h->M, td, T.d_lrec + 8 * (size_t)T.lh_ptr[hh], cnt, h->N, h->Nc, Bst, ctx.active,
+                                   h->d_U, h->d_E, h->d_fb, h->d_linA, h->d_w, h->d_I0, 0, ctx.s0);
             }
             break;
     }
     if (T.chain_launches)
-        hipLaunchKernelGGL(k_chain_factor2, dim3((unsigned)((T.n_chains * h->Hn + 127) / 128), (unsigned)h->cur_S), dim3(128),
-                           0, h->cur_stream, h->M, td, T.d_crec, T.d_cnode, T.n_chains, h->N, h->Nc, Bst, active, h->d_U,
+        hipLaunchKernelGGL(k_chain_factor2, dim3((unsigned)((T.n_chains * h->Hn + 127) / 128), (unsigned)ctx.S), dim3(128),
+                           0, ctx.stream, h->M, td, T.d_crec, T.d_cnode, T.n_chains, h->N, h->Nc, Bst, ctx.active, h->d_U,
                            h->d_E, h->d_fb, h->d_linA, h->d_w, h->d_I0, h->d_chG, h->d_chH, h->d_chD, h->d_chy, h->d_chZ,
-                           h->cur_s0);
+                           ctx.s0);
     return launch_status(h);
 }
 
 // back part of the 2x2 algebra: the contracted chains, then the all-linear subtrees in the tree's form
-static int lin_back(hpf_handle* h, const Tree& T, const TreeDev& td, const int* active, int Bst) {
+static int lin_back(hpf_handle* h, const LaunchCtx& ctx, const Tree& T, const TreeDev& td, int Bst) {
     if (T.chain_launches)
-        hipLaunchKernelGGL(k_chain_back2, dim3((unsigned)((T.n_chains * h->Hn + 127) / 128), (unsigned)h->cur_S), dim3(128), 0,
-                           h->cur_stream, h->M, td, T.d_crec, T.d_cnode, T.n_chains, h->N, h->Nc, Bst, active, h->d_U, h->d_E,
-                           h->d_linA, h->d_w, h->d_x, (double*)nullptr, h->d_chZ, h->cur_s0);
+        hipLaunchKernelGGL(k_chain_back2, dim3((unsigned)((T.n_chains * h->Hn + 127) / 128), (unsigned)ctx.S), dim3(128), 0,
+                           ctx.stream, h->M, td, T.d_crec, T.d_cnode, T.n_chains, h->N, h->Nc, Bst, ctx.active, h->d_U, h->d_E,
+                           h->d_linA, h->d_w, h->d_x, (double*)nullptr, h->d_chZ, ctx.s0);
     switch (T.lin_form) {
         case LIN_ROOTS: {
             const int lin_threads = T.n_lin_roots * h->Hn;
             if (lin_threads > 0)
-                hipLaunchKernelGGL((k_lin_back<false>), dim3((unsigned)((lin_threads + 127) / 128), (unsigned)h->cur_S), dim3(128), 0,
-                                   h->cur_stream, h->M, td, T.n_lin_roots, h->N, h->Nc, Bst, active, h->d_U, h->d_E, h->d_linA, h->d_w,
-                                   h->d_x, h->d_f, h->cur_s0);
+                hipLaunchKernelGGL((k_lin_back<false>), dim3((unsigned)((lin_threads + 127) / 128), (unsigned)ctx.S), dim3(128), 0,
+                                   ctx.stream, h->M, td, T.n_lin_roots, h->N, h->Nc, Bst, ctx.active, h->d_U, h->d_E, h->d_linA, h->d_w,
+                                   h->d_x, h->d_f, ctx.s0);
             break;
         }
-        case LIN_BUNDLE: lin_bundle(h, T, td, active, Bst, true); break;
+        case LIN_BUNDLE: lin_bundle(h, ctx, T, td, Bst, true); break;
         case LIN_TREE:
-            hipLaunchKernelGGL(k_lin_tree_back, dim3((unsigned)T.n_lin_bundles, (unsigned)h->cur_S), dim3(256), 0, h->cur_stream, h->M,
-                               td, T.d_lbrec, T.d_lbptr, T.n_lin_heights, h->N, h->Nc, Bst, active, h->d_U, h->d_E, h->d_linA, h->d_w,
-                               h->d_x, h->cur_s0);
+            hipLaunchKernelGGL(k_lin_tree_back, dim3((unsigned)T.n_lin_bundles, (unsigned)ctx.S), dim3(256), 0, ctx.stream, h->M,
+                               td, T.d_lbrec, T.d_lbptr, T.n_lin_heights, h->N, h->Nc, Bst, ctx.active, h->d_U, h->d_E, h->d_linA, h->d_w,
+                               h->d_x, ctx.s0);
             break;
         case LIN_LEVELS:
             for (int hh = T.n_lin_heights - 1; hh >= 0; --hh) {
                 const int cnt = T.lh_ptr[hh + 1] - T.lh_ptr[hh];
                 if (cnt == 0) continue;
-                hipLaunchKernelGGL(k_lin_level_back, dim3((unsigned)((cnt * h->Hn + 127) / 128), (unsigned)h->cur_S), dim3(128), 0,
-                                   h->cur_stream, h->M, td, T.d_lrec + 8 * (size_t)T.lh_ptr[hh], cnt, h->N, h->Nc, Bst, active, h->d_U,
-                                   h->d_E, h->d_linA, h->d_w, h->d_x, (double*)nullptr, 0, h->cur_s0);
+                hipLaunchKernelGGL(k_lin_level_back, dim3((unsigned)((cnt * h->Hn + 127) / 128), (unsigned)ctx.S), dim3(128), 0,
+                                   ctx.stream, h->M, td, T.d_lrec + 8 * (size_t)T.lh_ptr[hh], cnt, h->N, h->Nc, Bst, ctx.active, h->d_U,
+                                   h->d_E, h->d_linA, h->d_w, h->d_x, (double*)nullptr, 0, ctx.s0);
             }
             break;
     }
@@ -1212,53 +1210,56 @@ static int lin_back(hpf_handle* h, const Tree& T, const TreeDev& td, const int* 
 
 // elimination level l on the multi-wave kernels of blocks of BW = 12 / 28 / 52 rows (timing spans: one per launch, inside the launch helpers)
 template <int BW>
-static int factor_level(hpf_handle* h, const Tree& T, const TreeDev& td, int l, const int* active) {
+static int factor_level(hpf_handle* h, const LaunchCtx& ctx, const Tree& T, const TreeDev& td, int l) {
     const int cnt = T.lvl_ptr[l + 1] - T.lvl_ptr[l];
     const int* fdesc = T.d_fdesc + FDESC * (size_t)T.lvl_ptr[l];
     int kind = 0;                                   // (h->sw.leafbatch == 0: one workgroup per (leaf, scenario), no batched ones)
     const int nbatch = level_batched(h, T, l, &kind);
     if (level_is_fused(h, T, l, BW))                // one launch per level: batched and per-scenario workgroups side by side
-        return launch_level<BW>(h, td, fdesc, kind, nbatch, cnt - nbatch, active);
-    if (h->gj_mode != 1) return launch_factor_w<BW>(h, td, T.d_lvl_nodes + T.lvl_ptr[l], cnt, active);
-    if (nbatch == 0) return launch_factor_q<BW>(h, td, fdesc, cnt, active, T.lvl_all_leaf[l] != 0);
+        return launch_level<BW>(h, ctx, td, fdesc, kind, nbatch, cnt - nbatch);
+    if (h->gj_mode != 1) return launch_factor_w<BW>(h, ctx, td, T.d_lvl_nodes + T.lvl_ptr[l], cnt);
+    if (nbatch == 0) return launch_factor_q<BW>(h, ctx, td, fdesc, cnt, T.lvl_all_leaf[l] != 0);
     // the level's batched workgroups first (lazy leaves at level 0, vector-only bordered buses above: 16 scenarios each), then the rest
     int r;
-    if (batch_tile(h, kind) == 8) r = kind == 2 ? launch_sleaf_batch<BW, 8>(h, td, fdesc, nbatch, active) : launch_leaf_batch<BW, 8>(h, td, fdesc, nbatch, active);
-    else r = kind == 2 ? launch_sleaf_batch<BW, LB_SB>(h, td, fdesc, nbatch, active) : launch_leaf_batch<BW, LB_SB>(h, td, fdesc, nbatch, active);
-    if (!r && cnt > nbatch) r = launch_factor_q<BW>(h, td, fdesc + FDESC * (size_t)nbatch, cnt - nbatch, active, kind != 2);
+    if (note_batch_tile(h, kind, batch_tile(ctx.S, h->sw, kind)) == 8) r = kind == 2 ? launch_sleaf_batch<BW, 8>(h, ctx, td, fdesc, nbatch) : launch_leaf_batch<BW, 8>(h, ctx, td, fdesc, nbatch);
+    else r = kind == 2 ? launch_sleaf_batch<BW, LB_SB>(h, ctx, td, fdesc, nbatch) : launch_leaf_batch<BW, LB_SB>(h, ctx, td, fdesc, nbatch);
+    if (!r && cnt > nbatch) r = launch_factor_q<BW>(h, ctx, td, fdesc + FDESC * (size_t)nbatch, cnt - nbatch, kind != 2);
     return r;
 }
 
 // the generic 256-thread kernel (b > 100, and the pivoted variant for 52 < b <= 100)
-static int factor_level_generic(hpf_handle* h, const TreeDev& td, const int* nodes, int cnt, const int* active) {
+static int factor_level_generic(hpf_handle* h, const LaunchCtx& ctx, const TreeDev& td, const int* nodes, int cnt) {
     switch ((2 * h->Hn + 15) / 16) {
-        case 4: return launch_factor<4>(h, td, nodes, cnt, active);
-        case 5: return launch_factor<5>(h, td, nodes, cnt, active);
-        case 6: return launch_factor<6>(h, td, nodes, cnt, active);
-        case 7: return launch_factor<7>(h, td, nodes, cnt, active);
+        case 4: return launch_factor<4>(h, ctx, td, nodes, cnt);
+        case 5: return launch_factor<5>(h, ctx, td, nodes, cnt);
+        case 6: return launch_factor<6>(h, ctx, td, nodes, cnt);
+        case 7: return launch_factor<7>(h, ctx, td, nodes, cnt);
         default: return HPF_E_ARG;
     }
 }
 
-static int factor_sweep(hpf_handle* h, const Tree& T, const TreeDev& td, const int* active, int Bst) {
-    int r = lin_factor(h, T, td, active, Bst);
+// r = f(BW as a compile-time constant) for the block widths of the multi-wave kernels with batched bodies; false, f not called: any other width
+template <class F>
+static bool with_block_width(int BW, int& r, F f) {
+    switch (BW) {
+        case 12: r = f(std::integral_constant<int, 12>()); return true;
+        case 28: r = f(std::integral_constant<int, 28>()); return true;
+        case 52: r = f(std::integral_constant<int, 52>()); return true;
+        default: return false;
+    }
+}
+
+static int factor_sweep(hpf_handle* h, const LaunchCtx& ctx, const Tree& T, const TreeDev& td, int Bst) {
+    int r = lin_factor(h, ctx, T, td, Bst);
     if (r) return r;
     const int BW = wave_block_size(2 * h->Hn);
     for (int l = 0; l < T.n_levels; ++l) {
         const int cnt = T.lvl_ptr[l + 1] - T.lvl_ptr[l];
         if (cnt == 0) continue;
-        switch (BW) {
-            case 12: r = factor_level<12>(h, T, td, l, active); break;
-            case 28: r = factor_level<28>(h, T, td, l, active); break;
-            case 52: r = factor_level<52>(h, T, td, l, active); break;
-            case 100:       // 52 < b <= 100: general multi-wave kernel for every dense bus; pivoted mode = generic kernels
-                if (h->gj_mode == 1) {
-                    r = launch_factor_q<100>(h, td, T.d_fdesc + FDESC * (size_t)T.lvl_ptr[l], cnt, active, T.lvl_all_leaf[l] != 0);
-                    break;
-                }
-                [[fallthrough]];
-            default: r = factor_level_generic(h, td, T.d_lvl_nodes + T.lvl_ptr[l], cnt, active);
-        }
+        if (!with_block_width(BW, r, [&](auto B) { return factor_level<decltype(B)::value>(h, ctx, T, td, l); }))
+            // 52 < b <= 100: general multi-wave kernel for every dense bus; pivoted mode, and beyond 100 = generic kernels
+            r = BW == 100 && h->gj_mode == 1 ? launch_factor_q<100>(h, ctx, td, T.d_fdesc + FDESC * (size_t)T.lvl_ptr[l], cnt, T.lvl_all_leaf[l] != 0)
+                                             : factor_level_generic(h, ctx, td, T.d_lvl_nodes + T.lvl_ptr[l], cnt);
         if (r) return r;
     }
     return HPF_OK;
@@ -1267,8 +1268,8 @@ static int factor_sweep(hpf_handle* h, const Tree& T, const TreeDev& td, const i
 // one launch per depth for all bus kinds (k_level_back) where the batched bodies exist and every body has four wavefronts
 // (groups of up to 32 scenarios only: larger launches are throughput-bound, and k_back_q alone runs at twice the
 //  occupancy of the fused kernel -- 5.2 vs 5.4 ms per step at 1 024 scenarios, 0.297 vs 0.288 ms at one)
-static bool back_is_fused(const hpf_handle* h, const Tree& T, int BW) {
-    bool fused = h->sw.fuse_back && h->cur_S <= h->sw.fuse_back_max && h->sw.leafbatch && h->has_ctree && h->gj_mode == 1 && BW == 52 &&
+static bool back_is_fused(const hpf_handle* h, const LaunchCtx& ctx, const Tree& T, int BW) {
+    bool fused = h->sw.fuse_back && ctx.S <= h->sw.fuse_back_max && h->sw.leafbatch && h->has_ctree && h->gj_mode == 1 && BW == 52 &&
                  (int)T.bsl_dep_ptr.size() == T.n_depths + 1 && (int)T.bleaf_dep_ptr.size() == T.n_depths + 1 && (int)T.dep_nleaf.size() >= T.n_depths;
     for (int dl = 1; fused && dl < T.n_depths; ++dl)            // (a depth's batched records are exactly its leaves + bordered buses)
         fused = T.bsl_dep_ptr[dl + 1] - T.bsl_dep_ptr[dl] + T.bleaf_dep_ptr[dl + 1] - T.bleaf_dep_ptr[dl] == T.dep_nleaf[dl];
@@ -1278,19 +1279,19 @@ static bool back_is_fused(const hpf_handle* h, const Tree& T, int BW) {
 // back-sweep depth dl on the multi-wave kernels of blocks of BW = 12 / 28 / 52 rows; its first nlb buses are constant-inverse leaves
 // that wait for the one batched launch after the last depth
 template <int BW>
-static int back_depth(hpf_handle* h, const Tree& T, const TreeDev& td, int dl, int nlb, const int* active) {
+static int back_depth(hpf_handle* h, const LaunchCtx& ctx, const Tree& T, const TreeDev& td, int dl, int nlb) {
     const int cnt = T.dep_ptr[dl + 1] - T.dep_ptr[dl];
-    if (h->gj_mode != 1) return launch_back_w<BW>(h, td, T.d_dep_nodes + T.dep_ptr[dl], cnt, active);
-    return cnt > nlb ? launch_back_q<BW>(h, td, T.d_bdesc + 4 * (size_t)(T.dep_ptr[dl] + nlb), cnt - nlb, active) : HPF_OK;
+    if (h->gj_mode != 1) return launch_back_w<BW>(h, ctx, td, T.d_dep_nodes + T.dep_ptr[dl], cnt);
+    return cnt > nlb ? launch_back_q<BW>(h, ctx, td, T.d_bdesc + 4 * (size_t)(T.dep_ptr[dl] + nlb), cnt - nlb) : HPF_OK;
 }
 
 // every bordered bus and constant-inverse leaf at once, 16 scenarios per workgroup: a leaf's x needs its parent's only, and nothing of the
 // dense tree hangs below a leaf (the 2x2 kernels that do come next) -- in one launch that walks their families (k_back_tail), or with
 // HPF_BACKTAIL=0 in one launch per nesting order of the bordered buses and one for the leaves
 template <int BW>
-static int back_batched(hpf_handle* h, const Tree& T, const int* active) {
+static int back_batched(hpf_handle* h, const LaunchCtx& ctx, const Tree& T) {
     if (h->sw.back_tail && T.n_tail_fam > 0 && T.d_tail_rec) {
-        if (int r = launch_back_tail<BW>(h, T, active)) return r;
+        if (int r = launch_back_tail<BW>(h, ctx, T)) return r;
         ++h->n_back_tails;
         return HPF_OK;
     }
@@ -1298,83 +1299,68 @@ static int back_batched(hpf_handle* h, const Tree& T, const int* active) {
     for (size_t gi = 0; gi + 1 < T.bsleaf_ptr.size() && T.n_bsleaf > 0; ++gi) {
         const int b0 = T.bsleaf_ptr[gi], cnt = T.bsleaf_ptr[gi + 1] - b0;
         if (cnt <= 0) continue;
-        if (int r = launch_sleaf_back_batch<BW>(h, T.d_bsleaf + 8 * (size_t)b0, cnt, active)) return r;
+        if (int r = launch_sleaf_back_batch<BW>(h, ctx, T.d_bsleaf + 8 * (size_t)b0, cnt)) return r;
     }
-    return T.n_bleaf > 0 ? launch_leaf_back_batch<BW>(h, T.d_bleaf, T.n_bleaf, active) : HPF_OK;
+    return T.n_bleaf > 0 ? launch_leaf_back_batch<BW>(h, ctx, T.d_bleaf, T.n_bleaf) : HPF_OK;
 }
 
 // the Gauss-Jordan buses of the back sweep in two tree walks (k_back_walk) instead of one launch per depth; its batched workgroups
 // (bordered buses, constant-inverse leaves) follow in back_batched
-static bool back_walks(const hpf_handle* h, const Tree& T, int BW) {
-    return h->sw.back_walk && h->cur_S >= h->sw.back_walk_min && h->cur_S <= h->sw.back_walk_max && h->sw.leafbatch && h->has_ctree && h->gj_mode == 1 && BW == 52 &&
+static bool back_walks(const hpf_handle* h, const LaunchCtx& ctx, const Tree& T, int BW) {
+    return h->sw.back_walk && ctx.S >= h->sw.back_walk_min && ctx.S <= h->sw.back_walk_max && h->sw.leafbatch && h->has_ctree && h->gj_mode == 1 && BW == 52 &&
            T.walk_ptr.size() == (size_t)T.walk_lists + 2;
 }
 
-static int back_sweep(hpf_handle* h, const Tree& T, const TreeDev& td, const int* active, int Bst) {
-    ScopedTimer tb(h, T_BACK);
+static int back_sweep(hpf_handle* h, const LaunchCtx& ctx, const Tree& T, const TreeDev& td, int Bst) {
+    ScopedTimer tb(h, T_BACK, ctx.stream);
     const int BW = wave_block_size(2 * h->Hn);
-    const bool walk = back_walks(h, T, BW);
-    const bool fused_back = !walk && back_is_fused(h, T, BW);
+    const bool walk = back_walks(h, ctx, T, BW);
+    const bool fused_back = !walk && back_is_fused(h, ctx, T, BW);
     if (walk) {
-        int r = launch_back_walk<52>(h, T, td, 0, 1, active);
-        if (!r && T.walk_lists > 0) r = launch_back_walk<52>(h, T, td, 1, T.walk_lists, active);
+        int r = launch_back_walk<52>(h, ctx, T, td, 0, 1);
+        if (!r && T.walk_lists > 0) r = launch_back_walk<52>(h, ctx, T, td, 1, T.walk_lists);
         if (r) return r;
         ++h->n_back_walks;
     }
     for (int dl = 0; dl < (walk ? 0 : T.n_depths); ++dl) {
         const int cnt = T.dep_ptr[dl + 1] - T.dep_ptr[dl];
         if (cnt == 0) continue;
-        const int* nodes = T.d_dep_nodes + T.dep_ptr[dl];
         const int nlb = (h->sw.leafbatch && h->has_ctree && dl > 0 && dl < (int)T.dep_nleaf.size()) ? T.dep_nleaf[dl] : 0;
         int r = HPF_OK;
         if (fused_back) {
             const int n_sl = dl > 0 ? T.bsl_dep_ptr[dl + 1] - T.bsl_dep_ptr[dl] : 0, n_lf = dl > 0 ? T.bleaf_dep_ptr[dl + 1] - T.bleaf_dep_ptr[dl] : 0;
-            r = launch_level_back<52>(h, td, T.d_bsleaf_dep + 8 * (size_t)T.bsl_dep_ptr[dl], n_sl, T.d_bleaf + 4 * (size_t)T.bleaf_dep_ptr[dl], n_lf,
-                                      T.d_bdesc + 4 * (size_t)(T.dep_ptr[dl] + nlb), cnt - nlb, active);
+            r = launch_level_back<52>(h, ctx, td, T.d_bsleaf_dep + 8 * (size_t)T.bsl_dep_ptr[dl], n_sl, T.d_bleaf + 4 * (size_t)T.bleaf_dep_ptr[dl], n_lf,
+                                      T.d_bdesc + 4 * (size_t)(T.dep_ptr[dl] + nlb), cnt - nlb);
+        } else if (with_block_width(BW, r, [&](auto B) { return back_depth<decltype(B)::value>(h, ctx, T, td, dl, nlb); })) {
+            // (done)
+        } else if (BW == 100 && h->gj_mode == 1) {
+            r = launch_back_q<100>(h, ctx, td, T.d_bdesc + 4 * (size_t)T.dep_ptr[dl], cnt);
         } else {
-            switch (BW) {
-                case 12: r = back_depth<12>(h, T, td, dl, nlb, active); break;
-                case 28: r = back_depth<28>(h, T, td, dl, nlb, active); break;
-                case 52: r = back_depth<52>(h, T, td, dl, nlb, active); break;
-                case 100:
-                    if (h->gj_mode == 1) {
-                        r = launch_back_q<100>(h, td, T.d_bdesc + 4 * (size_t)T.dep_ptr[dl], cnt, active);
-                        break;
-                    }
-                    [[fallthrough]];
-                default:
-                    hipLaunchKernelGGL(k_tree_back, dim3((unsigned)cnt, (unsigned)h->cur_S), dim3(256), 0, h->cur_stream, h->n, h->c,
-                                       h->Hn, td, nodes, 2 * h->Hn, h->N, h->Nc, active, h->d_Z, h->d_w, h->d_x, h->d_f, h->cur_s0);
-                    r = launch_status(h);
-            }
+            hipLaunchKernelGGL(k_tree_back, dim3((unsigned)cnt, (unsigned)ctx.S), dim3(256), 0, ctx.stream, h->n, h->c, h->Hn, td,
+                               T.d_dep_nodes + T.dep_ptr[dl], 2 * h->Hn, h->N, h->Nc, ctx.active, h->d_Z, h->d_w, h->d_x, h->d_f, ctx.s0);
+            r = launch_status(h);
         }
         if (r) return r;
     }
     if (h->sw.leafbatch && !fused_back && h->has_ctree && h->gj_mode == 1) {
         int r = HPF_OK;
-        switch (BW) {
-            case 12: r = back_batched<12>(h, T, active); break;
-            case 28: r = back_batched<28>(h, T, active); break;
-            case 52: r = back_batched<52>(h, T, active); break;
-            default: break;
-        }
+        with_block_width(BW, r, [&](auto B) { return back_batched<decltype(B)::value>(h, ctx, T); });
         if (r) return r;
     }
-    return lin_back(h, T, td, active, Bst);
+    return lin_back(h, ctx, T, td, Bst);
 }
 
-int tree_newton_step(hpf_handle* h, bool only_active) {
+int tree_newton_step(hpf_handle* h, const LaunchCtx& ctx, TreePass pass) {
     const Tree& T = active_tree(h);
-    const int* active = only_active ? h->d_active : nullptr;
     const TreeDev td{T.d_parent, T.d_child_ptr, T.d_child, T.d_e_up, T.d_e_dn, T.d_child_mid, T.d_lin_ptr, T.d_lin_post, T.d_child3, T.d_dchild, T.d_chain_ptr, T.d_chain_nodes, T.d_chain_ch, T.d_lzrec, T.d_lzimg,
                      h->d_F, h->d_H2, T.d_comp_child, T.n_comp};
     const int b = 2 * h->Hn, BW = wave_block_size(b);
     const int Bst = BW ? BW : b;
-    if (!h->tree_back_only) {                                        // (factor-once bordered step: its second pass is a back sweep alone)
-        const int r = factor_sweep(h, T, td, active, Bst);
+    if (pass != BACK_ONLY) {                                         // (factor-once bordered step: its second pass is a back sweep alone)
+        const int r = factor_sweep(h, ctx, T, td, Bst);
         if (r) return r;
     }
-    return back_sweep(h, T, td, active, Bst);
+    return back_sweep(h, ctx, T, td, Bst);
 }
 
 // BFS spanning tree of the admittance pattern from bus 0 (the SAME visiting order as tree_build_into) and the entries that are
@@ -1925,18 +1911,18 @@ static void border_block_gj(hpf_handle* h, int cn, hipStream_t st) {
     hipLaunchKernelGGL(k_border_g_blocks, dim3((unsigned)((mT * b + 255) / 256), (unsigned)cn), dim3(256), 0, st, b, mT, (const double*)h->d_bB, h->d_sel_g);
 }
 
-// Newton step of a meshed handle in the factor-once form, for the running scenarios of slots h->cur_s0 .. + h->cur_S (see tree_newton_step_bordered):
+// Newton step of a meshed handle in the factor-once form, for the running scenarios of the context's slots (see tree_newton_step_bordered):
 //   1. ONE sweep of the tree for all of them (their own right-hand sides, their own slots: y = J_t^-1 f and the factors);
 //   2. in batches of sel_cap scenarios: selected inversion -> border matrices, border solve (block Gauss-Jordan, or rocSOLVER's unpivoted LU one
 //      system after the other), residual check of every solution against the untouched column-major copy -- ONE host synchronisation per batch --,
 //      pivoted rocSOLVER LU for the systems that fail it, correction of the forward vectors on P;
 //   3. the back sweep alone for all of them.
-static int tree_newton_step_sel(hpf_handle* h, bool only_active) {
+static int tree_newton_step_sel(hpf_handle* h, const LaunchCtx& ctx) {
     const int m = h->m_border, b = 2 * h->Hn, BW = wave_block_size(b), n = h->n;
-    const int s0 = h->cur_s0, cnt = h->cur_S;
-    hipStream_t st = h->cur_stream;
-    const int* active = only_active ? h->d_active : nullptr;
-    int rc = tree_newton_step(h, only_active);
+    const int s0 = ctx.s0, cnt = ctx.S;
+    hipStream_t st = ctx.stream;
+    const int* active = ctx.active;
+    int rc = tree_newton_step(h, ctx, FACTOR_AND_BACK);
     if (rc) return rc;
     for (int c0 = 0; c0 < cnt; c0 += h->sel_cap) {
         const int cn = cnt - c0 < h->sel_cap ? cnt - c0 : h->sel_cap;
@@ -1967,7 +1953,7 @@ static int tree_newton_step_sel(hpf_handle* h, bool only_active) {
         }
         const bool info_on = h->sw.border_info;
         for (int y = 0; y < cn; ++y) {
-            const int sc = only_active ? ((size_t)(sb + y) < h->host_act.size() ? h->host_act[sb + y] : -1) : sb + y;
+            const int sc = active ? ((size_t)(sb + y) < h->host_act.size() ? h->host_act[sb + y] : -1) : sb + y;
             if (sc < 0) continue;
             double r0, r1;
             memcpy(&r0, &h->sel_res_host[2 * y], sizeof(double));
@@ -1999,22 +1985,19 @@ static int tree_newton_step_sel(hpf_handle* h, bool only_active) {
                                h->d_sel_hl + h->sel_hl_ptr[l], h->d_sel_P, h->d_sel_slot, h->d_sel_cptr, h->d_sel_clist, (const double*)h->d_sel_S,
                                (const double*)h->d_sel_Up, (const double*)h->d_sel_g, h->d_sel_dw, h->d_w);
     }
-    h->tree_back_only = true;
-    rc = tree_newton_step(h, only_active);
-    h->tree_back_only = false;
-    if (rc) return rc;
+    if ((rc = tree_newton_step(h, ctx, BACK_ONLY))) return rc;
     return launch_status(h);
 }
 
-int tree_newton_step_bordered(hpf_handle* h, bool only_active) {
-    if (h->mesh_sel) return tree_newton_step_sel(h, only_active);
+int tree_newton_step_bordered(hpf_handle* h, const LaunchCtx& ctx) {
+    if (h->mesh_sel) return tree_newton_step_sel(h, ctx);
     const int m = h->m_border, VC = border_slots(h), v0 = h->S_max;
     const int b = 2 * h->Hn, BW = wave_block_size(b), n = h->n;
-    const int s0 = h->cur_s0, cnt = h->cur_S;
-    hipStream_t st = h->stream;
+    // (a meshed handle runs one scenario group: the context's stream is the handle's, which group 0 of the virtual sweeps below shares)
+    hipStream_t st = ctx.stream;
     std::vector<int> todo;
-    for (int slot = s0; slot < s0 + cnt; ++slot) {
-        const int sc = only_active ? ((size_t)slot < h->host_act.size() ? h->host_act[slot] : -1) : slot;
+    for (int slot = ctx.s0; slot < ctx.s0 + ctx.S; ++slot) {
+        const int sc = ctx.active ? ((size_t)slot < h->host_act.size() ? h->host_act[slot] : -1) : slot;
         if (sc >= 0) todo.push_back(sc);
     }
     const int save_groups = h->n_groups;
@@ -2028,17 +2011,11 @@ int tree_newton_step_bordered(hpf_handle* h, bool only_active) {
             const int a0 = (int)((long long)V * g / G), a1 = (int)((long long)V * (g + 1) / G);
             hipStream_t gs = G > 1 ? group_stream(h, g) : st;
             if (G > 1) hipStreamWaitEvent(gs, h->fork_ev, 0);
-            h->cur_stream = gs;
-            h->cur_s0 = v0 + a0;
-            h->cur_S = a1 - a0;
-            rc = tree_newton_step(h, false);
+            rc = tree_newton_step(h, LaunchCtx{gs, v0 + a0, a1 - a0, nullptr}, FACTOR_AND_BACK);
             if (G > 1) hipEventRecord(h->join_ev[g], gs);
         }
         if (G > 1)
             for (int g = 0; g < G; ++g) hipStreamWaitEvent(st, h->join_ev[g], 0);
-        h->cur_stream = st;
-        h->cur_s0 = s0;
-        h->cur_S = cnt;
         return rc;
     };
     for (int r : todo) {

@@ -232,7 +232,6 @@ struct hpf_handle {
     double *d_sel_tie = nullptr;      // [2 n_ties][Hn][4] the ties' coupling blocks of the current state
     void *d_sel_jobs = nullptr;       // BlkJob list: forward by height, back by depth
     std::vector<size_t> sel_fwd_beg, sel_back_beg, sel_hl_ptr;
-    bool tree_back_only = false;      // tree_newton_step skips its factor part (set around that second pass only)
     int *d_sel_hl = nullptr, *d_sel_slot = nullptr, *d_sel_cptr = nullptr, *d_sel_clist = nullptr;   // P by height | endpoint number | children in P
     double *d_sel_dw = nullptr;       // [nP][b] corrections of the forward vectors
     int sel_cap = 1;                  // scenarios whose selected inversion / border solve run as one batch (every d_sel_* / d_bB buffer holds that many)
@@ -340,8 +339,8 @@ struct hpf_handle {
     hpf::Tree ctree;                  // the same with pass-through buses contracted (multi-wave kernels, gj_mode 1)
     bool has_ctree = false;
     long long n_back_tails = 0;       // back sweeps whose bordered buses and constant-inverse leaves went through k_back_tail (hpf_tree_census[16])
-    int last_batch_tile = 0;          // scenarios per batched workgroup of the last factor launch with bordered buses (16 or 8; 0: none yet; hpf_tree_census[17])
-    int last_leaf_tile = 0;           // ... with lazy leaves (hpf_tree_census[18])
+    int last_batch_tile = 0;          // scenarios per batched workgroup of the last factor launch with bordered buses (16 or 8; 0: none yet; CENSUS_BATCH_TILE)
+    int last_leaf_tile = 0;           // ... with lazy leaves (CENSUS_LEAF_BATCH_TILE); both written by note_batch_tile at the dispatch sites that launch
     long long n_back_walks = 0;       // back sweeps (scenario group x Newton step) whose Gauss-Jordan buses went through k_back_walk (hpf_tree_census[15])
     int auto_repivot = 1;             // hpf_solve repeats scenarios flagged by the static-pivot monitor with partial pivoting
     int* h_act[2] = {nullptr, nullptr};          // pinned copies of the slot counter d_nactive, and of the queue's `next` (poll_post / poll_wait: the host looks at chunk c - 1 while chunk c runs)
@@ -367,10 +366,6 @@ struct hpf_handle {
     double* d_H2 = nullptr;           // [S][n_comp][Hn][4] A(v,c) of the compressed buses (back sweep)
 
     hipStream_t own_stream = nullptr, stream = nullptr;
-    // launch context: stream and scenario slice the launch helpers currently target (scenario groups run as independent
-    // pipelines on their own streams so that the latency-bound upper tree levels of one group overlap the others)
-    hipStream_t cur_stream = nullptr;
-    int cur_s0 = 0, cur_S = 0;
     int n_groups = 4;                 // (initially sw.n_groups) "scenario_groups"
     hipStream_t gstream[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // groups 1..7 (group 0: the handle's stream, group_stream)
     hipEvent_t fork_ev = nullptr, join_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -412,20 +407,37 @@ inline int launch_status(hpf_handle* h) {
 // runtime maps streams onto four queues; a fifth busy stream shares one and serialises two groups: 1.25 instead of 0.90 ms per step at G = 4)
 inline hipStream_t group_stream(const hpf_handle* h, int g) { return g == 0 ? h->stream : h->gstream[g]; }
 
+// Launch context: the stream and the scenario slice [s0, s0 + S) a launch helper targets, and the slot list of the slice (nullptr: every
+// scenario of it).  A value handed down the call chain -- scenario groups run as independent pipelines on their own streams, so that the
+// latency-bound upper tree levels of one group overlap the others, and a nested sweep (the bordered step) builds its own.
+struct LaunchCtx { hipStream_t stream; int s0, S; const int* active; };
+// the whole batch on the handle's stream
+inline LaunchCtx batch_ctx(const hpf_handle* h, const int* active = nullptr) { return {h->stream, 0, h->S, active}; }
+
+// which part of tree_newton_step runs (BACK_ONLY: the second pass of the factor-once bordered step)
+enum TreePass { FACTOR_AND_BACK, BACK_ONLY };
+
+// words of hpf_tree_census behind the tree's own eight (Tree::census), in the ABI's order (device.py: tree_census names them alike)
+enum CensusWord {
+    CENSUS_TIES = 8, CENSUS_FUSED_LEVELS, CENSUS_COMPRESS_STEPS, CENSUS_BORDER_REPIVOTS, CENSUS_BORDER_UNKNOWNS, CENSUS_ROOT_PATH_BUSES,
+    CENSUS_BORDERED_FORM, CENSUS_BACK_WALKS, CENSUS_BACK_TAILS, CENSUS_BATCH_TILE, CENSUS_LEAF_BATCH_TILE, CENSUS_WORDS
+};
+
 struct ScopedTimer {
     hpf_handle* h;
     int which;
+    hipStream_t stream;               // the stream the span is recorded on: the launch context's
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    ScopedTimer(hpf_handle* h_, int w) : h(h_), which(w) {
+    ScopedTimer(hpf_handle* h_, int w, hipStream_t st) : h(h_), which(w), stream(st) {
         if (h->timing == 1) {
             hipEventCreate(&e0);
             hipEventCreate(&e1);
-            hipEventRecord(e0, h->cur_stream);
+            hipEventRecord(e0, stream);
         }
     }
     ~ScopedTimer() {
         if (h->timing == 1) {
-            hipEventRecord(e1, h->cur_stream);
+            hipEventRecord(e1, stream);
             h->spans.push_back({which, e0, e1});
         }
     }
@@ -438,9 +450,9 @@ int tree_plan_dump(const hpf_desc* d, const char* path);  // host-only planning 
 hpf::Tree& active_tree(hpf_handle* h);
 bool tree_levels_fused(hpf_handle* h);                   // every elimination level of the current mode is one k_level launch
 int tree_alloc_scenarios(hpf_handle* h);
-int tree_fund_step(hpf_handle* h, bool only_active);     // fundamental pf Newton step on the tree (2x2 blocks)
-int tree_newton_step(hpf_handle* h, bool only_active);   // assembles, eliminates, back-substitutes -> d_f holds the step
-int tree_newton_step_bordered(hpf_handle* h, bool only_active);   // the same for a network with loop-closing lines (h->n_ties > 0)
+int tree_fund_step(hpf_handle* h, const LaunchCtx& ctx);   // fundamental pf Newton step on the tree (2x2 blocks)
+int tree_newton_step(hpf_handle* h, const LaunchCtx& ctx, TreePass pass);   // assembles, eliminates, back-substitutes -> d_f holds the step
+int tree_newton_step_bordered(hpf_handle* h, const LaunchCtx& ctx);   // the same for a network with loop-closing lines (h->n_ties > 0)
 int ensure_blas(hpf_handle* h);                                   // rocBLAS handle on first use (dense LU, border system)
 int border_slots(const hpf_handle* h);                            // virtual scenario slots of the bordered step (behind the S_max real ones)
 int tree_sel_build(hpf_handle* h, const hpf_desc* d);             // factor-once bordered step: P, forward pairs, block-product jobs, buffers (after tree_build)

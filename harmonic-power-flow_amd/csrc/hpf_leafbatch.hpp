@@ -269,12 +269,12 @@ __global__ __launch_bounds__(256, 4) void k_leaf_batch(
 }
 
 template <int B, int SB>
-int launch_leaf_batch(hpf_handle* h, const TreeDev& T, const int* nodes, int count, const int* active) {
-    ScopedTimer t(h, T_SOLVE);
-    const dim3 grid((unsigned)count, (unsigned)BatchTile<SB>::tiles(h->cur_S));
-    hipLaunchKernelGGL((k_leaf_batch<B, SB>), grid, dim3(256), 0, h->cur_stream, h->M, T, nodes, 2 * h->Hn, active, h->cur_S, h->d_U,
+int launch_leaf_batch(hpf_handle* h, const LaunchCtx& ctx, const TreeDev& T, const int* nodes, int count) {
+    ScopedTimer t(h, T_SOLVE, ctx.stream);
+    const dim3 grid((unsigned)count, (unsigned)BatchTile<SB>::tiles(ctx.S));
+    hipLaunchKernelGGL((k_leaf_batch<B, SB>), grid, dim3(256), 0, ctx.stream, h->M, T, nodes, 2 * h->Hn, ctx.active, ctx.S, h->d_U,
                        h->d_E, h->d_fb, h->d_w, h->d_linA, h->d_C, h->d_H, h->d_chG, h->d_chH, h->d_chD, h->d_chy,
-                       active_tree(h).d_lbimg, h->d_lfK, h->d_lfS, h->cur_s0);
+                       active_tree(h).d_lbimg, h->d_lfK, h->d_lfS, ctx.s0);
     return launch_status(h);
 }
 
@@ -486,10 +486,10 @@ __global__ __launch_bounds__(256) void k_leaf_back_batch(
 }
 
 template <int B>
-int launch_leaf_back_batch(hpf_handle* h, const int* nodes, int count, const int* active) {
-    const dim3 grid((unsigned)count, (unsigned)((h->cur_S + LB_SB - 1) / LB_SB));
-    hipLaunchKernelGGL((k_leaf_back_batch<B>), grid, dim3(256), 0, h->cur_stream, h->M, nodes, 2 * h->Hn, active, h->cur_S, h->d_w,
-                       h->d_x, h->d_H, active_tree(h).d_lbimg, h->d_lfK, h->d_lfS, h->cur_s0);
+int launch_leaf_back_batch(hpf_handle* h, const LaunchCtx& ctx, const int* nodes, int count) {
+    const dim3 grid((unsigned)count, (unsigned)((ctx.S + LB_SB - 1) / LB_SB));
+    hipLaunchKernelGGL((k_leaf_back_batch<B>), grid, dim3(256), 0, ctx.stream, h->M, nodes, 2 * h->Hn, ctx.active, ctx.S, h->d_w,
+                       h->d_x, h->d_H, active_tree(h).d_lbimg, h->d_lfK, h->d_lfS, ctx.s0);
     return launch_status(h);
 }
 
@@ -672,10 +672,10 @@ __global__ __launch_bounds__(256) void k_sleaf_back_batch(
 }
 
 template <int B>
-int launch_sleaf_back_batch(hpf_handle* h, const int* nodes, int count, const int* active) {
-    const dim3 grid((unsigned)count, (unsigned)((h->cur_S + LB_SB - 1) / LB_SB));
-    hipLaunchKernelGGL((k_sleaf_back_batch<B>), grid, dim3(256), 0, h->cur_stream, h->M, nodes, 2 * h->Hn, active, h->cur_S, h->d_w,
-                       h->d_x, h->d_H, active_tree(h).d_sbimg, active_tree(h).d_lzimg, h->d_Z, h->d_lfS, h->cur_s0);
+int launch_sleaf_back_batch(hpf_handle* h, const LaunchCtx& ctx, const int* nodes, int count) {
+    const dim3 grid((unsigned)count, (unsigned)((ctx.S + LB_SB - 1) / LB_SB));
+    hipLaunchKernelGGL((k_sleaf_back_batch<B>), grid, dim3(256), 0, ctx.stream, h->M, nodes, 2 * h->Hn, ctx.active, ctx.S, h->d_w,
+                       h->d_x, h->d_H, active_tree(h).d_sbimg, active_tree(h).d_lzimg, h->d_Z, h->d_lfS, ctx.s0);
     return launch_status(h);
 }
 
@@ -750,10 +750,10 @@ __global__ __launch_bounds__(256) void k_back_tail(
 }
 
 template <int B>
-int launch_back_tail(hpf_handle* h, const Tree& tr, const int* active) {
-    const dim3 grid((unsigned)tr.n_tail_fam, (unsigned)((h->cur_S + LB_SB - 1) / LB_SB));
-    hipLaunchKernelGGL((k_back_tail<B>), grid, dim3(256), 0, h->cur_stream, h->M, tr.d_tail_ptr, tr.d_tail_rec, tr.d_bsleaf, tr.d_bleaf, 2 * h->Hn,
-                       active, h->cur_S, h->d_w, h->d_x, h->d_H, tr.d_sbimg, tr.d_lzimg, tr.d_lbimg, h->d_Z, h->d_lfK, h->d_lfS, h->cur_s0);
+int launch_back_tail(hpf_handle* h, const LaunchCtx& ctx, const Tree& tr) {
+    const dim3 grid((unsigned)tr.n_tail_fam, (unsigned)((ctx.S + LB_SB - 1) / LB_SB));
+    hipLaunchKernelGGL((k_back_tail<B>), grid, dim3(256), 0, ctx.stream, h->M, tr.d_tail_ptr, tr.d_tail_rec, tr.d_bsleaf, tr.d_bleaf, 2 * h->Hn,
+                       ctx.active, ctx.S, h->d_w, h->d_x, h->d_H, tr.d_sbimg, tr.d_lzimg, tr.d_lbimg, h->d_Z, h->d_lfK, h->d_lfS, ctx.s0);
     return launch_status(h);
 }
 
@@ -1189,11 +1189,11 @@ __global__ __launch_bounds__(256, 4) void k_sleaf_batch(
 }
 
 template <int B, int SB>
-int launch_sleaf_batch(hpf_handle* h, const TreeDev& T, const int* nodes, int count, const int* active) {
-    ScopedTimer t(h, T_SOLVE);
-    const dim3 grid((unsigned)count, (unsigned)BatchTile<SB>::tiles(h->cur_S));
-    hipLaunchKernelGGL((k_sleaf_batch<B, SB>), grid, dim3(256), 0, h->cur_stream, h->M, T, nodes, 2 * h->Hn, active, h->cur_S, h->d_U,
+int launch_sleaf_batch(hpf_handle* h, const LaunchCtx& ctx, const TreeDev& T, const int* nodes, int count) {
+    ScopedTimer t(h, T_SOLVE, ctx.stream);
+    const dim3 grid((unsigned)count, (unsigned)BatchTile<SB>::tiles(ctx.S));
+    hipLaunchKernelGGL((k_sleaf_batch<B, SB>), grid, dim3(256), 0, ctx.stream, h->M, T, nodes, 2 * h->Hn, ctx.active, ctx.S, h->d_U,
                        h->d_E, h->d_fb, h->d_w, h->d_linA, h->d_C, h->d_H, h->d_I0, h->d_chG, h->d_chH, h->d_chD, h->d_chy,
-                       active_tree(h).d_sbimg, h->d_Z, h->d_lfK, h->d_lfS, h->cur_s0, h->d_dbg, h->sw.debug_ablate);
+                       active_tree(h).d_sbimg, h->d_Z, h->d_lfK, h->d_lfS, ctx.s0, h->d_dbg, h->sw.debug_ablate);
     return launch_status(h);
 }

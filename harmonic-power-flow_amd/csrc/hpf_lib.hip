@@ -1326,18 +1326,9 @@ int resolve_spans(hpf_handle* h) {
 }
 
 
-// launch context = (stream, first scenario, scenario count) used by the launch helpers
-inline void set_ctx(hpf_handle* h, hipStream_t st, int s0, int cnt) {
-    h->cur_stream = st;
-    h->cur_s0 = s0;
-    h->cur_S = cnt;
-}
-inline void full_ctx(hpf_handle* h) { set_ctx(h, h->stream, 0, h->S); }
-
-// polar + mismatch (+ optional err conversion) for the current state
+// U, E of the whole batch from its polar state (always every scenario, on the handle's stream)
 template <bool FUND>
 int launch_polar(hpf_handle* h) {
-    full_ctx(h);
     const int count = FUND ? h->n : h->n * h->Hn;
     hipLaunchKernelGGL((k_polar<FUND>), grid2(count, h->S), dim3(TPB), 0, h->stream, count, h->n * h->Hn, h->Hn, h->d_Vm,
                        h->d_Va, h->d_U, h->d_E);
@@ -1354,8 +1345,8 @@ static int err_parts(const hpf_handle* h) { return (TPB / 64) * (((FUND ? h->n :
 
 // stacked: also write the mismatch in the reference's stacked order (C ABI, dense solver, single-wave / generic tree kernels)
 template <bool FUND>
-int launch_mismatch(hpf_handle* h, const int* active, bool stacked = true) {
-    ScopedTimer t(h, T_MISMATCH);
+int launch_mismatch(hpf_handle* h, const LaunchCtx& ctx, bool stacked = true) {
+    ScopedTimer t(h, T_MISMATCH, ctx.stream);
     const int count = FUND ? h->n : h->n * h->Hn;
     const int N = FUND ? h->Nf : h->N;
     const int Nc = FUND ? h->n - 1 : h->Nc;
@@ -1372,9 +1363,9 @@ int launch_mismatch(hpf_handle* h, const int* active, bool stacked = true) {
             // (per launch: the attribute belongs to the device the handle runs on, and the call costs nothing next to the launch)
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         }
-        hipLaunchKernelGGL(kern, xcd_grid(nbx, h->cur_S), dim3(TPB), lds, h->cur_stream, h->M, count, N, Nc,
-                           active, h->d_U, h->d_P, h->d_Q, (stacked || !img) ? h->d_f : nullptr, h->d_errpart, h->errpart_stride, h->d_I0,
-                           img ? h->d_fb : nullptr, tree_bst(h), h->cur_s0, h->cur_S, div_magic(h->Hn),
+        hipLaunchKernelGGL(kern, xcd_grid(nbx, ctx.S), dim3(TPB), lds, ctx.stream, h->M, count, N, Nc,
+                           ctx.active, h->d_U, h->d_P, h->d_Q, (stacked || !img) ? h->d_f : nullptr, h->d_errpart, h->errpart_stride, h->d_I0,
+                           img ? h->d_fb : nullptr, tree_bst(h), ctx.s0, ctx.S, div_magic(h->Hn),
                            (!FUND && h->src_set) ? h->d_src : (const cplx*)nullptr);
         if (launch_status(h)) return HPF_E_HIP;
     }
@@ -1382,19 +1373,20 @@ int launch_mismatch(hpf_handle* h, const int* active, bool stacked = true) {
 }
 
 template <bool FUND>
-int launch_jacobian_dense(hpf_handle* h, const int* active) {
-    ScopedTimer t(h, T_JACOBIAN);
+int launch_jacobian_dense(hpf_handle* h, const LaunchCtx& ctx) {
+    ScopedTimer t(h, T_JACOBIAN, ctx.stream);
     const int N = FUND ? h->Nf : h->N;
     const int Nc = FUND ? h->n - 1 : h->Nc;
-    HIPCHK(hipMemsetAsync(h->d_J, 0, sizeof(double) * h->J_elems_per_scen * (size_t)h->S, h->stream));
+    // (the dense solver never runs in scenario groups: its slice is the whole batch, ctx.s0 == 0)
+    HIPCHK(hipMemsetAsync(h->d_J, 0, sizeof(double) * h->J_elems_per_scen * (size_t)ctx.S, ctx.stream));
     const int total = (FUND ? 1 : h->Hn) * h->nnz;
-    hipLaunchKernelGGL((k_jac_dense<FUND>), grid2(total, h->S), dim3(TPB), 0, h->stream, h->M, total, N, Nc,
-                       h->J_elems_per_scen, active, h->d_erow, h->d_U, h->d_E, h->d_J);
+    hipLaunchKernelGGL((k_jac_dense<FUND>), grid2(total, ctx.S), dim3(TPB), 0, ctx.stream, h->M, total, N, Nc,
+                       h->J_elems_per_scen, ctx.active, h->d_erow, h->d_U, h->d_E, h->d_J);
     if (launch_status(h)) return HPF_E_HIP;
     if (!FUND && h->coupled && h->n > h->m) {
         const int tot = (h->n - h->m) * h->Hn * h->Hn;
-        hipLaunchKernelGGL(k_jac_cross_dense, grid2(tot, h->S), dim3(TPB), 0, h->stream, h->M, tot, N, Nc,
-                           h->J_elems_per_scen, active, h->d_U, h->d_E, h->d_J);
+        hipLaunchKernelGGL(k_jac_cross_dense, grid2(tot, ctx.S), dim3(TPB), 0, ctx.stream, h->M, tot, N, Nc,
+                           h->J_elems_per_scen, ctx.active, h->d_U, h->d_E, h->d_J);
         if (launch_status(h)) return HPF_E_HIP;
     }
     return HPF_OK;
@@ -1402,7 +1394,7 @@ int launch_jacobian_dense(hpf_handle* h, const int* active) {
 
 // f <- J^{-1} f for every scenario (rocSOLVER LU with partial pivoting)
 int dense_solve(hpf_handle* h, int Nsys) {
-    ScopedTimer t(h, T_SOLVE);
+    ScopedTimer t(h, T_SOLVE, h->stream);
     if (Nsys <= 0) return HPF_OK;
     if (ensure_blas(h)) return HPF_E_ROCSOLVER;
     BLASCHK(rocblas_set_stream(h->blas, h->stream));
@@ -1436,21 +1428,21 @@ int dense_solve(hpf_handle* h, int Nsys) {
 }
 
 template <bool FUND>
-int launch_update(hpf_handle* h, const int* active) {
-    ScopedTimer t(h, T_UPDATE);
+int launch_update(hpf_handle* h, const LaunchCtx& ctx) {
+    ScopedTimer t(h, T_UPDATE, ctx.stream);
     const int count = FUND ? h->n : h->n * h->Hn;
     const int N = FUND ? h->Nf : h->N;
     const int Nc = FUND ? h->n - 1 : h->Nc;
     const bool busx = !FUND && bus_images(h);
     const int bw = tree_bst(h);
     if (!FUND && h->rect_update)
-        hipLaunchKernelGGL(k_update_rect, grid2(count, h->cur_S), dim3(TPB), 0, h->cur_stream, h->n, h->Hn, h->c, count,
-                           h->n * h->Hn, N, Nc, active, h->d_f, h->d_Vm, h->d_Va, h->d_U, h->d_E,
-                           busx ? h->d_x : nullptr, bw, h->cur_s0, div_magic(h->Hn));
+        hipLaunchKernelGGL(k_update_rect, grid2(count, ctx.S), dim3(TPB), 0, ctx.stream, h->n, h->Hn, h->c, count,
+                           h->n * h->Hn, N, Nc, ctx.active, h->d_f, h->d_Vm, h->d_Va, h->d_U, h->d_E,
+                           busx ? h->d_x : nullptr, bw, ctx.s0, div_magic(h->Hn));
     else
-        hipLaunchKernelGGL((k_update<FUND>), grid2(count, h->cur_S), dim3(TPB), 0, h->cur_stream, h->n, h->Hn, h->c, count,
-                           h->n * h->Hn, N, Nc, active, h->d_f, h->d_Vm, h->d_Va, h->d_U, h->d_E,
-                           busx ? h->d_x : nullptr, bw, h->cur_s0, div_magic(h->Hn));
+        hipLaunchKernelGGL((k_update<FUND>), grid2(count, ctx.S), dim3(TPB), 0, ctx.stream, h->n, h->Hn, h->c, count,
+                           h->n * h->Hn, N, Nc, ctx.active, h->d_f, h->d_Vm, h->d_Va, h->d_U, h->d_E,
+                           busx ? h->d_x : nullptr, bw, ctx.s0, div_magic(h->Hn));
     return launch_status(h);
 }
 
@@ -1472,8 +1464,8 @@ static size_t step_residual_lds(const hpf_handle* h) {
 }
 
 // The residual check of the step newton_step just left (in d_x or d_f, as launch_update will read it), before the update moves the state.
-int launch_step_residual(hpf_handle* h, const int* active) {
-    ScopedTimer t(h, T_RESID);
+int launch_step_residual(hpf_handle* h, const LaunchCtx& ctx) {
+    ScopedTimer t(h, T_RESID, ctx.stream);
     const int count = h->n * h->Hn;
     if (count <= 1) return HPF_OK;
     const bool busx = bus_images(h);
@@ -1483,31 +1475,30 @@ int launch_step_residual(hpf_handle* h, const int* active) {
                            : (busx ? &k_step_residual<true, false> : &k_step_residual<false, false>);
     if (lds > 64 * 1024)        // beyond the default dynamic-LDS limit of a kernel (as launch_mismatch)
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(kern, xcd_grid(nbx, h->cur_S), dim3(TPB), lds, h->cur_stream, h->M, count, h->N, h->Nc, active, h->d_U, h->d_E,
-                       h->d_P, h->d_Q, busx ? h->d_x : h->d_f, tree_bst(h), h->d_respart, h->errpart_stride, h->cur_s0, h->cur_S,
+    hipLaunchKernelGGL(kern, xcd_grid(nbx, ctx.S), dim3(TPB), lds, ctx.stream, h->M, count, h->N, h->Nc, ctx.active, h->d_U, h->d_E,
+                       h->d_P, h->d_Q, busx ? h->d_x : h->d_f, tree_bst(h), h->d_respart, h->errpart_stride, ctx.s0, ctx.S,
                        div_magic(h->Hn), lds > 0 ? 1 : 0, h->src_set ? h->d_src : (const cplx*)nullptr);
-    hipLaunchKernelGGL(k_step_eta, dim3((unsigned)h->cur_S), dim3(64), 0, h->cur_stream, h->cur_S, active, h->d_respart, h->errpart_stride,
-                       err_parts<false>(h), h->resid_limit, h->d_eta, h->S_alloc, h->d_pivflag, h->cur_s0);
+    hipLaunchKernelGGL(k_step_eta, dim3((unsigned)ctx.S), dim3(64), 0, ctx.stream, ctx.S, ctx.active, h->d_respart, h->errpart_stride,
+                       err_parts<false>(h), h->resid_limit, h->d_eta, h->S_alloc, h->d_pivflag, ctx.s0);
     return launch_status(h);
 }
 
 // One Newton step: Jacobian at the current state, step = J^{-1} f into d_f.
 template <bool FUND>
-int newton_step(hpf_handle* h, const int* active) {
+int newton_step(hpf_handle* h, const LaunchCtx& ctx) {
     int r;
     if (h->solver == HPF_SOLVER_BLOCK_TREE && h->n_ties == 0)
-        return FUND ? tree_fund_step(h, active != nullptr) : tree_newton_step(h, active != nullptr);
-    if (h->solver == HPF_SOLVER_BLOCK_TREE && !FUND) return tree_newton_step_bordered(h, active != nullptr);
+        return FUND ? tree_fund_step(h, ctx) : tree_newton_step(h, ctx, FACTOR_AND_BACK);
+    if (h->solver == HPF_SOLVER_BLOCK_TREE && !FUND) return tree_newton_step_bordered(h, ctx);
     // (a meshed network on the block-tree path takes its fundamental power flow through the dense LU: Nf = 2n - 1 - c is small)
     const int Nsys = FUND ? h->Nf : h->N;
     if ((r = ensure_dense(h, Nsys))) return r;
-    if ((r = launch_jacobian_dense<FUND>(h, active))) return r;
+    if ((r = launch_jacobian_dense<FUND>(h, ctx))) return r;
     return dense_solve(h, Nsys);
 }
 
-// what one Newton iteration of the current launch context launches besides step, update and mismatch; the defaults: nothing (hpf_iterate)
+// what one Newton iteration of a launch context launches besides step, update and mismatch; the defaults: nothing (hpf_iterate)
 struct IterSpec {
-    const int* active = nullptr;   // slot list, or nullptr: every scenario of the slice
     bool keep_prev = false;        // k_keep_prev before the step (hpf_solve with keep_previous_state)
     bool finalize = false;         // k_finalize behind the mismatch (the device's stop rule; it owns d_active and d_nactive) ...
     double thresh = 0.0;           // ... and its arguments
@@ -1516,19 +1507,19 @@ struct IterSpec {
 };
 
 template <bool FUND>
-int launch_iteration(hpf_handle* h, const IterSpec& it) {
+int launch_iteration(hpf_handle* h, const LaunchCtx& ctx, const IterSpec& it) {
     int r;
     if (it.keep_prev)
-        hipLaunchKernelGGL(k_keep_prev, grid2(h->n * h->Hn, h->cur_S), dim3(TPB), 0, h->cur_stream, h->n * h->Hn, it.active, h->d_Vm, h->d_Va,
-                           h->d_Vmp, h->d_Vap, h->cur_s0);
-    if ((r = newton_step<FUND>(h, it.active))) return r;
-    if (!FUND && h->resid_check && (r = launch_step_residual(h, it.active))) return r;
-    if ((r = launch_update<FUND>(h, it.active))) return r;
-    if ((r = launch_mismatch<FUND>(h, it.active, false))) return r;
+        hipLaunchKernelGGL(k_keep_prev, grid2(h->n * h->Hn, ctx.S), dim3(TPB), 0, ctx.stream, h->n * h->Hn, ctx.active, h->d_Vm, h->d_Va,
+                           h->d_Vmp, h->d_Vap, ctx.s0);
+    if ((r = newton_step<FUND>(h, ctx))) return r;
+    if (!FUND && h->resid_check && (r = launch_step_residual(h, ctx))) return r;
+    if ((r = launch_update<FUND>(h, ctx))) return r;
+    if ((r = launch_mismatch<FUND>(h, ctx, false))) return r;
     if (it.finalize)
-        hipLaunchKernelGGL(k_finalize, dim3((unsigned)h->cur_S), dim3(64), 0, h->cur_stream, h->cur_S, 0, it.thresh, it.max_iter, it.hist_cap,
+        hipLaunchKernelGGL(k_finalize, dim3((unsigned)ctx.S), dim3(64), 0, ctx.stream, ctx.S, 0, it.thresh, it.max_iter, it.hist_cap,
                            it.hist_off, h->d_errpart, h->errpart_stride, err_parts<FUND>(h), h->d_err, h->d_niter, h->d_active, h->d_nactive,
-                           it.hist, h->cur_s0, (const int*)nullptr);
+                           it.hist, ctx.s0, (const int*)nullptr);
     return HPF_OK;
 }
 
@@ -1537,11 +1528,11 @@ enum GroupOrder {
     ITERATION_MAJOR        // all groups' step i before any group's step i + 1: keeps the group pipelines in phase (hpf_iterate)
 };
 
-// `iters` iterations of slots [0, slots) of the active list / of the batch, split over the scenario groups (hpf_groups.hpp), each group on its
+// `iters` iterations of slots [0, slots) of the slot list `active` (nullptr: of the batch), split over the scenario groups (hpf_groups.hpp), each group on its
 // own stream between a fork and a join with the handle's stream.  One group, as the fundamental pass always is, runs on the handle's stream
 // without any event call.  An error ends the launches but not the joins: what was forked is joined, then the first error comes back.
 template <bool FUND>
-int enqueue_iterations(hpf_handle* h, int slots, int iters, const IterSpec& it, GroupOrder order) {
+int enqueue_iterations(hpf_handle* h, int slots, const int* active, int iters, const IterSpec& it, GroupOrder order) {
     const int G = FUND ? 1 : group_count(h->solver == HPF_SOLVER_BLOCK_TREE && h->n_ties == 0, h->n_groups, slots);
     if (G > 1) HIPCHK(hipEventRecord(h->fork_ev, h->stream));
     int rc = HPF_OK;
@@ -1556,8 +1547,7 @@ int enqueue_iterations(hpf_handle* h, int slots, int iters, const IterSpec& it, 
     auto iteration = [&](int g) {
         if (rc != HPF_OK) return;
         const int s0 = group_bound(slots, G, g);
-        set_ctx(h, group_stream(h, g), s0, group_bound(slots, G, g + 1) - s0);
-        rc = launch_iteration<FUND>(h, it);
+        rc = launch_iteration<FUND>(h, LaunchCtx{group_stream(h, g), s0, group_bound(slots, G, g + 1) - s0, active}, it);
     };
     if (order == GROUP_MAJOR) {
         for (int g = 0; g < G; ++g) {
@@ -1572,7 +1562,6 @@ int enqueue_iterations(hpf_handle* h, int slots, int iters, const IterSpec& it, 
         for (int g = 0; g < G; ++g) join(g);
     }
     for (int g = 0; G > 1 && g < G; ++g) ev(hipStreamWaitEvent(h->stream, h->join_ev[g], 0));
-    full_ctx(h);
     return rc;
 }
 
@@ -1645,7 +1634,7 @@ int nr_pass(hpf_handle* h, double thresh, int max_iter, const int* mask) {
     const int hist_off = FUND ? 1 : 0;                // pf records only post-update errors (HG:264)
     if ((r = launch_polar<FUND>(h))) return r;
     if (mask) hipLaunchKernelGGL(k_mask_to_list, dim3((S + 63) / 64), dim3(64), 0, h->stream, S, mask, h->d_active);
-    if ((r = launch_mismatch<FUND>(h, mask ? h->d_active : nullptr, false))) return r;
+    if ((r = launch_mismatch<FUND>(h, batch_ctx(h, mask ? h->d_active : nullptr), false))) return r;
     HIPCHK(hipMemsetAsync(h->d_nactive, 0, sizeof(int), h->stream));
     hipLaunchKernelGGL(k_finalize, dim3((unsigned)S), dim3(64), 0, h->stream, S, 1, thresh, max_iter, h->hist_cap,
                        hist_off, h->d_errpart, h->errpart_stride, err_parts<FUND>(h), h->d_err, h->d_niter, h->d_active, h->d_nactive, h->d_hist, 0, mask);
@@ -1657,7 +1646,7 @@ int nr_pass(hpf_handle* h, double thresh, int max_iter, const int* mask) {
     // c - 1 while chunk c is already queued (pinned double buffer + events), so the device never drains between chunks.
     const bool pipelined = !FUND && h->solver == HPF_SOLVER_BLOCK_TREE && !trace && h->n_ties == 0;
     const int chunk = pipelined ? (S >= 8 ? 4 : 2) : 1;
-    const IterSpec spec = {h->d_active, !FUND && h->keep_prev && h->d_Vmp, true, thresh, max_iter, h->hist_cap, hist_off, h->d_hist};
+    const IterSpec spec = {!FUND && h->keep_prev && h->d_Vmp, true, thresh, max_iter, h->hist_cap, hist_off, h->d_hist};
     if (pipelined) {
         if ((r = ensure_poll_buffers(h))) return r;
         // Between two chunks the slot list is compacted on the device (running scenarios first) and their count goes to the
@@ -1683,7 +1672,7 @@ int nr_pass(hpf_handle* h, double thresh, int max_iter, const int* mask) {
             }
             const int todo = (max_iter - it) < ch ? (max_iter - it) : ch;
             if (todo > 0) {
-                if ((r = enqueue_iterations<FUND>(h, n_ub, todo, spec, GROUP_MAJOR))) return r;
+                if ((r = enqueue_iterations<FUND>(h, n_ub, h->d_active, todo, spec, GROUP_MAJOR))) return r;
                 if ((r = compact_and_post((c + 1) & 1))) return r;
                 it += todo;
             }
@@ -1713,7 +1702,7 @@ int nr_pass(hpf_handle* h, double thresh, int max_iter, const int* mask) {
     while (nactive > 0 && it < max_iter) {
         was = act;                        // (no compaction on this path: slot i runs scenario i)
         h->host_act = act;                // (the bordered step of a meshed network walks the running scenarios on the host)
-        if ((r = enqueue_iterations<FUND>(h, S, 1, spec, GROUP_MAJOR))) return r;
+        if ((r = enqueue_iterations<FUND>(h, S, h->d_active, 1, spec, GROUP_MAJOR))) return r;
         HIPCHK(hipMemcpyAsync(act.data(), h->d_active, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         nactive = count_active(act.data());
@@ -2133,7 +2122,6 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
     const size_t q_lds = sizeof(int) * 2 * (size_t)S_max;
     // one round between two chunks: compact -> harvest / refill -> initial mismatch of the new scenarios -> counters to the host
     auto round = [&](int buf) -> int {
-        full_ctx(h);
         hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, h->stream, S_max, h->d_active, h->d_nactive);
         hipLaunchKernelGGL(k_queue_refill, dim3(1), dim3(1024), q_lds, h->stream, S_max, n_total, h->d_active, h->d_nactive, slot_scen, next,
                            hlist, hg, newlist, base);
@@ -2155,23 +2143,20 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
                 hipLaunchKernelGGL(k_source_expand, grid2(nnl * Hn, S_max), dim3(TPB), 0, h->stream, nnl, Hn, h->m, newlist, slot_scen, 0,
                                    (const double*)h->d_qsrc, h->d_qorders, h->d_dev, h->d_IN, h->d_src);
         }
-        set_ctx(h, h->stream, 0, S_max);
-        int rr = launch_mismatch<false>(h, newlist, false);
-        full_ctx(h);
-        if (rr) return rr;
+        if (int rr = launch_mismatch<false>(h, LaunchCtx{h->stream, 0, S_max, newlist}, false)) return rr;   // (every storage: the list names the new ones)
         hipLaunchKernelGGL(k_queue_first, dim3((unsigned)S_max), dim3(64), 0, h->stream, S_max, thresh, max_iter, newlist, base,
                            h->d_errpart, h->errpart_stride, err_parts<false>(h), h->d_err, h->d_active);
         if (launch_status(h)) return HPF_E_HIP;
         return poll_post(h, buf, {h->d_nactive, next});
     };
-    const IterSpec spec = {h->d_active, false, true, thresh, max_iter};       // (no error history, no previous state: nothing could read either after a sweep)
+    const IterSpec spec = {false, true, thresh, max_iter};       // (no error history, no previous state: nothing could read either after a sweep)
     const int chunk = h->queue_chunk > 0 ? h->queue_chunk : 4;
     int c = 0, n_ub = S_used;
     if ((r = round(0))) return cleanup(r);
     const long long max_rounds = ((long long)(n_total + S_used - 1) / S_used + 2) * ((max_iter + chunk - 1) / chunk + 2) + 8;
     for (long long rd = 0; rd < max_rounds; ++rd) {
         // queue the next chunk BEFORE looking at what the previous round left (the device never drains between chunks)
-        if (n_ub > 0 && (r = enqueue_iterations<false>(h, n_ub, chunk, spec, GROUP_MAJOR))) return cleanup(r);
+        if (n_ub > 0 && (r = enqueue_iterations<false>(h, n_ub, h->d_active, chunk, spec, GROUP_MAJOR))) return cleanup(r);
         if ((r = round((c + 1) & 1))) return cleanup(r);
         const int* left = poll_wait(h, c & 1);
         if (!left) return cleanup(HPF_E_HIP);
@@ -2296,7 +2281,6 @@ int hpf_create_opts(hpf_handle** out, const hpf_desc* d, const char* options) {
         if (hipEventCreateWithFlags(&h->join_ev[g], hipEventDisableTiming) != hipSuccess) return fail(HPF_E_HIP);
     }
     if (hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming) != hipSuccess) return fail(HPF_E_HIP);
-    set_ctx(h, h->stream, 0, 0);
     // (the rocBLAS handle is created on first use, ensure_blas: the radial block-tree path never needs it and its creation costs
     //  more than the whole set-up of a 10 000-bus model)
     h->S_alloc = h->S_max;
@@ -2615,7 +2599,7 @@ static int mismatch_impl(hpf_handle* h, bool fund, double* f, double* err) {
     if (!h->loads_set || !h->state_set || h->S < 1) return HPF_E_STATE;
     int r;
     if ((r = fund ? launch_polar<true>(h) : launch_polar<false>(h))) return r;
-    if ((r = fund ? launch_mismatch<true>(h, nullptr) : launch_mismatch<false>(h, nullptr))) return r;
+    if ((r = fund ? launch_mismatch<true>(h, batch_ctx(h)) : launch_mismatch<false>(h, batch_ctx(h)))) return r;
     hipLaunchKernelGGL(k_err_reduce, dim3((unsigned)h->S), dim3(64), 0, h->stream, h->d_errpart, h->errpart_stride,
                        fund ? err_parts<true>(h) : err_parts<false>(h), h->d_errbits);
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -2636,7 +2620,7 @@ static int jacobian_impl(hpf_handle* h, bool fund, int scen, double* J) {
     const int Nsys = fund ? h->Nf : h->N;
     if ((r = ensure_dense(h, Nsys))) return r;
     if ((r = fund ? launch_polar<true>(h) : launch_polar<false>(h))) return r;
-    if ((r = fund ? launch_jacobian_dense<true>(h, nullptr) : launch_jacobian_dense<false>(h, nullptr))) return r;
+    if ((r = fund ? launch_jacobian_dense<true>(h, batch_ctx(h)) : launch_jacobian_dense<false>(h, batch_ctx(h)))) return r;
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(J, h->d_J + (size_t)scen * h->J_elems_per_scen, sizeof(double) * (size_t)Nsys * Nsys,
                      hipMemcpyDeviceToHost));
@@ -2811,7 +2795,7 @@ int hpf_iterate(hpf_handle* h, int iters) {
     h->solve_done = false;
     // (replaying a captured hipGraph of several iterations was measured again in round 2, with 3 / 4 / 6 / 8 scenario groups at
     //  128 and 1 024 scenarios: 0..-6 % -- the step is not bound by the host's launch rate)
-    return enqueue_iterations<false>(h, h->S, iters, IterSpec{}, ITERATION_MAJOR);       // (every scenario, unconditionally: no stop rule)
+    return enqueue_iterations<false>(h, h->S, nullptr, iters, IterSpec{}, ITERATION_MAJOR);       // (every scenario, unconditionally: no stop rule)
 }
 
 int hpf_get_stats(hpf_handle* h, hpf_stat* stats) {
@@ -3161,7 +3145,6 @@ int hpf_set_stream(hpf_handle* h, void* s) {
     if (!h) return HPF_E_ARG;
     HIPCHK(hipStreamSynchronize(h->stream));
     h->stream = s ? (hipStream_t)s : h->own_stream;
-    full_ctx(h);
     return HPF_OK;
 }
 
@@ -3312,8 +3295,20 @@ int hpf_tree_census(const hpf_handle* h, int* counts, int n_counts) {
     if (!h || !counts || n_counts < 0) return HPF_E_ARG;
     if (h->solver != HPF_SOLVER_BLOCK_TREE) return HPF_E_STATE;
     const Tree& T = active_tree(const_cast<hpf_handle*>(h));
-    const int fused = tree_levels_fused(const_cast<hpf_handle*>(h)) ? 1 : 0;
-    for (int i = 0; i < n_counts; ++i) counts[i] = i < 8 ? T.census[i] : (i == 8 ? h->n_ties : (i == 9 ? fused : (i == 10 ? T.n_comp : (i == 11 ? h->border_repivots : (i == 12 ? h->m_border : (i == 13 ? (h->mesh_sel ? h->sel_nP : 0) : (i == 14 ? (h->mesh_sel ? (h->border_gj ? 2 : 1) : 0) : (i == 15 ? (int)h->n_back_walks : (i == 16 ? (int)h->n_back_tails : (i == 17 ? h->last_batch_tile : (i == 18 ? h->last_leaf_tile : 0)))))))))));
+    int w[CENSUS_WORDS] = {};
+    for (int i = 0; i < 8; ++i) w[i] = T.census[i];
+    w[CENSUS_TIES] = h->n_ties;
+    w[CENSUS_FUSED_LEVELS] = tree_levels_fused(const_cast<hpf_handle*>(h)) ? 1 : 0;
+    w[CENSUS_COMPRESS_STEPS] = T.n_comp;
+    w[CENSUS_BORDER_REPIVOTS] = h->border_repivots;
+    w[CENSUS_BORDER_UNKNOWNS] = h->m_border;
+    w[CENSUS_ROOT_PATH_BUSES] = h->mesh_sel ? h->sel_nP : 0;
+    w[CENSUS_BORDERED_FORM] = h->mesh_sel ? (h->border_gj ? 2 : 1) : 0;
+    w[CENSUS_BACK_WALKS] = (int)h->n_back_walks;
+    w[CENSUS_BACK_TAILS] = (int)h->n_back_tails;
+    w[CENSUS_BATCH_TILE] = h->last_batch_tile;
+    w[CENSUS_LEAF_BATCH_TILE] = h->last_leaf_tile;
+    for (int i = 0; i < n_counts; ++i) counts[i] = i < CENSUS_WORDS ? w[i] : 0;
     return HPF_OK;
 }
 

@@ -1661,32 +1661,32 @@ __global__ __launch_bounds__(64 * ((B + 16) / 16)) void k_back_q(
 }
 
 template <int B, bool LEAF>
-int launch_factor_q2(hpf_handle* h, const TreeDev& T, const int* nodes, int count, const int* active) {
-    ScopedTimer t(h, LEAF ? T_SOLVE : T_GJ);            // T_GJ: the general kernel k_factor_q<B, false> alone (roofline numerator: hpf_kernel_model)
+int launch_factor_q2(hpf_handle* h, const LaunchCtx& ctx, const TreeDev& T, const int* nodes, int count) {
+    ScopedTimer t(h, LEAF ? T_SOLVE : T_GJ, ctx.stream);            // T_GJ: the general kernel k_factor_q<B, false> alone (roofline numerator: hpf_kernel_model)
     unsigned long long* ts = nullptr;                   // device-clock stamps of this launch (timing leg, general kernel only)
     if (!LEAF && h->timing && h->d_tstamp && h->ts_next < hpf_handle::TS_CAP) ts = h->d_tstamp + 2 * (size_t)(h->ts_next++);
     constexpr int NT = (B + 16) / 16;
-    dim3 grid((unsigned)count, (unsigned)h->cur_S);
+    dim3 grid((unsigned)count, (unsigned)ctx.S);
 #if HPF_LEAF_XCD
-    if (LEAF) grid = dim3((unsigned)(((count + 7) / 8) * 8) * (unsigned)h->cur_S, 1, 1);        // (leaf-major id decode in the kernel)
+    if (LEAF) grid = dim3((unsigned)(((count + 7) / 8) * 8) * (unsigned)ctx.S, 1, 1);        // (leaf-major id decode in the kernel)
 #endif
-    hipLaunchKernelGGL((k_factor_q<B, LEAF>), grid, dim3(64 * NT), 0, h->cur_stream, h->M, T, nodes,
-                       2 * h->Hn, h->N, h->Nc, active, h->d_U, h->d_E, h->d_fb, h->d_Z, h->d_w, h->d_linA, h->d_C, h->d_H,
-                       h->d_I0, h->d_chG, h->d_chH, h->d_chD, h->d_chy, active_tree(h).d_Minv, h->d_lfK, h->d_lfS, h->d_dbg, h->sw.debug_ablate, h->cur_s0,
-                       h->d_pivflag, h->piv_limit, ts, count, (unsigned)h->cur_S);
+    hipLaunchKernelGGL((k_factor_q<B, LEAF>), grid, dim3(64 * NT), 0, ctx.stream, h->M, T, nodes,
+                       2 * h->Hn, h->N, h->Nc, ctx.active, h->d_U, h->d_E, h->d_fb, h->d_Z, h->d_w, h->d_linA, h->d_C, h->d_H,
+                       h->d_I0, h->d_chG, h->d_chH, h->d_chD, h->d_chy, active_tree(h).d_Minv, h->d_lfK, h->d_lfS, h->d_dbg, h->sw.debug_ablate, ctx.s0,
+                       h->d_pivflag, h->piv_limit, ts, count, (unsigned)ctx.S);
     return launch_status(h);
 }
 
 template <int B>
-int launch_factor_q(hpf_handle* h, const TreeDev& T, const int* nodes, int count, const int* active, bool all_leaves) {
-    return all_leaves ? launch_factor_q2<B, true>(h, T, nodes, count, active) : launch_factor_q2<B, false>(h, T, nodes, count, active);
+int launch_factor_q(hpf_handle* h, const LaunchCtx& ctx, const TreeDev& T, const int* nodes, int count, bool all_leaves) {
+    return all_leaves ? launch_factor_q2<B, true>(h, ctx, T, nodes, count) : launch_factor_q2<B, false>(h, ctx, T, nodes, count);
 }
 
 template <int B>
-int launch_back_q(hpf_handle* h, const TreeDev& T, const int* nodes, int count, const int* active) {
+int launch_back_q(hpf_handle* h, const LaunchCtx& ctx, const TreeDev& T, const int* nodes, int count) {
     constexpr int NT = (B + 16) / 16;
-    hipLaunchKernelGGL((k_back_q<B>), dim3((unsigned)count, (unsigned)h->cur_S), dim3(64 * NT), 0, h->cur_stream, h->M, T, nodes,
-                       2 * h->Hn, h->N, h->Nc, active, h->d_Z, h->d_w, h->d_x, (double*)nullptr, h->d_H, active_tree(h).d_Minv, h->d_lfK,
-                       h->d_lfS, h->cur_s0);
+    hipLaunchKernelGGL((k_back_q<B>), dim3((unsigned)count, (unsigned)ctx.S), dim3(64 * NT), 0, ctx.stream, h->M, T, nodes,
+                       2 * h->Hn, h->N, h->Nc, ctx.active, h->d_Z, h->d_w, h->d_x, (double*)nullptr, h->d_H, active_tree(h).d_Minv, h->d_lfK,
+                       h->d_lfS, ctx.s0);
     return launch_status(h);
 }

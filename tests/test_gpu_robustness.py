@@ -687,6 +687,51 @@ def test_meshed_batches_of_scenarios_equal_one_scenario_at_a_time(tmp_path):
     assert (errr <= 1e-4).all() and np.abs(Ub - Ur).max() < TOL_V
 
 
+def test_virtual_sweep_groups_leave_the_callers_slice_alone(tmp_path):
+    """The virtual-sweep bordered step (HPF_MESH_SEL=0) is the one place where a nested sweep launches on slices of its own -- one launch context per
+    virtual group -- inside its caller's slice of real scenarios.  64 buses, harmonics 1 .. 11 (blocks of 12 rows), 6 loop-closing lines with 12
+    distinct endpoint buses: 1 + m = 145 virtual scenarios, so with HPF_GROUPS=4 every sweep of the border columns runs as four groups on four streams,
+    with HPF_GROUPS=1 as one.  Two real scenarios with different loads, three iterations: the second scenario runs behind the first one's virtual
+    sweeps, so a slice that is not what the caller passed shows up as a difference between the two runs, or as an untouched state.  Bit for bit."""
+    hp = _hp()
+    from harmonic_power_flow_amd import api, synth
+    n, hmax, k, S = 64, 11, 6, 2
+    fb, fl = synth.gen(n, seed=0, outdir=str(tmp_path))
+    synth.add_ties(fl, n, k)                                  # (the host planner says 12 endpoint buses for this feeder and these lines)
+    st = hp.Settings(H_MAX=hmax)
+    buses, lines, m, nn, c = hp.init_network(fb, fl, settings=st)
+    Y = hp.build_admittance_matrices(buses, lines, st.HARMONICS)
+    NE = hp.import_Norton_Equivalents(buses, True, st, INPUTS)
+    P0, Q0 = buses["P"].to_numpy(float), buses["Q"].to_numpy(float)
+    scale = np.stack([np.ones(n), synth.scenario_scale(n, 1)])
+    seed = None
+    out = {}
+    for groups in (1, 4):
+        dm = api._device_model(buses, Y, NE, True, st.HARMONICS, solver="block_tree", max_scenarios=S, options="HPF_MESH_SEL=0 HPF_GROUPS=%d" % groups)
+        try:
+            dm.set_loads(P0 * scale, Q0 * scale)
+            dm.set_state(None, None, n_scen=S)
+            dm.fund_pf(1e-6, 30)
+            if seed is None:
+                seed = dm.get_state()
+            dm.set_state(*seed)                               # (the same fundamental seed for both runs)
+            dm.mismatch(want_f=False)
+            dm.iterate(3)
+            dm.sync()
+            out[groups] = (dm.get_state(), dm.tree_census())
+        finally:
+            dm.close()
+    (Vm1, Va1), cs1 = out[1]
+    (Vm4, Va4), cs4 = out[4]
+    print("\nvirtual sweeps of %d + 1 right-hand sides, one group | four: max |dVm| %.1e, max |dVa| %.1e; scenario 0 vs 1: %.1e"
+          % (cs4["border_unknowns"], np.abs(Vm1 - Vm4).max(), np.abs(Va1 - Va4).max(), np.abs(Vm4[0] - Vm4[1]).max()))
+    for cs in (cs1, cs4):
+        assert cs["ties"] == k and cs["bordered_form"] == 0 and cs["border_unknowns"] + 1 >= 128      # (the four-way split really ran)
+    assert not np.array_equal(Vm4[0], Vm4[1]) and not np.array_equal(Va4[0], Va4[1])                  # (the second scenario is no copy of the first)
+    assert not np.array_equal(Vm4, seed[0])                                                           # (and the steps moved the state)
+    assert np.array_equal(Vm1, Vm4) and np.array_equal(Va1, Va4)
+
+
 def test_many_scenarios_compaction_over_several_tiles(tmp_path):
     """1 500 scenarios of a small feeder in one handle: the slot-list compaction works in tiles of 1 024 slots, the scenario
     groups split the compacted list -- every record equals the single-scenario solve of that scenario."""

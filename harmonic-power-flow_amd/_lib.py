@@ -27,6 +27,11 @@ class hpf_stat(C.Structure):
     _fields_ = [("n_iter", C.c_int32), ("flags", C.c_int32), ("err", C.c_double), ("thd_max", C.c_double)]
 
 
+class hpf_zscan_net(C.Structure):
+    _fields_ = [("n", C.c_int32), ("nb", C.c_int32), ("from_", c_int_p), ("to", c_int_p), ("R", c_dbl_p), ("X", c_dbl_p),
+                ("gsh", c_dbl_p), ("bsh", c_dbl_p), ("xsh", c_dbl_p)]
+
+
 # every symbol declared in include/hpf.h: name -> (restype, argtypes)
 _H = C.c_void_p
 SYMBOLS = {
@@ -97,6 +102,8 @@ SYMBOLS = {
     "hpf_timing_reset": (C.c_int, [_H]),
     "hpf_dense_solve": (C.c_int, [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
     "hpf_sparse_solve": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]),
+    "hpf_impedance_scan": (C.c_int, [C.c_int, C.POINTER(hpf_zscan_net), C.c_int, c_dbl_p, c_dbl_p, C.c_int, c_int_p, C.c_int, c_dbl_p, c_dbl_p,
+                                     c_dbl_p, c_int_p]),
     "hpf_solve_flops": (C.c_double, [_H]),
     "hpf_solve_bytes": (C.c_double, [_H]),
     "hpf_back_bytes": (C.c_double, [_H]),

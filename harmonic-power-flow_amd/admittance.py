@@ -110,6 +110,34 @@ def build_admittance_csr(buses, lines, harmonics):
     return pat.rowptr, pat.col, Yval
 
 
+def line_model(buses, lines):
+    """The network in the form the impedance scan consumes (hpf_impedance_scan), resolved as `build_admittance_csr` resolves it -> dict:
+    n, nb; fr, to [nb] int32 (0-based, fr < to): one branch per stored upper-triangle pair, in the numbering of hpf_get_branches; R, X [nb] of
+    the line that OWNS the cell (a later parallel line overwrites an earlier one); xsh [n] = X_sh; gsh, bsh [n] = the sums of G / 2, B / 2 over
+    the lines the reference's off-by-one rule assigns to the bus (a 1-based ID compared with a 0-based index: bus 0 never receives any).  For a
+    real h > 0:  y_e = 1 / (R_e + j h X_e),  Y_ij = -y_e,
+    Y_ii = sum_{e at i} y_e + (gsh_i + j h bsh_i) + [xsh_i != 0 and h != 1] / (j xsh_i h)  -- the reference's matrix (HG:147-170) at every h; its
+    last bits are not the reference's (the summation order differs)."""
+    n = len(buses)
+    fid = lines.fromID.to_numpy(dtype=np.int64)
+    tid = lines.toID.to_numpy(dtype=np.int64)
+    pat = AdmittancePattern(n, fid, tid)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(pat.rowptr))
+    up = pat.col > rows
+    own = pat.line[up]
+    G = lines.G.to_numpy(dtype=float)
+    B = lines.B.to_numpy(dtype=float)
+    gsh, bsh = np.zeros(n), np.zeros(n)
+    for k in range(len(fid)):                                # HG:163-168, the visiting order of build_admittance_csr
+        for n0 in sorted({int(fid[k]), int(tid[k])}):
+            if 0 <= n0 < n:
+                gsh[n0] += G[k] / 2
+                bsh[n0] += B[k] / 2
+    return dict(n=n, nb=int(up.sum()), fr=rows[up].astype(np.int32), to=pat.col[up].astype(np.int32),
+                R=lines.R.to_numpy(dtype=float)[own], X=lines.X.to_numpy(dtype=float)[own], gsh=gsh, bsh=bsh,
+                xsh=buses["X_sh"].to_numpy(dtype=float).copy())
+
+
 def to_dense_frame(rowptr, col, Yval, harmonics, n):
     """The reference's `Y_all` object (HG:139-143,170): DataFrame (Hn*n) x n, MultiIndex (harmonic, bus)."""
     Hn = len(harmonics)

@@ -576,6 +576,108 @@ def waveforms(V, buses, harmonics=None, samples=1024, at=None):
     return table, v
 
 
+class ImpedanceScan:
+    """Result of `impedance_scan`: h [F] the grid; Z [F][n] complex driving-point impedances (None with full=False); Zt [F][len(transfer)][n] the
+    transfer columns Z_ij of the buses in `transfer`; peak [n] = max over the grid of |Z_ii|, peak_h [n] the harmonic order of that peak
+    (peak_index [n] its grid index)."""
+
+    def __init__(self, h, Z, Zt, peak, peak_index, bus_ids, transfer):
+        self.h, self.Z, self.Zt, self.peak, self.peak_index = h, Z, Zt, peak, peak_index
+        self.peak_h = h[peak_index]
+        self.bus_ids, self.transfer = bus_ids, transfer
+
+    def _pos(self, bus):
+        return self.bus_ids.index(int(bus))
+
+    def resonances(self, bus, prominence=0.0):
+        """Parallel resonances seen from `bus` (1-based ID): the strict local maxima of |Z_ii| along the grid, on the host from Z -> DataFrame
+        (index = grid index; h, z_abs, prominence).  The prominence of a maximum is (peak - base) / peak, base = the larger of the two minima
+        of |Z| between the maximum and the nearest higher grid point on either side (or the end of the grid); maxima below `prominence`
+        are left out."""
+        if self.Z is None:
+            raise ValueError("resonances needs the full scan (full=True)")
+        a = np.abs(self.Z[:, self._pos(bus)])
+        rows = []
+        for f in range(1, len(a) - 1):
+            if not (a[f] > a[f - 1] and a[f] > a[f + 1]):
+                continue
+            base = 0.0
+            for side in (a[:f][::-1], a[f + 1:]):
+                higher = np.nonzero(side > a[f])[0]
+                base = max(base, float(side[:higher[0]].min() if len(higher) else side.min()))
+            prom = (a[f] - base) / a[f]
+            if prom >= prominence:
+                rows.append((f, self.h[f], a[f], prom))
+        return pd.DataFrame([r[1:] for r in rows], index=pd.Index([r[0] for r in rows], name="index"), columns=["h", "z_abs", "prominence"])
+
+
+def impedance_scan_arrays(model, h, y_extra=None, sel=(), chunk=0, full=True, device=0):
+    """hpf_impedance_scan on the arrays of `admittance.line_model`: h [F] real orders, y_extra [F][n] complex or None, sel 0-based bus indices
+    -> (code, Z or None, Zt, zpeak, fpeak); code 0 or 3 (HPF_E_SINGULAR: the outputs are written), any other code raises."""
+    lib = _lib.load()
+    n, F = int(model["n"]), len(h)
+    h = np.ascontiguousarray(h, dtype=np.float64)
+    sel = np.ascontiguousarray(sel, dtype=np.int32)
+    arr = {k: np.ascontiguousarray(model[k], dtype=np.int32 if k in ("fr", "to") else np.float64) for k in ("fr", "to", "R", "X", "gsh", "bsh", "xsh")}
+    ip, dp = _lib.c_int_p, _lib.c_dbl_p
+    net = _lib.hpf_zscan_net(n, int(model["nb"]), arr["fr"].ctypes.data_as(ip), arr["to"].ctypes.data_as(ip),
+                             *[arr[k].ctypes.data_as(dp) for k in ("R", "X", "gsh", "bsh", "xsh")])
+    yx = None if y_extra is None else np.ascontiguousarray(y_extra, dtype=np.complex128)
+    if yx is not None and yx.shape != (F, n):
+        raise ValueError("y_extra must be [F][n]")
+    Z = np.empty((F, n), dtype=np.complex128) if full else None
+    Zt = np.empty((F, len(sel), n), dtype=np.complex128)
+    zpeak, fpeak = np.empty(n), np.empty(n, dtype=np.int32)
+    rc = lib.hpf_impedance_scan(int(device), C.byref(net), F, h.ctypes.data_as(dp), None if yx is None else yx.ctypes.data_as(dp), len(sel),
+                                sel.ctypes.data_as(ip), int(chunk), None if Z is None else Z.ctypes.data_as(dp),
+                                Zt.ctypes.data_as(dp) if len(sel) else None, zpeak.ctypes.data_as(dp), fpeak.ctypes.data_as(ip))
+    if rc not in (0, 3):
+        raise _lib.HpfError(rc, 0, "hpf_impedance_scan")
+    return rc, Z, Zt, zpeak, fpeak
+
+
+def impedance_scan(buses, lines, h, shunts=None, capacitors=None, transfer=None, full=True, device=0, settings=None, ne_dir=None, coupled=True):
+    """Frequency scan of the network on the GPU (not in the reference): the driving-point impedance Z_ii(h) of every bus, and the transfer
+    impedances Z_ij(h) to the buses in `transfer`, over the grid `h` of real harmonic orders > 0 -> ImpedanceScan.  The network is
+    `admittance.line_model(buses, lines)`: the reference's admittance matrix (HG:147-170) at every h, never formed.
+    capacitors={bus ID: b} adds the admittance j h b at that bus (b in p.u. at the fundamental); shunts: an [F][n] complex array of shunt
+    admittances added as given, or "norton": every grid point must be one of settings.HARMONICS, and the (q, q) entry of the Norton admittance
+    Y_N (uncoupled: entry q) of its device is added at every nonlinear bus (settings, ne_dir, coupled: as for hpf) -- ValueError otherwise.
+    Bus arguments are the reference's 1-based IDs, as in line_flows.  A grid point at which some Z_ii is not finite (a network without any
+    shunt at h = 1) leaves inf / NaN in the result."""
+    model = admittance.line_model(buses, lines)
+    n = model["n"]
+    h = np.ascontiguousarray(h, dtype=np.float64).reshape(-1)
+    F = len(h)
+    ids = [int(b) for b in buses["ID"]] if "ID" in buses else list(range(1, n + 1))
+    yx = None
+    if isinstance(shunts, str):
+        if shunts != "norton":
+            raise ValueError("shunts must be an [F][n] array or \"norton\"")
+        st = settings or globals()["settings"]
+        harmonics = list(st.HARMONICS)
+        if any(x not in harmonics for x in h):
+            raise ValueError("shunts=\"norton\" needs every grid point in settings.HARMONICS")
+        q = np.array([harmonics.index(x) for x in h])
+        NE = import_Norton_Equivalents(buses, coupled, st, ne_dir)
+        dev, Y_N, _, _ = ingest.norton_arrays(buses, NE, coupled, len(harmonics))
+        yx = np.zeros((F, n), dtype=np.complex128)
+        for i in np.nonzero(dev >= 0)[0]:
+            yx[:, i] = Y_N[dev[i], q, q] if coupled else Y_N[dev[i], q]
+    elif shunts is not None:
+        yx = np.array(shunts, dtype=np.complex128)
+        if yx.shape != (F, n):
+            raise ValueError("shunts must be [F][n] = [%d][%d]" % (F, n))
+    if capacitors:
+        yx = np.zeros((F, n), dtype=np.complex128) if yx is None else yx
+        for bus, b in capacitors.items():
+            yx[:, ids.index(int(bus))] += 1j * h * float(b)
+    transfer = [int(b) for b in (transfer or [])]
+    sel = [ids.index(b) for b in transfer]
+    _, Z, Zt, zpeak, fpeak = impedance_scan_arrays(model, h, yx, sel, 0, full, device)
+    return ImpedanceScan(h, Z, Zt, zpeak, fpeak, ids, transfer)
+
+
 def solve(filename_buses, filename_lines, coupled=True, settings=None, ne_dir=None, solver="auto", verbose=False, extra_iters=0,
           check_steps=False, line_flows=False, update="polar", sources=None, waveforms=False):
     """Convenience wrapper (= init_network + hpf + get_THD) -> dict(V, err_h, n_iter_h, THD, details).  check_steps, update, sources: see hpf.

@@ -5,7 +5,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["hpf_lib.hip", "hpf_block.hip", "hpf_csr_solve.hip"]
+SOURCES = ["hpf_lib.hip", "hpf_block.hip", "hpf_csr_solve.hip", "hpf_zscan.hip"]
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(HERE, "..", "include", "hpf.h")]   # (every header: an edit rebuilds)
 OUT = os.path.join(HERE, "libhpf.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")

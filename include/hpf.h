@@ -348,6 +348,42 @@ int  hpf_waveform_stats_get(hpf_handle* h, int64_t* counts, double* peak_max, in
                             uint32_t* crest_over);
 int  hpf_waveform_stats_end(hpf_handle* h);
 
+/* Impedance scan: the driving-point impedances Z_ii(h) = (Y(h)^-1)_ii of every bus, and the transfer columns Z_ij(h) of selected buses j, over a
+ * grid of F REAL harmonic orders h > 0 -- where the network resonates.  The reference has no counterpart.  Stateless like hpf_sparse_solve: no
+ * handle; the Newton path is not involved.  No matrix is stored: the network is a BFS spanning tree from bus 0 (neighbours in ascending branch
+ * index) plus at most HPF_ZSCAN_MAX_TIES loop-closing branches ("ties"), and per frequency point one upward and one downward walk of the tree in
+ * complex scalars give the diagonal of the tree's inverse, a walk from bus j its column j, and the ties enter as a rank-k correction
+ * (csrc/hpf_zscan.hpp states every recurrence with its association).
+ *   net:     n buses, nb branches (from[e] < to[e], 0-based, every pair once: the numbering of hpf_get_branches), series R, X per branch; per bus
+ *            gsh, bsh (line-charging halves) and xsh (bus shunt reactance, 0: none)
+ *   y_e(h) = 1 / (R_e + j h X_e);  Y_ij = -y_e;
+ *   Y_ii   = sum_{e at i} y_e + (gsh_i + j h bsh_i) + [xsh_i != 0 and h != 1] 1 / (j xsh_i h) + y_extra[f][i]
+ *            -- the matrix of build_admittance_matrices (HG:147-170) at every real h, its h != 1 rule included
+ *   y_extra: [F][n] complex (interleaved re, im) or NULL: caller-supplied shunt admittances per frequency point and bus
+ *   sel:     [n_sel] bus indices, 0 <= n_sel <= HPF_ZSCAN_MAX_SEL, whose columns go to Zt [F][n_sel][n] complex (Zt NULL iff n_sel = 0)
+ *   Z:       [F][n] complex, may be NULL (peaks only)
+ *   zpeak:   [n] max_f |Z_ii|, |z| = sqrt(re^2 + im^2); fpeak [n] int32 its grid index, ties to the smallest f; a NaN is the peak.  Either may be NULL.
+ *   chunk:   the grid is processed in chunks of frequency points so that the device scratch stays under 256 MiB (0: automatic, a multiple of 64);
+ *            chunk > 0 forces the length.  Every output is bit-identical for every chunk length.
+ * One thread per (bus of the current tree depth, frequency point), the frequency fastest; all device arrays are [bus][chunk], so a wavefront
+ * reads and writes 64 consecutive complex values; one launch per depth and walk; no atomics.  All device memory is per-call workspace and is
+ * released on every return path (hpf_debug_device_memory reads the same before and after).
+ * HPF_E_ARG, checked on the host before any HIP call: NULL net or h; n < 1, n > 2^22, nb < 0, F < 1, F > 2^20; a NULL model array; from >= to, an
+ * end bus outside 0 .. n-1, a duplicate pair; R = X = 0 on a branch; any non-finite input; h <= 0; n_sel outside 0 .. 64, a sel entry outside
+ * 0 .. n-1, Zt NULL with n_sel > 0; chunk < 0, or a forced chunk with n ceil(chunk / 256) > 2^30.  HPF_E_TOPOLOGY (host, too): not connected
+ * from bus 0, or more than HPF_ZSCAN_MAX_TIES ties.  HPF_E_SINGULAR, with the outputs still written, when any Z_ii is not finite (a floating
+ * network at h = 1, an exact resonance). */
+#define HPF_ZSCAN_MAX_TIES 8
+#define HPF_ZSCAN_MAX_SEL 64
+typedef struct hpf_zscan_net {
+    int32_t n, nb;
+    const int32_t *from, *to;        /* [nb] */
+    const double *R, *X;             /* [nb] */
+    const double *gsh, *bsh, *xsh;   /* [n] */
+} hpf_zscan_net;
+int  hpf_impedance_scan(int device, const hpf_zscan_net* net, int F, const double* h, const double* y_extra, int n_sel, const int32_t* sel,
+                        int chunk, double* Z, double* Zt, double* zpeak, int32_t* fpeak);
+
 /* Start state: warm-start the scenarios of a sweep from one solved case instead of the reference's flat start (HG:174-184) + pf (HG:244-275).  The
  * reference has no counterpart (hpf() always starts flat, HG:511-529).  The scenarios of a Monte-Carlo sweep sit close to each other: from the whole
  * raw state of the feeder solved at its nominal loads the harmonic NR needs 2 - 3 iterations where the flat start needs 20 - 30.

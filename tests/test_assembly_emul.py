@@ -152,3 +152,28 @@ def test_csr_jacobian_checksums_of_the_synthetic_feeders_vs_reference(n, hmax, t
     em = _syn_emul(n, hmax, tmp_path)
     J = em.jacobian_csr(g["V_it0"][:, 0].copy(), g["V_it0"][:, 1].copy())
     check_jacobian_checksums(J, g)
+
+
+# ---- several nonlinear device types (tests/multi_ne.py) -------------------------------------------------------------------------------
+@pytest.mark.parametrize("arrangement", ["interleaved", "blocked"])
+@pytest.mark.parametrize("coupled", [True, False], ids=["c", "uc"])
+def test_device_arithmetic_with_four_device_types_matches_oracle(coupled, arrangement, tmp_path):
+    """The four-type 24-bus feeder (vfd, band, smps, led; H_MAX 11): mismatch, dense Jacobian and the CSR walk follow dev_of_bus to the right
+    table, row and column -- vfd is row-scaled, so a transposed read or a neighbour's type shows -- at the oracle's pf seed and after 1 and 3 of
+    its iterations.  The CSR pattern is the oracle's entry for entry (band's structural zeros are skipped on both sides)."""
+    import multi_ne
+    case = multi_ne.host_case(tmp_path, INPUTS, arrangement=arrangement, coupled=coupled)
+    em, mdl = case["em"], case["mdl"]
+    assert case["n_dev"] == 4 and len(set(case["dev"][case["m"]:])) == 4
+    P, Q = case["buses"]["P"].to_numpy(float), case["buses"]["Q"].to_numpy(float)
+    for it, (Vm, Va) in zip((0, 1, 3), multi_ne.oracle_states(case)):
+        f_o, _ = o.harmonic_mismatch(mdl, Vm.copy(), Va.copy())
+        f_e = em.mismatch(Vm, Va, P, Q)
+        assert np.abs(f_e - f_o).max() <= 1e-13 * max(1.0, np.abs(f_o).max()), (it,)
+        Jo = o.build_harmonic_jacobian(mdl, Vm.copy(), Va.copy()).tocsr()
+        Jo.sort_indices()
+        J_e = em.jacobian(Vm, Va)
+        assert J_e.shape == Jo.shape and np.abs(J_e - Jo.toarray()).max() <= 1e-13 * np.abs(Jo.data).max(), (it,)
+        Jc = em.jacobian_csr(Vm, Va)
+        assert Jc.nnz == Jo.nnz and np.array_equal(Jc.indptr, Jo.indptr) and np.array_equal(Jc.indices, Jo.indices), (it,)
+        assert np.array_equal(Jc.toarray(), J_e)

@@ -672,20 +672,12 @@ def test_two_nonlinear_device_types_vs_oracle(tmp_path):
     """Two Norton device types with different tables on one radial feeder (HG:285: one Norton entry per unique component):
     the per-bus table lookup of the mismatch, the 2x2 / Gauss-Jordan kernels and the per-bus constant leaf images, block-tree
     and dense path, against the oracle on the same inputs.  The second type is the smps table scaled by 0.6 (rotated by 0.3 rad)."""
-    import shutil
-    import pandas as pd
+    import multi_ne
     hp = _hp()
     from harmonic_power_flow_amd import api, synth
     ne_dir = tmp_path / "ne"
     ne_dir.mkdir()
-    shutil.copy(os.path.join(INPUTS, "smps_NE.csv"), ne_dir / "smps_NE.csv")
-    d = pd.read_csv(os.path.join(INPUTS, "smps_NE.csv"), index_col=["Parameter", "Frequency"])
-    f = 0.6 * np.exp(0.3j)
-    def scaled(v):
-        z = complex(v.strip("()")) * f
-        return "(%.17g%+.17gj)" % (z.real, z.imag)
-    d2 = d.apply(lambda col: col.apply(scaled))
-    d2.to_csv(ne_dir / "led_NE.csv")
+    multi_ne.write(ne_dir, INPUTS, types=("smps", "led"))              # smps copied, led = smps times 0.6 e^{0.3j} (tests/multi_ne.py)
     fb, fl = synth.gen(60, seed=5, outdir=str(tmp_path))
     rows = open(fb).read().splitlines()
     for i in range(1, len(rows)):

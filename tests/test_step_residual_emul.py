@@ -108,3 +108,38 @@ def test_residual_rows_equal_f_minus_J_dx(name, form):
                 worst = max(worst, float(np.nanmax(np.where(scale > 0, np.abs(r - r_ref).astype(np.float64) / (U53 * scale), 0.0))))
     print("\nRESIDUAL EMUL %-14s form %d: worst |r - (f - J dx)| = %.2f x 2^-53 (|J||dx| + |f|)" % (name, form, worst))
     assert worst > 0.0 or em.Hn == 1
+
+
+@pytest.mark.parametrize("form", [0, 1], ids=["stacked", "bus_major"])
+@pytest.mark.parametrize("arrangement", ["interleaved", "blocked"])
+@pytest.mark.parametrize("coupled", [True, False], ids=["c", "uc"])
+def test_residual_rows_with_four_device_types(coupled, arrangement, form, tmp_path):
+    """The four-type 24-bus feeder of tests/multi_ne.py (H_MAX 11): step_residual_row reads Y_N of the row's own type and skips the zeros of a
+    band bus as the CSR walk does, in both forms of the step, at the bound of the file."""
+    import multi_ne
+    lib = _load()
+    case = multi_ne.host_case(tmp_path, INPUTS, arrangement=arrangement, coupled=coupled)
+    em = case["em"]
+    P, Q = case["buses"]["P"].to_numpy(float), case["buses"]["Q"].to_numpy(float)
+    rng = np.random.default_rng(7)
+    worst = 0.0
+    for Vm, Va in multi_ne.oracle_states(case):
+        J = em.jacobian_csr(Vm, Va)
+        f = em.mismatch(Vm, Va, P, Q)
+        k = np.diff(J.indptr)
+        assert len(set(k[case["m"] - 1:case["m"] - 1 + em.Hn * em.n])) > (2 if coupled else 1)       # rows of several lengths
+        Jl, aJ = J.astype(np.longdouble), abs(J)
+        for dx in (rng.standard_normal(J.shape[0]) * 10.0 ** rng.uniform(-6, 0, J.shape[0]), spl.spsolve(J.tocsc(), f)):
+            r, a, w, f_e = _residual(lib, em, Vm, Va, P, Q, dx, form)
+            assert np.array_equal(f_e, f)
+            scale = np.asarray(aJ @ np.abs(dx)).ravel() + np.abs(f)
+            r_ref = f.astype(np.longdouble) - Jl @ dx.astype(np.longdouble)
+            miss = np.abs(r - r_ref).astype(np.float64) - (k + 4) * U53 * scale
+            assert (miss <= 0).all(), (int(np.argmax(miss)), float(miss.max()))
+            assert (np.abs(a - np.asarray(aJ @ np.abs(dx)).ravel()) <= (k + 4) * U53 * scale).all()
+            w_ref = np.asarray(aJ.sum(axis=1)).ravel()
+            assert (np.abs(w - w_ref) <= (k + 4) * U53 * w_ref).all()
+            with np.errstate(invalid="ignore", divide="ignore"):
+                worst = max(worst, float(np.nanmax(np.where(scale > 0, np.abs(r - r_ref).astype(np.float64) / (U53 * scale), 0.0))))
+    print("\nRESIDUAL EMUL four types %s %s form %d: worst |r - (f - J dx)| = %.2f x 2^-53 (|J||dx| + |f|)" % ("c" if coupled else "uc", arrangement, form, worst))
+    assert worst > 0.0

@@ -18,9 +18,9 @@ from harmonic_power_flow_amd import _lib, ingest, synth   # noqa: E402
 INPUTS = os.path.join(REPO, "tests", "golden", "inputs")
 
 
-def plan(nb, hmax, seed=0, max_scenarios=1, ties=0, lines_out=False, files=None):
+def plan(nb, hmax, seed=0, max_scenarios=1, ties=0, lines_out=False, files=None, ne_dir=None):
     """rows of the planner's dump (ints); lines_out=True: every line of the dump instead, comments included, in file order.
-    files=(buses.csv, lines.csv): that network instead of the synthetic feeder of nb buses"""
+    files=(buses.csv, lines.csv): that network instead of the synthetic feeder of nb buses; ne_dir: its Norton tables (default: the golden inputs)"""
     tmp = tempfile.mkdtemp(prefix="hpf_plan_")
     if files:
         fb, fl = files
@@ -31,7 +31,7 @@ def plan(nb, hmax, seed=0, max_scenarios=1, ties=0, lines_out=False, files=None)
     st = hp.Settings(H_MAX=hmax)
     buses, lines, m, n, c = hp.init_network(fb, fl, settings=st)
     Y = hp.build_admittance_matrices(buses, lines, st.HARMONICS)
-    NE = hp.import_Norton_Equivalents(buses, True, st, INPUTS)
+    NE = hp.import_Norton_Equivalents(buses, True, st, ne_dir or INPUTS)
     dev, Y_N, I_N, n_dev = ingest.norton_arrays(buses, NE, True, len(st.HARMONICS))
     d = _lib.hpf_desc()
     rowptr = np.ascontiguousarray(Y.rowptr, dtype=np.int32)

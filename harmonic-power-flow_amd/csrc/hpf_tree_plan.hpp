@@ -426,6 +426,10 @@ static void plan_bus_classes(const hpf_desc& d, Tree& T, PlanWork& W) {
         if (!T.lin[i]) ndc[T.parent[i]]++;
     if (contract)
         for (int i = 1; i < n; ++i) pass[i] = (!T.lin[i] && i < d.m && ndc[i] == 1 && !(use_fp && fmask[i])) ? 1 : 0;
+    // The parent of a dense PV bus stays a dense bus: a chain contracted down to the PV bus would leave its block the chain's series admittance
+    // in place of the line's, and the static pivot order of a block without the V_m column then costs the step three digits.
+    for (int i = 1; i < d.c && i < n; ++i)
+        if (!T.lin[i] && !pass[i] && T.parent[i] > 0) pass[T.parent[i]] = 0;
     for (size_t oi = 1; oi < order.size(); ++oi) {
         const int i = order[oi];
         if (!kept(T, W, i)) continue;
@@ -1076,7 +1080,9 @@ static void plan_compress(const hpf_desc& d, const Switches& sw, Tree& T, PlanWo
             if (gjb[k2] && pard[k2] >= 0 && gjb[pard[k2]] && !(use_fp && fmask[k2]))
                 for (int i = dchild_ptr[k2]; i < dchild_ptr[k2 + 1]; ++i) {
                     const int c1 = dchild[i];
-                    if (!gjb[c1] || (use_fp && fmask[c1])) continue;
+                    // (a PV bus is no pending child: with v gone first its block loses the line admittance towards v, and the static pivot
+                    //  order of a block without the V_m column then costs the step three digits -- DESIGN.md 3.13)
+                    if (!gjb[c1] || (use_fp && fmask[c1]) || c1 < d.c) continue;
                     const int levk = std::max(1, (c1 == a1 ? m2 : m1) + 1), levc = std::max(nrm[c1], levk + 1);
                     if (levc < best) {
                         best = levc;

@@ -347,6 +347,12 @@ struct hpf_handle {
     hipEvent_t poll_ev[2] = {nullptr, nullptr};
     double *trace_Vm = nullptr, *trace_Va = nullptr;   // hpf_set_trace: caller's [S][trace_cap][Hn*n] arrays (per-iteration states)
     int trace_cap = 0;
+    // hpf_solve with a trace on a handle that may repeat: the first pass records into trace_stage (the layout of the caller's arrays: Vm, then
+    // Va), the repeat pass writes the rows of the scenarios in trace_only alone; trace_last: the last row the pass just finished recorded
+    std::vector<double> trace_stage;
+    bool trace_staged = false;
+    std::vector<int> trace_only;
+    int trace_last = 0;
     double* d_Z = nullptr;            // [S][n][b*b]
     double* d_w = nullptr;            // [S][n][b]
     double* d_x = nullptr;            // [S][n][b]  Newton step, bus-major

@@ -1580,24 +1580,55 @@ int check_info(hpf_handle* h, const std::vector<int>& was_active) {
     return HPF_OK;
 }
 
-// state of every scenario after iteration `it` -> the caller's trace arrays (hpf_set_trace), ABI order q*n + i
+// state of every scenario after iteration `it` -> the caller's trace arrays (hpf_set_trace), ABI order q*n + i.  A first pass that may be
+// repeated records into the staging copy instead (trace_staged; trace_finish sorts the rows out), the repeat pass only the scenarios it runs
+// (trace_only): a scenario's rows never hold states of a pass its result does not come from.
 int trace_record(hpf_handle* h, int it) {
     if (!h->trace_Vm || it >= h->trace_cap) return HPF_OK;
-    const size_t count = (size_t)h->n * h->Hn, cnt = (size_t)h->S * count;
+    const size_t count = (size_t)h->n * h->Hn, cnt = (size_t)h->S * count, all = (size_t)h->S * h->trace_cap * count;
     std::vector<double> tm(cnt), ta(cnt);
     HIPCHK(hipMemcpyAsync(tm.data(), h->d_Vm, sizeof(double) * cnt, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(ta.data(), h->d_Va, sizeof(double) * cnt, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    double* const bm = h->trace_staged ? h->trace_stage.data() : h->trace_Vm;
+    double* const ba = h->trace_staged ? h->trace_stage.data() + all : h->trace_Va;
     for (int sc = 0; sc < h->S; ++sc) {
-        double* om = h->trace_Vm + ((size_t)sc * h->trace_cap + it) * count;
-        double* oa = h->trace_Va + ((size_t)sc * h->trace_cap + it) * count;
+        if (!h->trace_only.empty() && !h->trace_only[sc]) continue;
+        double* om = bm + ((size_t)sc * h->trace_cap + it) * count;
+        double* oa = ba + ((size_t)sc * h->trace_cap + it) * count;
         for (int i = 0; i < h->n; ++i)
             for (int q = 0; q < h->Hn; ++q) {
                 om[(size_t)q * h->n + i] = tm[(size_t)sc * count + (size_t)i * h->Hn + q];
                 oa[(size_t)q * h->n + i] = ta[(size_t)sc * count + (size_t)i * h->Hn + q];
             }
     }
+    h->trace_last = it;
     return HPF_OK;
+}
+
+// The trace of a solve whose first pass was staged, after its last pass.  mask[s] != 0: scenario s was repeated (its rows 1 .. it_rep are the
+// repeat's, already in the caller's arrays); niter1: the iteration counts the first pass left.  Rows 0 .. L are written, L = the largest
+// iteration count among the results the call returns: a scenario that was not repeated gets its first-pass rows, a repeated one row 0 (the
+// entering state) from the stage; behind its own pass every scenario repeats its last state up to L.  Rows beyond L stay the caller's.
+void trace_finish(hpf_handle* h, const std::vector<int>& mask, const std::vector<int>& niter1, int it_rep) {
+    const size_t count = (size_t)h->n * h->Hn, all = (size_t)h->S * h->trace_cap * count;
+    const int top = h->trace_cap - 1;
+    int Lu = 0;
+    for (int s = 0; s < h->S; ++s)
+        if (!mask[s] && niter1[s] > Lu) Lu = niter1[s];
+    Lu = Lu < top ? Lu : top;
+    it_rep = it_rep < top ? it_rep : top;
+    const int L = Lu > it_rep ? Lu : it_rep;
+    for (int v = 0; v < 2; ++v) {
+        double* out = v ? h->trace_Va : h->trace_Vm;
+        const double* stage = h->trace_stage.data() + (v ? all : 0);
+        for (int s = 0; s < h->S; ++s) {
+            double* rows = out + (size_t)s * h->trace_cap * count;
+            const int own = mask[s] ? it_rep : Lu;                 // the last row the scenario's own pass recorded
+            memcpy(rows, stage + (size_t)s * h->trace_cap * count, sizeof(double) * count * (mask[s] ? 1 : (size_t)Lu + 1));
+            for (int k = own + 1; k <= L; ++k) memcpy(rows + (size_t)k * count, rows + (size_t)own * count, sizeof(double) * count);
+        }
+    }
 }
 
 // pinned double buffer + events through which the host reads the slot counters one chunk late (every object under its own check: a failed
@@ -1639,6 +1670,7 @@ int nr_pass(hpf_handle* h, double thresh, int max_iter, const int* mask) {
     hipLaunchKernelGGL(k_finalize, dim3((unsigned)S), dim3(64), 0, h->stream, S, 1, thresh, max_iter, h->hist_cap,
                        hist_off, h->d_errpart, h->errpart_stride, err_parts<FUND>(h), h->d_err, h->d_niter, h->d_active, h->d_nactive, h->d_hist, 0, mask);
     const bool trace = !FUND && h->trace_Vm != nullptr;
+    h->trace_last = 0;
     if (trace && !mask && (r = trace_record(h, 0))) return r;
     // The per-scenario stop rule lives on the device (k_finalize after every iteration, in the scenario group's own pipeline):
     // frozen scenarios are skipped by every kernel, so the host only has to notice when NO scenario is active any more, and
@@ -2011,22 +2043,45 @@ int nr_loop(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* err
         HIPCHK(hipMemcpyAsync(h->d_Vm0, h->d_Vm, sizeof(double) * S * count, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(h->d_Va0, h->d_Va, sizeof(double) * S * count, hipMemcpyDeviceToDevice, h->stream));
     }
-    if ((r = nr_pass<FUND>(h, thresh, max_iter, nullptr))) return r;
+    // (trace: the first pass of a handle that may repeat is staged -- which rows belong to the caller is known after k_mark_repeat)
+    const bool stage = can_repeat && h->trace_Vm != nullptr;
+    if (stage) h->trace_stage.assign(2 * (size_t)S * h->trace_cap * count, 0.0);
+    h->trace_staged = stage;
+    r = nr_pass<FUND>(h, thresh, max_iter, nullptr);
+    h->trace_staged = false;
+    if (r) return r;
     if (can_repeat) {
         int nrep = 0;
         HIPCHK(hipMemsetAsync(h->d_nactive, 0, sizeof(int), h->stream));
         hipLaunchKernelGGL(k_mark_repeat, dim3((S + 63) / 64), dim3(64), 0, h->stream, S, h->d_err, h->d_pivflag, h->d_mask,
                            h->d_nactive, h->resid_check ? h->d_eta : (double*)nullptr, h->S_alloc);
         HIPCHK(hipMemcpyAsync(&nrep, h->d_nactive, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        std::vector<int> rep_mask, niter1;
+        if (stage) {
+            rep_mask.resize(S);
+            niter1.resize(S);
+            HIPCHK(hipMemcpyAsync(rep_mask.data(), h->d_mask, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(niter1.data(), h->d_niter, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream));
+        }
         HIPCHK(hipStreamSynchronize(h->stream));
+        h->trace_last = 0;
         if (nrep > 0) {
             const unsigned gx = (unsigned)(((count > (size_t)h->hist_cap ? count : (size_t)h->hist_cap) + TPB - 1) / TPB);
             hipLaunchKernelGGL(k_restore_masked, dim3(gx, (unsigned)S), dim3(TPB), 0, h->stream, (int)count, h->d_mask, h->d_Vm0,
                                h->d_Va0, h->d_Vm, h->d_Va, h->d_hist, h->hist_cap);
             h->gj_mode = 0;
+            h->trace_only = rep_mask;
             r = nr_pass<FUND>(h, thresh, max_iter, h->d_mask);
+            h->trace_only.clear();
             h->gj_mode = 1;
-            if (r) return r;
+            if (r) {
+                h->trace_stage = std::vector<double>();
+                return r;
+            }
+        }
+        if (stage) {
+            trace_finish(h, rep_mask, niter1, h->trace_last);
+            h->trace_stage = std::vector<double>();
         }
     }
     h->mismatch_valid = false;   // frozen scenarios leave stale rows in d_f: hpf_mismatch before hpf_iterate

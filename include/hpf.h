@@ -181,7 +181,11 @@ int  hpf_solve_queue(hpf_handle* h, int n_total, const double* P, const double* 
  * every iterate, hcne_based_on_fuchs.py:186,370-372): while set, hpf_solve writes the voltages after iteration k (k = 0: the
  * state it was entered with) of every scenario to Vm_traj / Va_traj [S][cap][Hn*n] (caller-owned host arrays, stacked order
  * q*n + i; frozen scenarios repeat their last state; iterations >= cap are not recorded).  The solve then synchronises with the
- * host after every iteration.  NULL, NULL, 0 switches it off. */
+ * host after every iteration.  Rows 0 .. L are written, L = the largest n_iter among the results the call returns; rows beyond L are left
+ * as the caller filled them.  Where hpf_solve repeats scenarios with partial pivoting (flags bit 4), the rows of a repeated scenario are the
+ * repeat's (row 0: the entering state) and the rows of every other scenario those of the first pass: no row holds a state of a pass the
+ * scenario's result does not come from.  (Such a handle keeps the first pass in a host copy of the size of the two arrays until it knows which
+ * scenarios are repeated.)  NULL, NULL, 0 switches it off. */
 int  hpf_set_trace(hpf_handle* h, double* Vm_traj, double* Va_traj, int cap);
 
 /* One unconditional NR iteration (Jacobian -> solve -> update -> mismatch) for all S scenarios, repeated `iters`

@@ -104,6 +104,8 @@ SYMBOLS = {
     "hpf_sparse_solve": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p]),
     "hpf_impedance_scan": (C.c_int, [C.c_int, C.POINTER(hpf_zscan_net), C.c_int, c_dbl_p, c_dbl_p, C.c_int, c_int_p, C.c_int, c_dbl_p, c_dbl_p,
                                      c_dbl_p, c_int_p]),
+    "hpf_penetration": (C.c_int, [C.c_int, C.POINTER(hpf_zscan_net), C.c_int, c_dbl_p, c_dbl_p, C.c_int, C.c_int, c_int_p, c_dbl_p, C.c_int, C.c_int,
+                                  c_dbl_p, c_dbl_p, c_dbl_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p, c_int_p, c_dbl_p, c_dbl_p]),
     "hpf_solve_flops": (C.c_double, [_H]),
     "hpf_solve_bytes": (C.c_double, [_H]),
     "hpf_back_bytes": (C.c_double, [_H]),

@@ -645,6 +645,29 @@ def impedance_scan(buses, lines, h, shunts=None, capacitors=None, transfer=None,
     Y_N (uncoupled: entry q) of its device is added at every nonlinear bus (settings, ne_dir, coupled: as for hpf) -- ValueError otherwise.
     Bus arguments are the reference's 1-based IDs, as in line_flows.  A grid point at which some Z_ii is not finite (a network without any
     shunt at h = 1) leaves inf / NaN in the result."""
+    model, h, ids, yx = _scan_network(buses, lines, h, shunts, capacitors, settings, ne_dir, coupled)
+    transfer = [int(b) for b in (transfer or [])]
+    sel = [ids.index(b) for b in transfer]
+    _, Z, Zt, zpeak, fpeak = impedance_scan_arrays(model, h, yx, sel, 0, full, device)
+    return ImpedanceScan(h, Z, Zt, zpeak, fpeak, ids, transfer)
+
+
+def _norton_on_grid(buses, h, what, settings, ne_dir, coupled):
+    """The Norton equivalents at the grid points of h, every one of which must be in settings.HARMONICS (ValueError otherwise; `what` names the
+    argument) -> dev_of_bus [n], Y_N, I_N (ingest.norton_arrays), q [F] the position of every grid point in settings.HARMONICS"""
+    st = settings or globals()["settings"]
+    harmonics = list(st.HARMONICS)
+    if any(x not in harmonics for x in h):
+        raise ValueError("%s=\"norton\" needs every grid point in settings.HARMONICS" % what)
+    q = np.array([harmonics.index(x) for x in h])
+    NE = import_Norton_Equivalents(buses, coupled, st, ne_dir)
+    dev, Y_N, I_N, _ = ingest.norton_arrays(buses, NE, coupled, len(harmonics))
+    return dev, Y_N, I_N, q
+
+
+def _scan_network(buses, lines, h, shunts, capacitors, settings, ne_dir, coupled):
+    """What impedance_scan and penetration share: the line model, the grid as a float64 vector, the 1-based bus IDs in bus order and the shunt
+    admittances y_extra [F][n] (or None) of `shunts` and `capacitors`"""
     model = admittance.line_model(buses, lines)
     n = model["n"]
     h = np.ascontiguousarray(h, dtype=np.float64).reshape(-1)
@@ -654,13 +677,7 @@ def impedance_scan(buses, lines, h, shunts=None, capacitors=None, transfer=None,
     if isinstance(shunts, str):
         if shunts != "norton":
             raise ValueError("shunts must be an [F][n] array or \"norton\"")
-        st = settings or globals()["settings"]
-        harmonics = list(st.HARMONICS)
-        if any(x not in harmonics for x in h):
-            raise ValueError("shunts=\"norton\" needs every grid point in settings.HARMONICS")
-        q = np.array([harmonics.index(x) for x in h])
-        NE = import_Norton_Equivalents(buses, coupled, st, ne_dir)
-        dev, Y_N, _, _ = ingest.norton_arrays(buses, NE, coupled, len(harmonics))
+        dev, Y_N, _, q = _norton_on_grid(buses, h, "shunts", settings, ne_dir, coupled)
         yx = np.zeros((F, n), dtype=np.complex128)
         for i in np.nonzero(dev >= 0)[0]:
             yx[:, i] = Y_N[dev[i], q, q] if coupled else Y_N[dev[i], q]
@@ -672,10 +689,100 @@ def impedance_scan(buses, lines, h, shunts=None, capacitors=None, transfer=None,
         yx = np.zeros((F, n), dtype=np.complex128) if yx is None else yx
         for bus, b in capacitors.items():
             yx[:, ids.index(int(bus))] += 1j * h * float(b)
-    transfer = [int(b) for b in (transfer or [])]
-    sel = [ids.index(b) for b in transfer]
-    _, Z, Zt, zpeak, fpeak = impedance_scan_arrays(model, h, yx, sel, 0, full, device)
-    return ImpedanceScan(h, Z, Zt, zpeak, fpeak, ids, transfer)
+    return model, h, ids, yx
+
+
+class Penetration:
+    """Result of `penetration`: h [F] the grid; V [S][F][n] complex bus voltages (None with full=False); rss [S][n] = sqrt(sum_f |V|^2) over the
+    whole grid; over the S scenarios, per (grid point, bus): vmax [F][n] the largest |V|, varg [F][n] its scenario (ties: the smallest), vmean and
+    vstd [F][n] of |V|; per bus: rss_max, rss_arg, rss_mean, rss_std [n] of rss.  bus_ids: the 1-based IDs of the n columns; at: those of the
+    injecting buses."""
+
+    def __init__(self, h, S, out, bus_ids, at):
+        self.h, self.S, self.bus_ids, self.at = h, S, bus_ids, at
+        self.V, self.rss = out["V"], out["rss"]
+        for pre in ("v", "rss_"):
+            setattr(self, pre + "max", out[pre + "max"])
+            setattr(self, pre + "arg", out[pre + "arg"])
+            mean = out[pre + "sum"] / S
+            setattr(self, pre + "mean", mean)
+            setattr(self, pre + "std", np.sqrt(np.maximum(out[pre + "sumsq"] / S - mean * mean, 0.0)))
+
+
+PENETRATION_OUTPUTS = ("V", "rss", "vmax", "varg", "vsum", "vsumsq", "rss_max", "rss_arg", "rss_sum", "rss_sumsq")
+
+
+def penetration_arrays(model, h, I, inj, y_extra=None, chunk_f=0, chunk_s=0, full=True, device=0):
+    """hpf_penetration on the arrays of `admittance.line_model`: h [F] real orders, I [S][F][n_inj] complex currents injected at the 0-based bus
+    indices inj, y_extra [F][n] complex or None -> (code, dict of the arrays PENETRATION_OUTPUTS; V is None with full=False); code 0 or 3
+    (HPF_E_SINGULAR: the outputs are written), any other code raises."""
+    lib = _lib.load()
+    n, F = int(model["n"]), len(h)
+    h = np.ascontiguousarray(h, dtype=np.float64)
+    inj = np.ascontiguousarray(inj, dtype=np.int32).reshape(-1)
+    I = np.ascontiguousarray(I, dtype=np.complex128)
+    if I.ndim != 3 or I.shape[1:] != (F, len(inj)):
+        raise ValueError("I must be [S][F][n_inj] = [S][%d][%d], got %s" % (F, len(inj), I.shape))
+    S = I.shape[0]
+    arr = {k: np.ascontiguousarray(model[k], dtype=np.int32 if k in ("fr", "to") else np.float64) for k in ("fr", "to", "R", "X", "gsh", "bsh", "xsh")}
+    ip, dp = _lib.c_int_p, _lib.c_dbl_p
+    net = _lib.hpf_zscan_net(n, int(model["nb"]), arr["fr"].ctypes.data_as(ip), arr["to"].ctypes.data_as(ip),
+                             *[arr[k].ctypes.data_as(dp) for k in ("R", "X", "gsh", "bsh", "xsh")])
+    yx = None if y_extra is None else np.ascontiguousarray(y_extra, dtype=np.complex128)
+    if yx is not None and yx.shape != (F, n):
+        raise ValueError("y_extra must be [F][n]")
+    out = {"V": np.empty((S, F, n), dtype=np.complex128) if full else None, "rss": np.empty((S, n))}
+    for pre, shape in (("v", (F, n)), ("rss_", (n,))):
+        out.update({pre + "max": np.empty(shape), pre + "arg": np.empty(shape, dtype=np.int32), pre + "sum": np.empty(shape),
+                    pre + "sumsq": np.empty(shape)})
+    ptrs = [None if out[k] is None else out[k].ctypes.data_as(ip if k.endswith("arg") else dp) for k in PENETRATION_OUTPUTS]
+    rc = lib.hpf_penetration(int(device), C.byref(net), F, h.ctypes.data_as(dp), None if yx is None else yx.ctypes.data_as(dp), S, len(inj),
+                             inj.ctypes.data_as(ip), I.ctypes.data_as(dp), int(chunk_f), int(chunk_s), *ptrs)
+    if rc not in (0, 3):
+        raise _lib.HpfError(rc, 0, "hpf_penetration")
+    return rc, out
+
+
+def penetration(buses, lines, h, currents, at=None, shunts=None, capacitors=None, sources=None, full=True, device=0, settings=None, ne_dir=None,
+                coupled=True):
+    """Harmonic penetration on the GPU (the "current injection method"; not in the reference): the bus voltages V(h) = Y(h)^-1 I(h) that S
+    scenarios of injected harmonic currents produce over the grid `h` of real harmonic orders > 0, with statistics over the scenarios
+    -> Penetration.  The network, `shunts` and `capacitors` are those of impedance_scan (shunts="norton" makes the Norton admittances part of
+    Y(h): the harmonic part of an uncoupled Norton model is then exactly this linear solve).
+    currents: [S][F][len(at)] complex, or [F][len(at)] for one scenario -- the current injected INTO the network at the buses `at` (1-based IDs,
+    each once), p.u.; or "norton": I_N[dev(i)][q] of its device, as stored, at every nonlinear bus (`at` must be None, every grid point one of
+    settings.HARMONICS; settings, ne_dir, coupled: as for hpf).  With currents="norton", sources={"scale": a, "shift": phi} ([S][n - m], either
+    may be missing: 1 / 0) makes S scenarios of a units of each bus's device, their waveform shifted in time by phi rad at the fundamental:
+    I = a e^(j h phi) I_N, expanded on the host (sweep.source_currents).  A grid point at which Y(h) is singular leaves inf / NaN in the result."""
+    model, h, ids, yx = _scan_network(buses, lines, h, shunts, capacitors, settings, ne_dir, coupled)
+    F = len(h)
+    if isinstance(currents, str):
+        if currents != "norton" or at is not None:
+            raise ValueError("currents must be an array with the bus IDs `at`, or \"norton\" with at=None")
+        dev, _, I_N, q = _norton_on_grid(buses, h, "currents", settings, ne_dir, coupled)
+        inj = np.nonzero(dev >= 0)[0]
+        I_bus = I_N[dev[inj]][:, q]                           # [n - m][F]
+        if sources is None:
+            I = np.ascontiguousarray(I_bus.T)[None]
+        else:
+            if not isinstance(sources, dict) or not sources or not set(sources) <= {"scale", "shift"}:
+                raise ValueError("penetration: sources=%r ({'scale': .., 'shift': ..})" % (sources,))
+            from .sweep import source_currents, sources_argument
+            S = len(next(iter(sources.values())))
+            _, ab = sources_argument(sources, S, len(inj), F, "penetration")
+            I = np.ascontiguousarray(source_currents(I_bus, ab[:, :, 0], ab[:, :, 1], h).transpose(0, 2, 1))
+    else:
+        if sources is not None:
+            raise ValueError("penetration: sources needs currents=\"norton\"")
+        if at is None:
+            raise ValueError("penetration: currents as an array needs the bus IDs `at`")
+        inj = np.array([ids.index(int(b)) for b in at], dtype=np.int32)
+        I = np.asarray(currents, dtype=np.complex128)
+        I = I[None] if I.ndim == 2 else I
+        if I.ndim != 3 or I.shape[1:] != (F, len(inj)):
+            raise ValueError("currents must be [S][F][len(at)] = [S][%d][%d] (or [F][len(at)]), got %s" % (F, len(inj), I.shape))
+    _, out = penetration_arrays(model, h, I, inj, yx, 0, 0, full, device)
+    return Penetration(h, I.shape[0], out, ids, [ids[i] for i in inj])
 
 
 def solve(filename_buses, filename_lines, coupled=True, settings=None, ne_dir=None, solver="auto", verbose=False, extra_iters=0,

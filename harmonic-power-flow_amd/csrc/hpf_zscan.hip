@@ -1,11 +1,12 @@
 // hpf_impedance_scan: driving-point and transfer impedances over a grid of harmonic orders (hpf_zscan.hpp has the arithmetic and the planner;
 // include/hpf.h the contract).  Every kernel maps a thread to (item, frequency point) with the frequency fastest: block b of a launch over m items
 // serves item b / fb, points (b % fb) * ZS_TPB + threadIdx.x, fb = ceil(Fc / ZS_TPB) -- a one-dimensional grid, so that the widest depth of a large
-// star still fits; the host keeps n * fb <= 2^30.
+// star still fits; the host keeps n * fb <= 2^30.  hpf_penetration (below, hpf_penetration.hpp) shares the factor kernels of the scan.
 #include <algorithm>
 #include <utility>
 
 #include "hpf_internal.hpp"
+#include "hpf_penetration.hpp"
 #include "hpf_zscan.hpp"
 
 using namespace hpf;
@@ -292,4 +293,312 @@ extern "C" int hpf_impedance_scan(int device, const hpf_zscan_net* net, int F, c
         singular |= bad[i] != 0;
     }
     return done(singular ? HPF_E_SINGULAR : HPF_OK);
+}
+
+// ---- hpf_penetration ---------------------------------------------------------------------------------------------------------------------------
+// V(h) = Y(h)^-1 I(h) for S scenarios (hpf_penetration.hpp has the arithmetic; include/hpf.h the contract).  The factor of a chunk of fc frequency
+// points (w, t, the tie columns, W^-1) comes from the scan's kernels above; the right-hand sides of a chunk of sc scenarios live in place as
+// r [n][J], j = f sc + s, J = fc sc.  The walks map a thread to (bus of the depth, j) with j fastest (zs_item over J): a wavefront reads 64
+// consecutive values of r and, with sc >= 64, one w_i / t_i.
+namespace {
+
+// r [inj[q]][f sc + s] <- in [s][f][q] (the caller's currents of the chunk, [sc][fc][n_inj]): 32 x 32 tiles over (s, q) of one point f through LDS,
+// so that the loads run along q and the stores along s; tile b of a one-dimensional grid
+__global__ __launch_bounds__(ZS_TILE * 8) void k_pen_scatter(const cplx* __restrict__ in, const int* __restrict__ inj, int n_inj, int fc, int sc,
+                                                             cplx* __restrict__ r) {
+    __shared__ cplx tile[ZS_TILE][ZS_TILE + 1];
+    const long long tq = (n_inj + ZS_TILE - 1) / ZS_TILE, ts = (sc + ZS_TILE - 1) / ZS_TILE, b = blockIdx.x;
+    const int f = (int)(b / (ts * tq)), s0 = (int)(b % (ts * tq) / tq) * ZS_TILE, q0 = (int)(b % tq) * ZS_TILE;
+    const int tx = threadIdx.x & (ZS_TILE - 1), ty = threadIdx.x / ZS_TILE;
+    const size_t J = (size_t)fc * sc;
+    for (int y = ty; y < ZS_TILE; y += 8)
+        if (s0 + y < sc && q0 + tx < n_inj) tile[y][tx] = in[((size_t)(s0 + y) * fc + f) * n_inj + (q0 + tx)];
+    __syncthreads();
+    for (int y = ty; y < ZS_TILE; y += 8)
+        if (q0 + y < n_inj && s0 + tx < sc) r[(size_t)inj[q0 + y] * J + (size_t)f * sc + (s0 + tx)] = tile[tx][y];
+}
+
+// upward walk of the right-hand sides, the m buses `nodes` of one depth: r_i gathers t_c r_c of its children (t_c stays in registers while applied)
+__global__ __launch_bounds__(ZS_TPB) void k_pen_up(ZscanView V, const int* __restrict__ nodes, int m, int fc, int sc, const cplx* __restrict__ t,
+                                                   cplx* r) {
+    int bi, j;
+    if (!zs_item(m, fc * sc, bi, j)) return;
+    const int i = nodes[bi];
+    if (V.child_ptr[i] == V.child_ptr[i + 1]) return;    // a leaf: r_i = b_i
+    const size_t J = (size_t)fc * sc;
+    r[(size_t)i * J + j] = pen_up(V.child_ptr, V.child, i, t, r, (size_t)fc, J, (size_t)(j / sc), (size_t)j);
+}
+
+// downward walk of one depth: V overwrites r
+__global__ __launch_bounds__(ZS_TPB) void k_pen_down(ZscanView V, const int* __restrict__ nodes, int m, int fc, int sc, const cplx* __restrict__ w,
+                                                     const cplx* __restrict__ t, cplx* r) {
+    int bi, j;
+    if (!zs_item(m, fc * sc, bi, j)) return;
+    const int i = nodes[bi], p = V.parent[i];
+    const size_t J = (size_t)fc * sc, o = (size_t)i * J + j, fo = (size_t)i * fc + j / sc;
+    r[o] = p < 0 ? pen_down_root(w[fo], r[o]) : pen_down(w[fo], r[o], t[fo], r[(size_t)p * J + j]);
+}
+
+// ties: the k coefficients c_l of every j -> coef [k][J]
+__global__ __launch_bounds__(ZS_TPB) void k_pen_tie_coef(int k, const int* __restrict__ ta, const int* __restrict__ tb, int fc, int sc,
+                                                         const cplx* __restrict__ Winv, const cplx* __restrict__ r, cplx* __restrict__ coef) {
+    int z, j;
+    if (!zs_item(1, fc * sc, z, j)) return;
+    pen_tie_coef(k, ta, tb, Winv, r, (size_t)fc, (size_t)fc * sc, (size_t)(j / sc), (size_t)j, coef);
+}
+
+// ties: V'_i = V_i - sum_l u_l[i] c_l
+__global__ __launch_bounds__(ZS_TPB) void k_pen_tie_fix(int k, int n, int fc, int sc, const cplx* __restrict__ tc, const cplx* __restrict__ coef,
+                                                        cplx* __restrict__ r) {
+    int i, j;
+    if (!zs_item(n, fc * sc, i, j)) return;
+    const size_t J = (size_t)fc * sc, o = (size_t)i * J + j;
+    r[o] = pen_tie_fix(k, tc, coef, (size_t)n, (size_t)fc, J, (size_t)(j / sc), (size_t)j, i, r[o]);
+}
+
+// statistics: a row-wise SEQUENTIAL fold of a [rows][cols] matrix, one lane per row, one wavefront per block.  The wavefront loads 64 rows x 32
+// columns at a time along the rows (two 512-byte segments per load instruction), leaves the derived value in LDS, and every lane then folds its own
+// row in ascending column order (pen_stat_add) -- the order the sums over the scenarios are defined in.
+//   RSS = false: the matrix is r viewed as [n fc][sc] (row p = i fc + f), value = |V|; the running statistics of row p are those of (f0 + f, i),
+//                carried from scenario chunk to scenario chunk (c_start = s0; fresh at s0 = 0).  *bad = 1 for a non-finite V.
+//   RSS = true:  the matrix is the finished sums of squares [n][S], value = sqrt, written back in place (the rss of (i, s)); the statistics of row i.
+constexpr int PEN_FOLD_COLS = 32;
+template <bool RSS>
+__global__ __launch_bounds__(64) void k_pen_fold(long long rows, int cols, int c_start, int n, int fc, int f0, const cplx* __restrict__ r,
+                                                 double* __restrict__ sq, unsigned long long* __restrict__ key, int* __restrict__ arg,
+                                                 double* __restrict__ sum, double* __restrict__ sumsq, int* __restrict__ bad) {
+    __shared__ double tile[64][PEN_FOLD_COLS + 1];
+    const int lane = threadIdx.x, tx = lane & (PEN_FOLD_COLS - 1);
+    const long long p0 = (long long)blockIdx.x * 64, p = p0 + lane;
+    size_t g = 0;
+    PenStat st = pen_stat_start();
+    if (p < rows) {
+        g = RSS ? (size_t)p : (size_t)(f0 + (int)(p % fc)) * n + (size_t)(p / fc);
+        if (c_start != 0) st = {key[g], arg[g], sum[g], sumsq[g]};
+    }
+    int nonfinite = 0;
+    for (int c0 = 0; c0 < cols; c0 += PEN_FOLD_COLS) {
+        for (int y = lane / PEN_FOLD_COLS; y < 64; y += 64 / PEN_FOLD_COLS)
+            if (p0 + y < rows && c0 + tx < cols) {
+                const size_t o = (size_t)(p0 + y) * cols + (c0 + tx);
+                if (RSS) {
+                    const double a = sqrt(sq[o]);
+                    sq[o] = a;
+                    tile[y][tx] = a;
+                } else {
+                    const cplx v = r[o];
+                    nonfinite |= !zscan_finite(v);
+                    tile[y][tx] = zscan_abs(v);
+                }
+            }
+        __syncthreads();
+        if (p < rows) {
+            const int cn = cols - c0 < PEN_FOLD_COLS ? cols - c0 : PEN_FOLD_COLS;
+            for (int c = 0; c < cn; ++c) pen_stat_add(st, tile[lane][c], c_start + c0 + c);
+        }
+        __syncthreads();
+    }
+    if (p < rows) {
+        key[g] = st.key;
+        arg[g] = st.arg;
+        sum[g] = st.sum;
+        sumsq[g] = st.sumsq;
+    }
+    if (!RSS && nonfinite) *bad = 1;                     // (every writer stores the same value)
+}
+
+// rss: the running sum of squares of (bus, scenario) takes the chunk's fc points in ascending order; sq [n][S] (fresh at f0 = 0)
+__global__ __launch_bounds__(ZS_TPB) void k_pen_fold_sq(int n, int fc, int sc, int f0, int s0, int S, const cplx* __restrict__ r,
+                                                        double* __restrict__ sq) {
+    int i, s;
+    if (!zs_item(n, sc, i, s)) return;
+    const size_t J = (size_t)fc * sc, o = (size_t)i * S + s0 + s;
+    double acc = f0 == 0 ? 0.0 : sq[o];
+    for (int f = 0; f < fc; ++f) acc = acc + pen_sq(r[(size_t)i * J + (size_t)f * sc + s]);
+    sq[o] = acc;
+}
+
+// out [s][f][i] <- r [i][f sc + s] (the chunk's V in the caller's order, [sc][fc][n]): 32 x 32 tiles over (i, s) of one point f through LDS
+__global__ __launch_bounds__(ZS_TILE * 8) void k_pen_copy_out(const cplx* __restrict__ r, int n, int fc, int sc, cplx* __restrict__ out) {
+    __shared__ cplx tile[ZS_TILE][ZS_TILE + 1];
+    const long long ts = (sc + ZS_TILE - 1) / ZS_TILE, ti = (n + ZS_TILE - 1) / ZS_TILE, b = blockIdx.x;
+    const int f = (int)(b / (ti * ts)), i0 = (int)(b % (ti * ts) / ts) * ZS_TILE, s0 = (int)(b % ts) * ZS_TILE;
+    const int tx = threadIdx.x & (ZS_TILE - 1), ty = threadIdx.x / ZS_TILE;
+    const size_t J = (size_t)fc * sc;
+    for (int y = ty; y < ZS_TILE; y += 8)
+        if (i0 + y < n && s0 + tx < sc) tile[y][tx] = r[(size_t)(i0 + y) * J + (size_t)f * sc + (s0 + tx)];
+    __syncthreads();
+    for (int y = ty; y < ZS_TILE; y += 8)
+        if (s0 + y < sc && i0 + tx < n) out[((size_t)(s0 + y) * fc + f) * n + (i0 + tx)] = tile[tx][y];
+}
+
+// the host checks of hpf_penetration beyond the scan's (before any HIP call)
+bool pen_args_ok(int n, int F, int S, int n_inj, const int32_t* inj, const double* I, int chunk_f, int chunk_s) {
+    if (S < 1 || S > PEN_MAX_S || n_inj < 1 || n_inj > n || !inj || !I || chunk_f < 0 || chunk_s < 0 || (long long)S * n > PEN_MAX_SN) return false;
+    std::vector<char> seen((size_t)n, 0);
+    for (int q = 0; q < n_inj; ++q) {
+        if (inj[q] < 0 || inj[q] >= n || seen[inj[q]]) return false;
+        seen[inj[q]] = 1;
+    }
+    return finite_all(I, (size_t)2 * S * F * n_inj);
+}
+
+}  // namespace
+
+extern "C" int hpf_penetration(int device, const hpf_zscan_net* net, int F, const double* h, const double* y_extra, int S, int n_inj,
+                               const int32_t* inj, const double* I, int chunk_f, int chunk_s, double* V, double* rss, double* vmax, int32_t* varg,
+                               double* vsum, double* vsumsq, double* rss_max, int32_t* rss_arg, double* rss_sum, double* rss_sumsq) {
+    if (!zscan_args_ok(net, F, h, y_extra, 0, nullptr, 0, nullptr) || !pen_args_ok(net->n, F, S, n_inj, inj, I, chunk_f, chunk_s)) return HPF_E_ARG;
+    const int n = net->n, nb = net->nb;
+    ZscanPlan P;
+    int r = zscan_plan(n, nb, net->from, net->to, P);
+    if (r != HPF_OK) return r;
+    const int k = (int)P.tie.size(), ncol = 2 * k;
+    std::vector<int> colbus, ta(k), tb(k);
+    std::vector<double> tR(k), tX(k);
+    for (int l = 0; l < k; ++l) {
+        ta[l] = net->from[P.tie[l]], tb[l] = net->to[P.tie[l]];
+        tR[l] = net->R[P.tie[l]], tX[l] = net->X[P.tie[l]];
+        colbus.push_back(ta[l]);
+        colbus.push_back(tb[l]);
+    }
+    std::vector<unsigned char> path((size_t)ncol * n, 0);
+    for (int s = 0; s < ncol; ++s) zscan_mark_path(P, colbus[s], path.data() + (size_t)s * n);
+    const bool want_rss = rss || rss_max || rss_arg || rss_sum || rss_sumsq;
+    // scratch in complex values.  Per frequency point: w, t | Z (the column walks read it) | y_extra and its staging | tie columns | W^-1;
+    // per (point, scenario): r | the staging buffer of I and V | the tie coefficients
+    const size_t stage_rows = std::max<size_t>((size_t)n_inj, V ? n : 0);
+    const size_t per_f = (size_t)2 * n + (k ? n : 0) + (y_extra ? (size_t)2 * n : 0) + (size_t)ncol * n + (size_t)k * k;
+    const size_t per_j = (size_t)n + stage_rows + k;
+    int Fc, Sc;
+    pen_chunks(F, S, chunk_f, chunk_s, per_f, per_j, Fc, Sc);
+    if ((long long)n * Fc * Sc > PEN_MAX_NJ) return HPF_E_ARG;   // (forced lengths only: the automatic ones stay inside the budget)
+
+    if (hipSetDevice(device) != hipSuccess) return HPF_E_HIP;
+    int detail = 0;
+    int *d_parent = nullptr, *d_pbranch = nullptr, *d_child_ptr = nullptr, *d_child = nullptr, *d_inc_ptr = nullptr, *d_inc = nullptr;
+    int *d_nodes = nullptr, *d_colbus = nullptr, *d_ta = nullptr, *d_tb = nullptr, *d_inj = nullptr, *d_varg = nullptr, *d_rarg = nullptr, *d_bad = nullptr;
+    double *d_R = nullptr, *d_X = nullptr, *d_gsh = nullptr, *d_bsh = nullptr, *d_xsh = nullptr, *d_h = nullptr, *d_tR = nullptr, *d_tX = nullptr;
+    double *d_vsum = nullptr, *d_vsumsq = nullptr, *d_sq = nullptr, *d_rsum = nullptr, *d_rsumsq = nullptr;
+    unsigned char* d_path = nullptr;
+    unsigned long long *d_vkey = nullptr, *d_rkey = nullptr;
+    cplx *d_w = nullptr, *d_t = nullptr, *d_Zd = nullptr, *d_yx = nullptr, *d_yst = nullptr, *d_cols = nullptr, *d_Winv = nullptr;
+    cplx *d_r = nullptr, *d_stage = nullptr, *d_coef = nullptr;
+    DevMem ws(&detail);                                  // per-call workspace (declared after the pointers it nulls): gone on every return path
+    auto done = [&](int code) {
+        hipDeviceSynchronize();
+        ws.clear();
+        return code;
+    };
+    const size_t nF = (size_t)n * Fc, Jmax = (size_t)Fc * Sc, Fn = (size_t)F * n;
+    const std::vector<int> injv(inj, inj + n_inj);
+    if ((r = ws.upload(&d_parent, P.parent)) || (r = ws.upload(&d_pbranch, P.pbranch)) || (r = ws.upload(&d_child_ptr, P.child_ptr)) ||
+        (r = ws.upload(&d_child, P.child)) || (r = ws.upload(&d_inc_ptr, P.inc_ptr)) || (r = ws.upload(&d_inc, P.inc)) ||
+        (r = ws.upload(&d_nodes, P.dep_nodes)) || (r = ws.upload(&d_R, net->R, (size_t)nb)) || (r = ws.upload(&d_X, net->X, (size_t)nb)) ||
+        (r = ws.upload(&d_gsh, net->gsh, (size_t)n)) || (r = ws.upload(&d_bsh, net->bsh, (size_t)n)) ||
+        (r = ws.upload(&d_xsh, net->xsh, (size_t)n)) || (r = ws.upload(&d_h, h, (size_t)F)) || (r = ws.upload(&d_inj, injv)) ||
+        (r = ws.alloc(&d_w, nF)) || (r = ws.alloc(&d_t, nF)) || (r = ws.alloc(&d_r, n * Jmax)) || (r = ws.alloc(&d_stage, stage_rows * Jmax)) ||
+        (r = ws.alloc(&d_vkey, Fn)) || (r = ws.alloc(&d_varg, Fn)) || (r = ws.alloc(&d_vsum, Fn)) || (r = ws.alloc(&d_vsumsq, Fn)) ||
+        (r = ws.alloc(&d_bad, (size_t)1)))
+        return done(r);
+    if (y_extra && ((r = ws.alloc(&d_yx, nF)) || (r = ws.alloc(&d_yst, nF)))) return done(r);
+    if (want_rss && ((r = ws.alloc(&d_sq, (size_t)n * S)) || (r = ws.alloc(&d_rkey, (size_t)n)) || (r = ws.alloc(&d_rarg, (size_t)n)) ||
+                     (r = ws.alloc(&d_rsum, (size_t)n)) || (r = ws.alloc(&d_rsumsq, (size_t)n))))
+        return done(r);
+    if (k && ((r = ws.upload(&d_colbus, colbus)) || (r = ws.upload(&d_path, path)) || (r = ws.alloc(&d_cols, (size_t)ncol * nF)) ||
+              (r = ws.alloc(&d_Zd, nF)) || (r = ws.upload(&d_ta, ta)) || (r = ws.upload(&d_tb, tb)) || (r = ws.upload(&d_tR, tR)) ||
+              (r = ws.upload(&d_tX, tX)) || (r = ws.alloc(&d_Winv, (size_t)k * k * Fc)) || (r = ws.alloc(&d_coef, (size_t)k * Jmax))))
+        return done(r);
+
+    const ZscanView Vw{n, d_parent, d_pbranch, d_child_ptr, d_child, d_inc_ptr, d_inc, d_R, d_X, d_gsh, d_bsh, d_xsh};
+    const hipStream_t st = nullptr;
+    auto tiles = [](long long a, long long b) { return (unsigned)(((a + ZS_TILE - 1) / ZS_TILE) * ((b + ZS_TILE - 1) / ZS_TILE)); };
+    if (hipMemsetAsync(d_bad, 0, sizeof(int), st) != hipSuccess) return done(HPF_E_HIP);
+    for (int f0 = 0; f0 < F; f0 += Fc) {
+        const int fc = std::min(Fc, F - f0);             // (the arrays of a short last chunk are [bus][fc])
+        const double* hh = d_h + f0;
+        // the factor of the chunk's points: the scan's kernels
+        if (y_extra) {
+            if (hipMemcpy(d_yst, y_extra + (size_t)2 * f0 * n, sizeof(cplx) * (size_t)fc * n, hipMemcpyHostToDevice) != hipSuccess)
+                return done(HPF_E_HIP);
+            hipLaunchKernelGGL(k_zscan_transpose, dim3(tiles(fc, n)), dim3(ZS_TILE * 8), 0, st, d_yst, (long long)fc, (long long)n, d_yx);
+        }
+        for (int d = P.n_depths - 1; d >= 0; --d) {
+            const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
+            hipLaunchKernelGGL(k_zscan_up, dim3(zs_grid(m, fc)), dim3(ZS_TPB), 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, hh, d_yx, d_w, d_t);
+        }
+        if (k) {
+            for (int d = 0; d < P.n_depths; ++d) {
+                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
+                hipLaunchKernelGGL(k_zscan_down, dim3(zs_grid(m, fc)), dim3(ZS_TPB), 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, d_w, d_t, d_Zd);
+            }
+            hipLaunchKernelGGL(k_zscan_col_walk, dim3(zs_grid(ncol, fc)), dim3(ZS_TPB), 0, st, Vw, d_colbus, ncol, fc, d_t, d_Zd, d_cols);
+            for (int d = 1; d < P.n_depths; ++d) {
+                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
+                hipLaunchKernelGGL(k_zscan_col_fill, dim3(zs_grid(m, fc), ncol), dim3(ZS_TPB), 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, d_path, d_t,
+                                   d_cols);
+            }
+            hipLaunchKernelGGL(k_zscan_tie_winv, dim3(zs_grid(1, fc)), dim3(ZS_TPB), 0, st, k, d_ta, d_tb, d_tR, d_tX, n, fc, hh, d_cols, d_Winv);
+        }
+        for (int s0 = 0; s0 < S; s0 += Sc) {
+            const int sc = std::min(Sc, S - s0);
+            const int J = fc * sc;
+            // I [s0 ..][f0 ..][:] -> stage [sc][fc][n_inj] -> r
+            if (hipMemcpy2D(d_stage, sizeof(cplx) * (size_t)fc * n_inj, I + (size_t)2 * ((size_t)s0 * F + f0) * n_inj, sizeof(cplx) * (size_t)F * n_inj,
+                            sizeof(cplx) * (size_t)fc * n_inj, (size_t)sc, hipMemcpyHostToDevice) != hipSuccess)
+                return done(HPF_E_HIP);
+            if (n_inj < n && hipMemsetAsync(d_r, 0, sizeof(cplx) * (size_t)n * J, st) != hipSuccess) return done(HPF_E_HIP);
+            hipLaunchKernelGGL(k_pen_scatter, dim3((unsigned)fc * tiles(sc, n_inj)), dim3(ZS_TILE * 8), 0, st, d_stage, d_inj, n_inj, fc, sc, d_r);
+            for (int d = P.n_depths - 2; d >= 0; --d) {      // (the deepest depth holds leaves only)
+                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
+                hipLaunchKernelGGL(k_pen_up, dim3(zs_grid(m, J)), dim3(ZS_TPB), 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, sc, d_t, d_r);
+            }
+            for (int d = 0; d < P.n_depths; ++d) {
+                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
+                hipLaunchKernelGGL(k_pen_down, dim3(zs_grid(m, J)), dim3(ZS_TPB), 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, sc, d_w, d_t, d_r);
+            }
+            if (k) {
+                hipLaunchKernelGGL(k_pen_tie_coef, dim3(zs_grid(1, J)), dim3(ZS_TPB), 0, st, k, d_ta, d_tb, fc, sc, d_Winv, d_r, d_coef);
+                hipLaunchKernelGGL(k_pen_tie_fix, dim3(zs_grid(n, J)), dim3(ZS_TPB), 0, st, k, n, fc, sc, d_cols, d_coef, d_r);
+            }
+            const long long rows = (long long)n * fc;
+            hipLaunchKernelGGL(k_pen_fold<false>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, rows, sc, s0, n, fc, f0, d_r, (double*)nullptr,
+                               d_vkey, d_varg, d_vsum, d_vsumsq, d_bad);
+            if (want_rss) hipLaunchKernelGGL(k_pen_fold_sq, dim3(zs_grid(n, sc)), dim3(ZS_TPB), 0, st, n, fc, sc, f0, s0, S, d_r, d_sq);
+            if (V) {
+                hipLaunchKernelGGL(k_pen_copy_out, dim3((unsigned)fc * tiles(n, sc)), dim3(ZS_TILE * 8), 0, st, d_r, n, fc, sc, d_stage);
+                if (hipMemcpy2D(V + (size_t)2 * ((size_t)s0 * F + f0) * n, sizeof(cplx) * (size_t)F * n, d_stage, sizeof(cplx) * (size_t)fc * n,
+                                sizeof(cplx) * (size_t)fc * n, (size_t)sc, hipMemcpyDeviceToHost) != hipSuccess)
+                    return done(HPF_E_HIP);
+            }
+            if (hipGetLastError() != hipSuccess) return done(HPF_E_HIP);
+        }
+    }
+    if (want_rss)
+        hipLaunchKernelGGL(k_pen_fold<true>, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, (long long)n, S, 0, n, 1, 0, (const cplx*)nullptr, d_sq,
+                           d_rkey, d_rarg, d_rsum, d_rsumsq, d_bad);
+    auto fetch = [&](void* dst, const void* src, size_t bytes) { return !dst || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+    auto fetch_max = [&](double* dst, const unsigned long long* src, size_t count) {
+        if (!dst) return true;
+        std::vector<unsigned long long> key(count);
+        if (hipMemcpy(key.data(), src, sizeof(unsigned long long) * count, hipMemcpyDeviceToHost) != hipSuccess) return false;
+        for (size_t q = 0; q < count; ++q) dst[q] = wave_key_value(key[q]);
+        return true;
+    };
+    int bad = 0;
+    if (hipMemcpy(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess || !fetch_max(vmax, d_vkey, Fn) ||
+        !fetch(varg, d_varg, sizeof(int) * Fn) || !fetch(vsum, d_vsum, sizeof(double) * Fn) || !fetch(vsumsq, d_vsumsq, sizeof(double) * Fn))
+        return done(HPF_E_HIP);
+    if (want_rss) {
+        if (!fetch_max(rss_max, d_rkey, (size_t)n) || !fetch(rss_arg, d_rarg, sizeof(int) * n) || !fetch(rss_sum, d_rsum, sizeof(double) * n) ||
+            !fetch(rss_sumsq, d_rsumsq, sizeof(double) * n))
+            return done(HPF_E_HIP);
+        if (rss) {                                       // [n][S] on the device (the scenario fastest) -> the caller's [S][n]
+            std::vector<double> a((size_t)n * S);
+            if (hipMemcpy(a.data(), d_sq, sizeof(double) * a.size(), hipMemcpyDeviceToHost) != hipSuccess) return done(HPF_E_HIP);
+            for (int i = 0; i < n; ++i)
+                for (int s = 0; s < S; ++s) rss[(size_t)s * n + i] = a[(size_t)i * S + s];
+        }
+    }
+    return done(bad ? HPF_E_SINGULAR : HPF_OK);
 }

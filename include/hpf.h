@@ -388,6 +388,34 @@ typedef struct hpf_zscan_net {
 int  hpf_impedance_scan(int device, const hpf_zscan_net* net, int F, const double* h, const double* y_extra, int n_sel, const int32_t* sel,
                         int chunk, double* Z, double* Zt, double* zpeak, int32_t* fpeak);
 
+/* Harmonic penetration ("current injection method"): the bus voltages V(h) = Y(h)^-1 I(h) that S scenarios of injected harmonic currents produce,
+ * over a grid of F REAL harmonic orders h > 0, with statistics over the scenarios.  The reference has no counterpart.  Stateless like
+ * hpf_impedance_scan: no handle; the Newton path is not involved.  net, h, y_extra, Y(h), the spanning tree and the ties are those of
+ * hpf_impedance_scan; the tree factor (w, t, the tie columns, W^-1) is formed once per frequency point by the scan's kernels and shared by all
+ * scenarios, and per (point, scenario) one upward and one downward walk of the tree in complex scalars, plus a rank-k correction for k ties, give
+ * V (csrc/hpf_penetration.hpp states every recurrence with its association).
+ *   inj:     [n_inj] distinct bus indices, 1 <= n_inj <= n: the buses that inject; every other bus injects zero
+ *   I:       [S][F][n_inj] complex (interleaved re, im): the current injected INTO the network at bus inj[q], point f, scenario s
+ *   V:       [S][F][n] complex, may be NULL (statistics only)
+ *   rss:     [S][n] sqrt(sum_f |V|^2) over ALL grid points (leave h = 1 out of the grid for "harmonics only"), may be NULL
+ *   vmax, varg (int32), vsum, vsumsq: [F][n], over the scenarios: the maximum of |V|, |v| = sqrt(re^2 + im^2), the scenario it belongs to (ties to
+ *            the smallest s; a NaN is the maximum), sum_s |V| and sum_s |V|^2 (sequential over ascending s).  Each may be NULL.
+ *   rss_max, rss_arg (int32), rss_sum, rss_sumsq: [n], the same four of rss[s][i] over the scenarios.  Each may be NULL.
+ *   chunk_f, chunk_s: the work is cut into chunks of frequency points (outer loop) and scenarios (inner loop), both ascending, so that the device
+ *            scratch of a chunk (w, t, the tie columns, W^-1, the right-hand sides and the staging buffer) stays under 256 MiB; 0: automatic, > 0
+ *            forces the length.  The carried rss sums [S][n] and the running statistics [F][n] sit outside that budget.  Every output is
+ *            bit-identical for every chunking.
+ * One thread per (bus of the current tree depth, j = f chunk_s + s), the scenario fastest: the right-hand sides live in place as [bus][j], so a
+ * wavefront reads and writes 64 consecutive complex values and one w_i, t_i; one launch per depth and walk; no atomics.  All device memory is
+ * per-call workspace and is released on every return path (hpf_debug_device_memory reads the same before and after).
+ * HPF_E_ARG, checked on the host before any HIP call: everything hpf_impedance_scan rejects for net, F, h and y_extra; S < 1, S > 2^16; n_inj < 1,
+ * n_inj > n; a NULL inj or I; an inj entry outside 0 .. n-1 or one that appears twice; a non-finite entry of I; S n > 2^27; a negative chunk, or
+ * forced chunks with n chunk_f chunk_s > 2^30.  HPF_E_TOPOLOGY exactly as hpf_impedance_scan returns it.  HPF_E_SINGULAR, with the outputs still
+ * written, when any V is not finite. */
+int  hpf_penetration(int device, const hpf_zscan_net* net, int F, const double* h, const double* y_extra, int S, int n_inj, const int32_t* inj,
+                     const double* I, int chunk_f, int chunk_s, double* V, double* rss, double* vmax, int32_t* varg, double* vsum, double* vsumsq,
+                     double* rss_max, int32_t* rss_arg, double* rss_sum, double* rss_sumsq);
+
 /* Start state: warm-start the scenarios of a sweep from one solved case instead of the reference's flat start (HG:174-184) + pf (HG:244-275).  The
  * reference has no counterpart (hpf() always starts flat, HG:511-529).  The scenarios of a Monte-Carlo sweep sit close to each other: from the whole
  * raw state of the feeder solved at its nominal loads the harmonic NR needs 2 - 3 iterations where the flat start needs 20 - 30.

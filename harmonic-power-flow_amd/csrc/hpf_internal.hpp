@@ -288,6 +288,7 @@ struct hpf_handle {
     // distortion accumulator `dist` (hpf_distortion_*, hpf_distortion.hpp).  Entries bus-major like the state: t = i*Hn + q for x of (bus i,
     // harmonic position q), t = n*Hn + i for the THD of bus i; f [3][n*Hn + n], arg [n*Hn + n], over [n*Hn + n] | [n][bins + 1] THD histogram
     bool solve_done = false;          // d_stats / the state belong to a finished hpf_solve of the current batch (hpf_distortion_add)
+    bool stats_valid = false;         // d_stats were written by an hpf_solve of the current batch (hpf_get_stats; a new batch -- set_loads, set_state, start_apply, the queue -- ends it)
     int dist_bins = 0;
     int dist_id_base = 0;             // option "distortion_id_base": hpf_solve_queue adds scenario g of a call under id base + g
     double dist_thd_limit = 0.0, dist_hist_max = 0.0, dist_inv_w = 0.0;

@@ -2096,6 +2096,7 @@ int nr_loop(hpf_handle* h, double thresh, int max_iter, int* n_iter, double* err
     if (!FUND) {
         hipLaunchKernelGGL(k_stats, dim3(S), dim3(TPB), 0, h->stream, h->n, h->Hn, thresh, max_iter, h->d_Vm, h->d_err,
                            h->d_niter, h->d_pivflag, stat_mode_flags(h, h->from_start), h->d_stats);
+        h->stats_valid = true;             // (also where the call goes on to return HPF_E_SINGULAR: its outputs are written)
         std::vector<int> pf(S);
         HIPCHK(hipMemcpyAsync(pf.data(), h->d_pivflag, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -2228,7 +2229,7 @@ int solve_queue_fast(hpf_handle* h, int n_total, const double* P, const double* 
                hipMemcpy(Va, qVa, sizeof(double) * (size_t)n_total * count, hipMemcpyDeviceToHost) != hipSuccess))
         return cleanup(HPF_E_HIP);
     // the handle is left without a defined batch: loads and state have to be set again before the per-batch entry points
-    h->loads_set = h->state_set = h->solve_done = h->from_start = false;
+    h->loads_set = h->state_set = h->solve_done = h->from_start = h->stats_valid = false;
     h->S = 0;
     return cleanup(HPF_OK);
 }
@@ -2447,6 +2448,7 @@ int hpf_set_loads(hpf_handle* h, int n_scen, const double* P, const double* Q) {
     h->mismatch_valid = false;
     h->prev_valid = false;
     h->solve_done = false;
+    h->stats_valid = false;
     return HPF_OK;
 }
 
@@ -2487,9 +2489,12 @@ int hpf_clear_sources(hpf_handle* h) {
         return HPF_OK;
     }
     HIPCHK(hipStreamSynchronize(h->stream));
+    const bool had = h->src_set;                         // (storage alone -- kept by hpf_set_loads, or a registration -- is no source of the batch)
     sources_free(h);
-    h->mismatch_valid = false;
-    h->solve_done = false;
+    if (had) {
+        h->mismatch_valid = false;
+        h->solve_done = false;
+    }
     return HPF_OK;
 }
 
@@ -2533,6 +2538,7 @@ int hpf_set_state(hpf_handle* h, int n_scen, const double* Vm, const double* Va)
     h->mismatch_valid = false;
     h->prev_valid = false;
     h->solve_done = false;
+    h->stats_valid = false;
     return HPF_OK;
 }
 
@@ -2581,9 +2587,9 @@ int hpf_start_set(hpf_handle* h, const double* Vm0, const double* Va0) {
 }
 
 int hpf_start_capture(hpf_handle* h, int scen) {
-    if (!h) return HPF_E_ARG;
+    if (!h || scen < 0) return HPF_E_ARG;
     if (!h->state_set || h->S < 1) return HPF_E_STATE;
-    if (scen < 0 || scen >= h->S) return HPF_E_ARG;
+    if (scen >= h->S) return HPF_E_ARG;
     const int count = h->n * h->Hn;
     int r, bad = 0;
     if ((r = start_alloc(h))) return r;
@@ -2646,6 +2652,7 @@ int hpf_start_apply(hpf_handle* h, int n_scen) {
     h->mismatch_valid = false;
     h->prev_valid = false;
     h->solve_done = false;
+    h->stats_valid = false;
     return HPF_OK;
 }
 
@@ -2669,8 +2676,9 @@ int hpf_mismatch(hpf_handle* h, double* f, double* err) { return mismatch_impl(h
 int hpf_fund_mismatch(hpf_handle* h, double* f, double* err) { return mismatch_impl(h, true, f, err); }
 
 static int jacobian_impl(hpf_handle* h, bool fund, int scen, double* J) {
-    if (!h || !J || scen < 0 || scen >= h->S) return HPF_E_ARG;
-    if (!h->loads_set || !h->state_set) return HPF_E_STATE;
+    if (!h || !J || scen < 0) return HPF_E_ARG;
+    if (!h->loads_set || !h->state_set || h->S < 1) return HPF_E_STATE;
+    if (scen >= h->S) return HPF_E_ARG;
     int r;
     const int Nsys = fund ? h->Nf : h->N;
     if ((r = ensure_dense(h, Nsys))) return r;
@@ -2710,8 +2718,9 @@ static int jcsr_pattern(hpf_handle* h) {
 }
 
 static int jacobian_csr_impl(hpf_handle* h, int scen, int32_t* indptr, int32_t* indices, double* data) {
-    if (!h || !data || scen < 0 || scen >= h->S) return HPF_E_ARG;
-    if (!h->loads_set || !h->state_set) return HPF_E_STATE;
+    if (!h || !data || scen < 0) return HPF_E_ARG;
+    if (!h->loads_set || !h->state_set || h->S < 1) return HPF_E_STATE;
+    if (scen >= h->S) return HPF_E_ARG;
     int r;
     if ((r = jcsr_pattern(h))) return r;
     if (!h->d_jval && (r = h->mem.alloc(&h->d_jval, (size_t)h->jnnz))) return r;      // (each buffer under its own check: a failed second
@@ -2742,12 +2751,13 @@ int hpf_jacobian_csr(hpf_handle* h, int scen, int32_t* indptr, int32_t* indices,
 
 // run fn() with the voltages of option "keep_previous_state" in place of the current ones, then put the current state back
 static int with_previous_state(hpf_handle* h, int scen, const std::function<int()>& fn) {
-    if (!h || scen < 0 || scen >= h->S) return HPF_E_ARG;
-    if (!h->keep_prev || !h->d_Vmp || !h->state_set) return HPF_E_STATE;
+    if (!h || scen < 0) return HPF_E_ARG;
+    if (!h->keep_prev || !h->d_Vmp || !h->loads_set || !h->state_set || h->S < 1 || !h->prev_valid) return HPF_E_STATE;     // (all on the host)
+    if (scen >= h->S) return HPF_E_ARG;
     {   // the kept state exists for scenarios that took at least one Newton step in the last hpf_solve
         int ni = 0;
         HIPCHK(hipMemcpy(&ni, h->d_niter + scen, sizeof(int), hipMemcpyDeviceToHost));
-        if (ni <= 0 || !h->prev_valid) return HPF_E_STATE;
+        if (ni <= 0) return HPF_E_STATE;
     }
     const size_t cnt = (size_t)h->S * h->n * h->Hn;
     // (the swap buffers belong to the handle: no allocation / release per call -- a hipFree right after another handle returned tens of GB to
@@ -2826,7 +2836,7 @@ static int solve_queue_any(hpf_handle* h, int n_total, const double* P, const do
         if (stats && (r = hpf_get_stats(h, stats + g0))) return r;
         if (Vm && (r = hpf_get_state(h, Vm + (size_t)g0 * cnt, Va + (size_t)g0 * cnt))) return r;
     }
-    h->loads_set = h->state_set = h->solve_done = h->from_start = false;   // (as on the queued path: the handle is left without a defined batch)
+    h->loads_set = h->state_set = h->solve_done = h->from_start = h->stats_valid = false;   // (as on the queued path: the handle is left without a defined batch)
     h->S = 0;
     return HPF_OK;
 }
@@ -2855,7 +2865,7 @@ int hpf_iterate(hpf_handle* h, int iters) {
 
 int hpf_get_stats(hpf_handle* h, hpf_stat* stats) {
     if (!h || !stats) return HPF_E_ARG;
-    if (!h->state_set || h->S < 1) return HPF_E_STATE;     // (no batch in the handle, e.g. after hpf_solve_queue)
+    if (!h->state_set || h->S < 1 || !h->stats_valid) return HPF_E_STATE;     // (no batch in the handle, e.g. after hpf_solve_queue, or no hpf_solve of it yet)
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(stats, h->d_stats, sizeof(hpf_stat) * h->S, hipMemcpyDeviceToHost));
     return HPF_OK;
@@ -2863,7 +2873,7 @@ int hpf_get_stats(hpf_handle* h, hpf_stat* stats) {
 
 int hpf_get_stats_dev(hpf_handle* h, void* stats_dev) {
     if (!h || !stats_dev) return HPF_E_ARG;
-    if (!h->state_set || h->S < 1) return HPF_E_STATE;
+    if (!h->state_set || h->S < 1 || !h->stats_valid) return HPF_E_STATE;
     HIPCHK(hipMemcpyAsync(stats_dev, h->d_stats, sizeof(hpf_stat) * h->S, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return HPF_OK;
@@ -3119,7 +3129,8 @@ int hpf_set_option(hpf_handle* h, const char* name, int value) {
     }
     if (!strcmp(name, "block_pivoting")) {          // 1: partial pivoting (wave Gauss-Jordan), 0: static 4x4 blocks on MFMA
         if (value && h->n_ties > 0) return HPF_E_STATE;    // meshed network: the bordered Newton step exists for the static-pivot kernels only
-        h->gj_mode = value ? 0 : 1;
+        if (h->gj_mode != (value ? 0 : 1)) h->mismatch_valid = false;     // (static-pivot steps read the bus-major image d_fb, pivoted ones d_f:
+        h->gj_mode = value ? 0 : 1;                                       //  a mismatch taken in the other mode left only one of them current)
         return HPF_OK;
     }
     if (!strcmp(name, "pivot_growth_limit_log10")) { // static pivot order: amplification limit of a 4x4 pivot block, 10^value

@@ -117,7 +117,19 @@ int  hpf_max_scenarios(const hpf_handle* h);
 int  hpf_tree_levels(const hpf_handle* h);
 int  hpf_tree_depths(const hpf_handle* h);
 
-/* Loads P,Q [S][n] in p.u. (buses.P / buses.Q of HG:197,372).  Sets the active scenario count S. */
+/* Loads P,Q [S][n] in p.u. (buses.P / buses.Q of HG:197,372).  Sets the active scenario count S.
+ * Call order of a batch (tests/handle_contract.py is this paragraph as a table).  hpf_set_loads opens a batch: n_scen outside 1 .. S_max is
+ * HPF_E_ARG and leaves the handle as it was.  A state of the SAME n_scen is kept -- new loads for the state the handle holds, as a sweep's re-solve
+ * uses it, and hpf_stat.flags bit 8 of a state that came from hpf_start_apply stays with it; a state of another n_scen is dropped (hpf_get_state
+ * and every call that needs a state then return HPF_E_STATE until the next hpf_set_state / hpf_start_apply).  Sources, the mismatch, the kept
+ * previous state and the records of the last hpf_solve do not survive hpf_set_loads.  hpf_set_state / hpf_start_apply with loads set take the
+ * loads' n_scen only (HPF_E_ARG otherwise: change the batch size with hpf_set_loads first); they keep loads and sources and end the mismatch, the
+ * previous state and the records.  A call refused by a check on the host (code < 0, before any device work) changes nothing: not the batch, not
+ * hpf_num_scenarios, not an option -- with one exception, hpf_solve_queue refusing a registration of hpf_queue_sources, which drops the
+ * registration.  (hpf_start_capture answering HPF_E_STATE for a scenario with a non-finite or zero entry is no such refusal: its kernel found
+ * the entry while overwriting the start buffers, and the handle is left without a start state, as stated there.)  Where a call could be refused for its
+ * arguments and for the handle's state, the argument ranges that do not depend on the state (n_scen against S_max, an unknown form, a NULL
+ * pointer, scen < 0) come first, then the state, then the arguments that are measured against the batch (n_scen against S, scen >= S). */
 int  hpf_set_loads(hpf_handle* h, int n_scen, const double* P, const double* Q);
 /* Voltages Vm,Va [S][Hn*n] (the V DataFrame of HG:174-184, signed magnitudes allowed).  NULL,NULL -> the reference's
  * initial values (1 p.u. at h=1, 0.1 p.u. above, angle 0; init_voltages HG:174-184) for all S scenarios. */
@@ -132,7 +144,9 @@ int  hpf_mismatch(hpf_handle* h, double* f, double* err);
 int  hpf_jacobian(hpf_handle* h, int scen, double* J_colmajor);
 /* The Jacobian the reference's hpf() returns (HG:537,560): the one of the LAST iteration of the last hpf_solve, i.e. built at the
  * state scenario `scen`'s last Newton step started from (needs option "keep_previous_state" = 1 before hpf_solve; the current state
- * is left untouched). */
+ * is left untouched).  HPF_E_STATE, checked on the host: option off, no batch, no hpf_solve with the option on since the batch's loads and state
+ * were set (hpf_mismatch, hpf_iterate and hpf_fund_pf do not end it: the kept state stays the last hpf_solve's), or a scenario that took no step
+ * in that solve.  The option may be switched off and on again in between: the kept state survives. */
 int  hpf_jacobian_last(hpf_handle* h, int scen, double* J_colmajor);
 /* build_harmonic_jacobian (HG:401-473) in the form the reference returns it from build_harmonic_jacobian and from hpf() (HG:469-472,
  * HG:560): the stacked real matrix [[dP/dth dP/dV] [Re dI/dth Re dI/dV] [dQ/dth dQ/dV] [Im dI/dth Im dI/dV]] as CSR -- indptr [N+1],
@@ -190,7 +204,10 @@ int  hpf_set_trace(hpf_handle* h, double* Vm_traj, double* Va_traj, int cap);
 
 /* One unconditional NR iteration (Jacobian -> solve -> update -> mismatch) for all S scenarios, repeated `iters`
  * times, no host synchronisation inside (throughput measurement; update_harmonic_state_vec HG:476-479 +
- * update_harmonic_voltages HG:482-485).  Requires a valid mismatch (hpf_mismatch or hpf_solve first). */
+ * update_harmonic_voltages HG:482-485).  Requires a valid mismatch: hpf_mismatch after the last call that set loads, sources or state and after
+ * the last hpf_solve / hpf_fund_pf (scenarios those froze hold stale mismatch rows); HPF_E_STATE otherwise.  hpf_iterate itself leaves the
+ * mismatch valid.  It ends "hpf_solve was the last call that touched the batch" for the accumulators' add; the records of hpf_get_stats stay
+ * those of the last hpf_solve. */
 int  hpf_iterate(hpf_handle* h, int iters);
 
 /* update_harmonic_state_vec (HG:476-479) as a standalone, stateless call like the reference's: dx = J^-1 f for a dense
@@ -215,14 +232,17 @@ int  hpf_dense_solve(int device, int N, const double* J_colmajor, const double* 
 int  hpf_sparse_solve(int device, int n, int c, int Hn, const int32_t* indptr, const int32_t* indices, const double* data, const double* f,
                       double* dx);
 
-/* Per-scenario statistics after hpf_solve; `thd_max` from get_THD (HG:563-572) evaluated on device. */
+/* Per-scenario statistics after hpf_solve; `thd_max` from get_THD (HG:563-572) evaluated on device.  The records are those of the last hpf_solve
+ * of the CURRENT batch (an hpf_solve that returned HPF_E_SINGULAR included: its outputs are written): HPF_E_STATE without a batch, and after
+ * hpf_set_loads / hpf_set_state / hpf_start_apply until the next hpf_solve -- never the records of an earlier batch.  hpf_mismatch, hpf_iterate,
+ * hpf_fund_pf and the source calls leave them as they are. */
 int  hpf_get_stats(hpf_handle* h, hpf_stat* stats /* [S] host */);
 int  hpf_get_stats_dev(hpf_handle* h, void* stats_dev /* [S] hpf_stat, device memory of the caller (RCCL gather) */);
 
 /* Residual check of the Newton steps (option "step_residual_check"): eta_last [S] the normwise backward error
  * eta = |f - J dx|_inf / (| |J| |_inf |dx|_inf + |f|_inf) of every scenario's last harmonic Newton step, eta_max [S] the largest one since
  * hpf_solve was entered (since hpf_set_state for hpf_iterate; after a pivoted repeat: of the repeat).  NaN for a scenario that took no step.
- * Either array may be NULL.  HPF_E_STATE without a batch or with the check off. */
+ * Either array may be NULL.  HPF_E_STATE with the check off or without a state (no batch, or loads alone). */
 int  hpf_get_step_residuals(hpf_handle* h, double* eta_last, double* eta_max);
 
 /* Distortion accumulator: per-bus / per-harmonic statistics of a sweep, accumulated on the device (the reference's counterpart is a loop of hpf() calls
@@ -467,7 +487,8 @@ int  hpf_start_apply(hpf_handle* h, int n_scen);
  * hpf_get_sources: the I_src the device holds for the batch, [S][n - m][Hn] complex (after form 1: the expanded currents).  HPF_E_STATE when the
  *   batch has none (never set, cleared, or dropped by hpf_set_loads).
  * hpf_clear_sources: the batch goes back to the model's I_N; frees the storage and a pending registration (HPF_OK when there is none); hpf_destroy
- *   frees them too.
+ *   frees them too.  On a batch WITH sources it ends the mismatch and "hpf_solve was the last call" like hpf_set_sources does; on a batch without
+ *   (never set, or dropped by hpf_set_loads) it changes nothing of the batch, whatever storage it frees.
  * hpf_queue_sources: the sources of a whole sweep of n_total scenarios (same forms, [n_total][...]), uploaded to HBM and consumed by the NEXT
  *   hpf_solve_queue.  If that call's n_total differs it returns HPF_E_ARG, the registration is dropped and nothing is solved.  Radial BLOCK_TREE
  *   handles move a scenario's sources into its storage with its loads (k_source_gather / k_source_expand next to k_queue_init); the wave handles
@@ -502,7 +523,8 @@ int  hpf_debug_device_memory(int64_t* blocks, int64_t* bytes);
  * a static pivot order (4x4 blocks = two harmonics, lane-parallel cofactor inverse), after contracting pass-through buses and
  * with per-model constant inverses for nonlinear leaf buses; 1 uses wave-level Gauss-Jordan with partial pivoting over the
  * whole block on the uncontracted tree (slower, for networks whose bus blocks are not block-diagonally dominant).  Env
- * HPF_GJ_MODE=0 selects the pivoted variant process-wide.
+ * HPF_GJ_MODE=0 selects the pivoted variant process-wide.  Changing the value ends a valid mismatch (the two variants read it in different
+ * layouts): hpf_mismatch again before hpf_iterate.  Meshed handles: 1 is refused with HPF_E_STATE.
  * "pivot_growth_limit_log10" (0..300, default 10): the static-pivot monitor flags a scenario when |a_ij W_ji| of a pivot block
  * (a lower bound of its condition number) exceeds 10^value; "auto_repivot" (default 1): hpf_solve repeats flagged scenarios
  * with partial pivoting (0: they are only reported in hpf_stat.flags).

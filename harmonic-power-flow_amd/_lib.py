@@ -106,7 +106,9 @@ SYMBOLS = {
                                      c_dbl_p, c_int_p]),
     "hpf_penetration": (C.c_int, [C.c_int, C.POINTER(hpf_zscan_net), C.c_int, c_dbl_p, c_dbl_p, C.c_int, C.c_int, c_int_p, c_dbl_p, C.c_int, C.c_int,
                                   c_dbl_p, c_dbl_p, c_dbl_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p, c_int_p, c_dbl_p, c_dbl_p]),
-    "hpf_solve_flops": (C.c_double, [_H]),
+    "hpf_resonance_modes": (C.c_int, [C.c_int, C.POINTER(hpf_zscan_net), C.c_int, c_dbl_p, c_dbl_p, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_int_p,
+                                      c_dbl_p]),
+    "hpf_solve_flops":(C.c_double, [_H]),
     "hpf_solve_bytes": (C.c_double, [_H]),
     "hpf_back_bytes": (C.c_double, [_H]),
     "hpf_kernel_model": (C.c_int, [_H, C.c_int, c_dbl_p, c_dbl_p, c_int_p]),

@@ -785,6 +785,89 @@ def penetration(buses, lines, h, currents, at=None, shunts=None, capacitors=None
     return Penetration(h, I.shape[0], out, ids, [ids[i] for i in inj])
 
 
+class ResonanceModes:
+    """Result of `resonance_modes`: h [F] the grid; per grid point lam [F] complex the eigenvalue of Y(h) of smallest modulus, zm [F] its modal
+    impedance 1 / |lam|, residual [F] the relative residual of the returned eigenpair, top [F] the 1-based ID of the bus with the largest
+    participation; pf [F][n] complex participation factors (sum over the buses = 1; None with full=False).  bus_ids: the IDs of the n columns."""
+
+    def __init__(self, h, out, bus_ids):
+        self.h, self.bus_ids = h, bus_ids
+        self.lam, self.zm, self.residual, self.pf = out["lam"], out["zm"], out["res"], out["pf"]
+        self.top = np.array(bus_ids)[out["top"]]
+
+    def converged(self, tol=1e-8):
+        """Mask [F] of the grid points whose eigenpair is resolved: residual <= tol (a NaN is not).  32 steps leave 2e-10 or less where the two
+        smallest eigenvalues are a factor of two apart; a point where two modes cross stays above any tolerance."""
+        return self.residual <= tol
+
+    def modes(self, prominence=0.0, tol=1e-8):
+        """The resonances of the network: the strict local maxima of zm along the grid among the converged points, on the host -> DataFrame
+        (index = grid index; h, zm, top = the bus ID of the largest participation, pf_top = its |pf|, bus1 .. bus5 = the IDs of the five buses of
+        largest |pf|, descending; prominence).  Prominence as in ImpedanceScan.resonances: (peak - base) / peak, base = the larger of the two minima
+        of zm between the maximum and the nearest higher converged point on either side (or the end of the grid); maxima below `prominence` are
+        left out."""
+        if self.pf is None:
+            raise ValueError("modes needs the participation factors (full=True)")
+        idx = np.nonzero(self.converged(tol))[0]
+        a = self.zm[idx]
+        nb = min(5, len(self.bus_ids))
+        rows = []
+        for q in range(1, len(a) - 1):
+            if not (a[q] > a[q - 1] and a[q] > a[q + 1]):
+                continue
+            base = 0.0
+            for side in (a[:q][::-1], a[q + 1:]):
+                higher = np.nonzero(side > a[q])[0]
+                base = max(base, float(side[:higher[0]].min() if len(higher) else side.min()))
+            prom = (a[q] - base) / a[q]
+            if prom >= prominence:
+                f = int(idx[q])
+                mag = np.abs(self.pf[f])
+                order = np.argsort(-mag, kind="stable")[:nb]
+                rows.append((f, self.h[f], a[q], int(self.top[f]), float(mag[self.bus_ids.index(int(self.top[f]))])) +
+                            tuple(self.bus_ids[i] for i in order) + (prom,))
+        cols = ["h", "zm", "top", "pf_top"] + ["bus%d" % (j + 1) for j in range(nb)] + ["prominence"]
+        return pd.DataFrame([r[1:] for r in rows], index=pd.Index([r[0] for r in rows], name="index"), columns=cols)
+
+
+RESONANCE_OUTPUTS = ("lam", "zm", "res", "top", "pf")
+
+
+def resonance_modes_arrays(model, h, y_extra=None, iters=32, chunk=0, full=True, device=0):
+    """hpf_resonance_modes on the arrays of `admittance.line_model`: h [F] real orders, y_extra [F][n] complex or None, iters steps of inverse
+    iteration -> (code, lam, zm, res, top (0-based), pf or None); code 0 or 3 (HPF_E_SINGULAR: the outputs are written), any other code raises."""
+    lib = _lib.load()
+    n, F = int(model["n"]), len(h)
+    h = np.ascontiguousarray(h, dtype=np.float64)
+    arr = {k: np.ascontiguousarray(model[k], dtype=np.int32 if k in ("fr", "to") else np.float64) for k in ("fr", "to", "R", "X", "gsh", "bsh", "xsh")}
+    ip, dp = _lib.c_int_p, _lib.c_dbl_p
+    net = _lib.hpf_zscan_net(n, int(model["nb"]), arr["fr"].ctypes.data_as(ip), arr["to"].ctypes.data_as(ip),
+                             *[arr[k].ctypes.data_as(dp) for k in ("R", "X", "gsh", "bsh", "xsh")])
+    yx = None if y_extra is None else np.ascontiguousarray(y_extra, dtype=np.complex128)
+    if yx is not None and yx.shape != (F, n):
+        raise ValueError("y_extra must be [F][n]")
+    lam, zm, res, top = np.empty(F, dtype=np.complex128), np.empty(F), np.empty(F), np.empty(F, dtype=np.int32)
+    pf = np.empty((F, n), dtype=np.complex128) if full else None
+    rc = lib.hpf_resonance_modes(int(device), C.byref(net), F, h.ctypes.data_as(dp), None if yx is None else yx.ctypes.data_as(dp), int(iters),
+                                 int(chunk), lam.ctypes.data_as(dp), zm.ctypes.data_as(dp), res.ctypes.data_as(dp), top.ctypes.data_as(ip),
+                                 None if pf is None else pf.ctypes.data_as(dp))
+    if rc not in (0, 3):
+        raise _lib.HpfError(rc, 0, "hpf_resonance_modes")
+    return rc, lam, zm, res, top, pf
+
+
+def resonance_modes(buses, lines, h, shunts=None, capacitors=None, iters=32, full=True, device=0, settings=None, ne_dir=None, coupled=True):
+    """Resonance mode analysis on the GPU (not in the reference): at every point of the grid `h` of real harmonic orders > 0 the critical mode of
+    the network -- the eigenvalue of Y(h) of smallest modulus, its modal impedance 1 / |lambda| and the participation factors of the buses
+    -> ResonanceModes.  Where impedance_scan shows a peak in many |Z_ii| at once, this says that they are one mode and which buses excite and
+    observe it most (where a filter has to go).  The network, `shunts` and `capacitors` are those of impedance_scan.  `iters` (1 .. 256) steps of
+    inverse iteration run at every point, nothing is adapted: ResonanceModes.converged tells the resolved points (two modes that cross at a grid
+    point are not); only the critical mode of a point is returned.  A grid point at which Y(h) is singular leaves inf / NaN in the result."""
+    model, h, ids, yx = _scan_network(buses, lines, h, shunts, capacitors, settings, ne_dir, coupled)
+    _, lam, zm, res, top, pf = resonance_modes_arrays(model, h, yx, iters, 0, full, device)
+    return ResonanceModes(h, dict(lam=lam, zm=zm, res=res, top=top, pf=pf), ids)
+
+
 def solve(filename_buses, filename_lines, coupled=True, settings=None, ne_dir=None, solver="auto", verbose=False, extra_iters=0,
           check_steps=False, line_flows=False, update="polar", sources=None, waveforms=False):
     """Convenience wrapper (= init_network + hpf + get_THD) -> dict(V, err_h, n_iter_h, THD, details).  check_steps, update, sources: see hpf.

@@ -1,12 +1,14 @@
 // hpf_impedance_scan: driving-point and transfer impedances over a grid of harmonic orders (hpf_zscan.hpp has the arithmetic and the planner;
 // include/hpf.h the contract).  Every kernel maps a thread to (item, frequency point) with the frequency fastest: block b of a launch over m items
 // serves item b / fb, points (b % fb) * ZS_TPB + threadIdx.x, fb = ceil(Fc / ZS_TPB) -- a one-dimensional grid, so that the widest depth of a large
-// star still fits; the host keeps n * fb <= 2^30.  hpf_penetration (below, hpf_penetration.hpp) shares the factor kernels of the scan.
+// star still fits; the host keeps n * fb <= 2^30.  hpf_penetration (below, hpf_penetration.hpp) shares the factor kernels of the scan, and
+// hpf_resonance_modes (last, hpf_resonance.hpp) those and the penetration's walks.
 #include <algorithm>
 #include <utility>
 
 #include "hpf_internal.hpp"
 #include "hpf_penetration.hpp"
+#include "hpf_resonance.hpp"
 #include "hpf_zscan.hpp"
 
 using namespace hpf;
@@ -600,5 +602,252 @@ extern "C" int hpf_penetration(int device, const hpf_zscan_net* net, int F, cons
                 for (int s = 0; s < S; ++s) rss[(size_t)s * n + i] = a[(size_t)i * S + s];
         }
     }
+    return done(bad ? HPF_E_SINGULAR : HPF_OK);
+}
+
+// ---- hpf_resonance_modes -----------------------------------------------------------------------------------------------------------------------
+// The critical mode of Y(h) per frequency point by inverse iteration (hpf_resonance.hpp has the arithmetic; include/hpf.h the contract).  The factor
+// of a chunk comes from the scan's kernels, y = Y^-1 x from the penetration's walks with sc = 1 (r = y [n][fc], in place); the kernels below are the
+// loop around them.  x, y and pf are [bus][fc], the partial keys and sums [tile][fc], the per-point values [fc]: a wavefront reads 64 consecutive
+// values everywhere.  No atomics: every reduction over the buses is a partial per tile of RMA_TILE buses and then one thread per point over the tiles.
+namespace {
+
+// x = y = the start vector
+__global__ __launch_bounds__(ZS_TPB) void k_rma_start(int n, int fc, cplx* __restrict__ x, cplx* __restrict__ y) {
+    int i, f;
+    if (!zs_item(n, fc, i, f)) return;
+    const size_t o = (size_t)i * fc + f;
+    x[o] = y[o] = rma_start(i, n);
+}
+
+// the pivot of every point.  STAGE 0: the partial key of (tile, point) -> pkey, parg [tiles][fc]; STAGE 1: over the tiles -> piv [fc], yp [fc] = y_p
+template <int STAGE>
+__global__ __launch_bounds__(ZS_TPB) void k_rma_pivot(int n, int fc, const cplx* __restrict__ y, unsigned long long* __restrict__ pkey,
+                                                      int* __restrict__ parg, int* __restrict__ piv, cplx* __restrict__ yp) {
+    int T, f;
+    if (!zs_item(STAGE == 0 ? rma_tiles(n) : 1, fc, T, f)) return;
+    uint64_t key;
+    int arg;
+    if (STAGE == 0) {
+        rma_tile_peak(y, n, (size_t)fc, (size_t)f, T, key, arg);
+        pkey[(size_t)T * fc + f] = key;
+        parg[(size_t)T * fc + f] = arg;
+    } else {
+        rma_peak_fold((const uint64_t*)pkey, parg, rma_tiles(n), (size_t)fc, (size_t)f, key, arg);
+        piv[f] = arg;
+        yp[f] = y[(size_t)arg * fc + f];
+    }
+}
+
+// x = y = y / y_p (yp [fc] is the pivot kernel's copy: y_p itself is overwritten here)
+__global__ __launch_bounds__(ZS_TPB) void k_rma_scale(int n, int fc, const cplx* __restrict__ yp, cplx* __restrict__ x, cplx* __restrict__ y) {
+    int i, f;
+    if (!zs_item(n, fc, i, f)) return;
+    const size_t o = (size_t)i * fc + f;
+    x[o] = y[o] = rma_scale(y[o], yp[f]);
+}
+
+// the three bilinear sums.  STAGE 0: the tile sums -> part [3][tiles][fc]; STAGE 1: the ordered fold over the tiles -> sums [3][fc]
+template <int STAGE>
+__global__ __launch_bounds__(ZS_TPB) void k_rma_sums(int n, int fc, const cplx* __restrict__ x, const cplx* __restrict__ y, cplx* __restrict__ part,
+                                                     cplx* __restrict__ sums) {
+    int T, f;
+    const int tiles = rma_tiles(n);
+    if (!zs_item(STAGE == 0 ? tiles : 1, fc, T, f)) return;
+    const size_t q = (size_t)tiles * fc;
+    if (STAGE == 0) {
+        cplx a, b, g;
+        rma_tile_sums(x, y, n, (size_t)fc, (size_t)f, T, a, b, g);
+        part[(size_t)T * fc + f] = a;
+        part[q + (size_t)T * fc + f] = b;
+        part[2 * q + (size_t)T * fc + f] = g;
+    } else {
+        for (int s = 0; s < 3; ++s) sums[(size_t)s * fc + f] = rma_sum_fold(part + s * q, tiles, (size_t)fc, (size_t)f);
+    }
+}
+
+// the eigenpair, the participation factors and the residual.
+//   STAGE 0 (one thread per point): lambda, zm and 1 / g from the sums -> lam, zr [fc] (.re = zm), ginv [fc]
+//   STAGE 1 (per tile and point):   pf_i of the tile's buses -> pf [n][fc] (when wanted), the partial key of the largest defect -> pkey, parg;
+//                                   *bad = 1 for a non-finite pf
+//   STAGE 2 (per point):            res from the largest defect -> zr (.im = res); *bad = 1 for a non-finite lambda, zm or res
+template <int STAGE>
+__global__ __launch_bounds__(ZS_TPB) void k_rma_finish(int n, int fc, const cplx* __restrict__ x, const cplx* __restrict__ y,
+                                                       const cplx* __restrict__ sums, const cplx* __restrict__ yp, cplx* __restrict__ lam,
+                                                       cplx* __restrict__ zr, cplx* __restrict__ ginv, cplx* __restrict__ pf,
+                                                       unsigned long long* __restrict__ pkey, int* __restrict__ parg, int* __restrict__ bad) {
+    int T, f;
+    const int tiles = rma_tiles(n);
+    if (!zs_item(STAGE == 1 ? tiles : 1, fc, T, f)) return;
+    if (STAGE == 0) {
+        cplx l, gi;
+        double zm;
+        rma_eig(sums[f], sums[(size_t)fc + f], sums[(size_t)2 * fc + f], l, zm, gi);
+        lam[f] = l;
+        ginv[f] = gi;
+        zr[f] = {zm, 0.0};
+    } else if (STAGE == 1) {
+        const cplx l = lam[f], gi = ginv[f];
+        uint64_t key = 0;
+        int arg = RMA_NO_BUS, nonfinite = 0;
+        const int i1 = (T + 1) * RMA_TILE < n ? (T + 1) * RMA_TILE : n;
+        for (int i = T * RMA_TILE; i < i1; ++i) {
+            const size_t o = (size_t)i * fc + f;
+            const cplx yi = y[o], p = rma_pf(yi, gi);
+            nonfinite |= !zscan_finite(p);
+            if (pf) pf[o] = p;
+            wave_peak_combine(key, arg, wave_key(rma_defect(x[o], l, yi)), i);
+        }
+        pkey[(size_t)T * fc + f] = key;
+        parg[(size_t)T * fc + f] = arg;
+        if (nonfinite) *bad = 1;                         // (every writer stores the same value)
+    } else {
+        uint64_t key;
+        int arg;
+        rma_peak_fold((const uint64_t*)pkey, parg, tiles, (size_t)fc, (size_t)f, key, arg);
+        const cplx l = lam[f];
+        const double zm = zr[f].re, res = rma_res(key, l, yp[f]);
+        zr[f].im = res;
+        if (!zscan_finite(l) || !rma_finite(zm) || !rma_finite(res)) *bad = 1;
+    }
+}
+
+}  // namespace
+
+extern "C" int hpf_resonance_modes(int device, const hpf_zscan_net* net, int F, const double* h, const double* y_extra, int iters, int chunk,
+                                   double* lam, double* zm, double* res, int32_t* top, double* pf) {
+    if (!zscan_args_ok(net, F, h, y_extra, 0, nullptr, chunk, nullptr) || iters < 1 || iters > RMA_MAX_ITERS) return HPF_E_ARG;
+    const int n = net->n, nb = net->nb;
+    ZscanPlan P;
+    int r = zscan_plan(n, nb, net->from, net->to, P);
+    if (r != HPF_OK) return r;
+    const int k = (int)P.tie.size(), ncol = 2 * k, tiles = rma_tiles(n);
+    std::vector<int> colbus, ta(k), tb(k);
+    std::vector<double> tR(k), tX(k);
+    for (int l = 0; l < k; ++l) {
+        ta[l] = net->from[P.tie[l]], tb[l] = net->to[P.tie[l]];
+        tR[l] = net->R[P.tie[l]], tX[l] = net->X[P.tie[l]];
+        colbus.push_back(ta[l]);
+        colbus.push_back(tb[l]);
+    }
+    std::vector<unsigned char> path((size_t)ncol * n, 0);
+    for (int s = 0; s < ncol; ++s) zscan_mark_path(P, colbus[s], path.data() + (size_t)s * n);
+    int Fc = zscan_chunk(F, chunk, rma_per_f(n, k, y_extra != nullptr, pf != nullptr));
+    const long long fb_max = (1ll << 30) / n;            // blocks of ZS_TPB points a launch over n buses may have
+    if ((Fc + ZS_TPB - 1) / ZS_TPB > fb_max) {
+        if (chunk > 0) return HPF_E_ARG;
+        Fc = (int)fb_max * ZS_TPB;
+    }
+
+    if (hipSetDevice(device) != hipSuccess) return HPF_E_HIP;
+    int detail = 0;
+    int *d_parent = nullptr, *d_pbranch = nullptr, *d_child_ptr = nullptr, *d_child = nullptr, *d_inc_ptr = nullptr, *d_inc = nullptr;
+    int *d_nodes = nullptr, *d_colbus = nullptr, *d_ta = nullptr, *d_tb = nullptr, *d_parg = nullptr, *d_piv = nullptr, *d_bad = nullptr;
+    double *d_R = nullptr, *d_X = nullptr, *d_gsh = nullptr, *d_bsh = nullptr, *d_xsh = nullptr, *d_h = nullptr, *d_tR = nullptr, *d_tX = nullptr;
+    unsigned char* d_path = nullptr;
+    unsigned long long* d_pkey = nullptr;
+    cplx *d_w = nullptr, *d_t = nullptr, *d_Zd = nullptr, *d_yx = nullptr, *d_cols = nullptr, *d_Winv = nullptr, *d_coef = nullptr, *d_stage = nullptr;
+    cplx *d_x = nullptr, *d_y = nullptr, *d_pf = nullptr, *d_part = nullptr, *d_sums = nullptr, *d_yp = nullptr, *d_lam = nullptr, *d_zr = nullptr;
+    cplx* d_ginv = nullptr;
+    DevMem ws(&detail);                                  // per-call workspace (declared after the pointers it nulls): gone on every return path
+    auto done = [&](int code) {
+        hipDeviceSynchronize();
+        ws.clear();
+        return code;
+    };
+    const size_t nF = (size_t)n * Fc, tF = (size_t)tiles * Fc;
+    if ((r = ws.upload(&d_parent, P.parent)) || (r = ws.upload(&d_pbranch, P.pbranch)) || (r = ws.upload(&d_child_ptr, P.child_ptr)) ||
+        (r = ws.upload(&d_child, P.child)) || (r = ws.upload(&d_inc_ptr, P.inc_ptr)) || (r = ws.upload(&d_inc, P.inc)) ||
+        (r = ws.upload(&d_nodes, P.dep_nodes)) || (r = ws.upload(&d_R, net->R, (size_t)nb)) || (r = ws.upload(&d_X, net->X, (size_t)nb)) ||
+        (r = ws.upload(&d_gsh, net->gsh, (size_t)n)) || (r = ws.upload(&d_bsh, net->bsh, (size_t)n)) ||
+        (r = ws.upload(&d_xsh, net->xsh, (size_t)n)) || (r = ws.upload(&d_h, h, (size_t)F)) || (r = ws.alloc(&d_w, nF)) ||
+        (r = ws.alloc(&d_t, nF)) || (r = ws.alloc(&d_x, nF)) || (r = ws.alloc(&d_y, nF)) || (r = ws.alloc(&d_pkey, tF)) ||
+        (r = ws.alloc(&d_parg, tF)) || (r = ws.alloc(&d_part, 3 * tF)) || (r = ws.alloc(&d_sums, (size_t)3 * Fc)) ||
+        (r = ws.alloc(&d_piv, (size_t)Fc)) || (r = ws.alloc(&d_yp, (size_t)Fc)) || (r = ws.alloc(&d_lam, (size_t)Fc)) ||
+        (r = ws.alloc(&d_zr, (size_t)Fc)) || (r = ws.alloc(&d_ginv, (size_t)Fc)) || (r = ws.alloc(&d_bad, (size_t)1)))
+        return done(r);
+    if (y_extra && (r = ws.alloc(&d_yx, nF))) return done(r);
+    if (pf && (r = ws.alloc(&d_pf, nF))) return done(r);
+    if ((y_extra || pf) && (r = ws.alloc(&d_stage, nF))) return done(r);
+    if (k && ((r = ws.upload(&d_colbus, colbus)) || (r = ws.upload(&d_path, path)) || (r = ws.alloc(&d_cols, (size_t)ncol * nF)) ||
+              (r = ws.alloc(&d_Zd, nF)) || (r = ws.upload(&d_ta, ta)) || (r = ws.upload(&d_tb, tb)) || (r = ws.upload(&d_tR, tR)) ||
+              (r = ws.upload(&d_tX, tX)) || (r = ws.alloc(&d_Winv, (size_t)k * k * Fc)) || (r = ws.alloc(&d_coef, (size_t)k * Fc))))
+        return done(r);
+
+    const ZscanView Vw{n, d_parent, d_pbranch, d_child_ptr, d_child, d_inc_ptr, d_inc, d_R, d_X, d_gsh, d_bsh, d_xsh};
+    const hipStream_t st = nullptr;
+    auto transpose = [&](const cplx* in, long long R, long long C, cplx* out) {
+        const long long t2 = ((R + ZS_TILE - 1) / ZS_TILE) * ((C + ZS_TILE - 1) / ZS_TILE);
+        hipLaunchKernelGGL(k_zscan_transpose, dim3((unsigned)t2), dim3(ZS_TILE * 8), 0, st, in, R, C, out);
+    };
+    std::vector<cplx> hl((size_t)Fc), hz((size_t)Fc);
+    if (hipMemsetAsync(d_bad, 0, sizeof(int), st) != hipSuccess) return done(HPF_E_HIP);
+    for (int f0 = 0; f0 < F; f0 += Fc) {
+        const int fc = std::min(Fc, F - f0);             // (the arrays of a short last chunk are [bus][fc])
+        const double* hh = d_h + f0;
+        const dim3 g_n(zs_grid(n, fc)), g_t(zs_grid(tiles, fc)), g_1(zs_grid(1, fc)), tpb(ZS_TPB);
+        // the factor of the chunk's points: the scan's kernels
+        if (y_extra) {
+            if (hipMemcpy(d_stage, y_extra + (size_t)2 * f0 * n, sizeof(cplx) * (size_t)fc * n, hipMemcpyHostToDevice) != hipSuccess)
+                return done(HPF_E_HIP);
+            transpose(d_stage, fc, n, d_yx);
+        }
+        for (int d = P.n_depths - 1; d >= 0; --d) {
+            const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
+            hipLaunchKernelGGL(k_zscan_up, dim3(zs_grid(m, fc)), tpb, 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, hh, d_yx, d_w, d_t);
+        }
+        if (k) {
+            for (int d = 0; d < P.n_depths; ++d) {
+                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
+                hipLaunchKernelGGL(k_zscan_down, dim3(zs_grid(m, fc)), tpb, 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, d_w, d_t, d_Zd);
+            }
+            hipLaunchKernelGGL(k_zscan_col_walk, dim3(zs_grid(ncol, fc)), tpb, 0, st, Vw, d_colbus, ncol, fc, d_t, d_Zd, d_cols);
+            for (int d = 1; d < P.n_depths; ++d) {
+                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
+                hipLaunchKernelGGL(k_zscan_col_fill, dim3(zs_grid(m, fc), ncol), tpb, 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, d_path, d_t, d_cols);
+            }
+            hipLaunchKernelGGL(k_zscan_tie_winv, g_1, tpb, 0, st, k, d_ta, d_tb, d_tR, d_tX, n, fc, hh, d_cols, d_Winv);
+        }
+        // inverse iteration: y = Y^-1 x by the penetration's walks with one scenario, the pivot, the scaling
+        hipLaunchKernelGGL(k_rma_start, g_n, tpb, 0, st, n, fc, d_x, d_y);
+        for (int it = 1; it <= iters; ++it) {
+            for (int d = P.n_depths - 2; d >= 0; --d) {      // (the deepest depth holds leaves only)
+                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
+                hipLaunchKernelGGL(k_pen_up, dim3(zs_grid(m, fc)), tpb, 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, 1, d_t, d_y);
+            }
+            for (int d = 0; d < P.n_depths; ++d) {
+                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
+                hipLaunchKernelGGL(k_pen_down, dim3(zs_grid(m, fc)), tpb, 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, 1, d_w, d_t, d_y);
+            }
+            if (k) {
+                hipLaunchKernelGGL(k_pen_tie_coef, g_1, tpb, 0, st, k, d_ta, d_tb, fc, 1, d_Winv, d_y, d_coef);
+                hipLaunchKernelGGL(k_pen_tie_fix, g_n, tpb, 0, st, k, n, fc, 1, d_cols, d_coef, d_y);
+            }
+            hipLaunchKernelGGL(k_rma_pivot<0>, g_t, tpb, 0, st, n, fc, d_y, d_pkey, d_parg, d_piv, d_yp);
+            hipLaunchKernelGGL(k_rma_pivot<1>, g_1, tpb, 0, st, n, fc, d_y, d_pkey, d_parg, d_piv, d_yp);
+            if (it < iters) hipLaunchKernelGGL(k_rma_scale, g_n, tpb, 0, st, n, fc, d_yp, d_x, d_y);
+        }
+        hipLaunchKernelGGL(k_rma_sums<0>, g_t, tpb, 0, st, n, fc, d_x, d_y, d_part, d_sums);
+        hipLaunchKernelGGL(k_rma_sums<1>, g_1, tpb, 0, st, n, fc, d_x, d_y, d_part, d_sums);
+        hipLaunchKernelGGL(k_rma_finish<0>, g_1, tpb, 0, st, n, fc, d_x, d_y, d_sums, d_yp, d_lam, d_zr, d_ginv, d_pf, d_pkey, d_parg, d_bad);
+        hipLaunchKernelGGL(k_rma_finish<1>, g_t, tpb, 0, st, n, fc, d_x, d_y, d_sums, d_yp, d_lam, d_zr, d_ginv, d_pf, d_pkey, d_parg, d_bad);
+        hipLaunchKernelGGL(k_rma_finish<2>, g_1, tpb, 0, st, n, fc, d_x, d_y, d_sums, d_yp, d_lam, d_zr, d_ginv, d_pf, d_pkey, d_parg, d_bad);
+        if (pf) {
+            transpose(d_pf, n, fc, d_stage);
+            if (hipMemcpy(pf + (size_t)2 * f0 * n, d_stage, sizeof(cplx) * (size_t)fc * n, hipMemcpyDeviceToHost) != hipSuccess) return done(HPF_E_HIP);
+        }
+        if (hipMemcpy(hl.data(), d_lam, sizeof(cplx) * fc, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(hz.data(), d_zr, sizeof(cplx) * fc, hipMemcpyDeviceToHost) != hipSuccess ||
+            (top && hipMemcpy(top + f0, d_piv, sizeof(int) * fc, hipMemcpyDeviceToHost) != hipSuccess))
+            return done(HPF_E_HIP);
+        for (int f = 0; f < fc; ++f) {
+            if (lam) lam[2 * (size_t)(f0 + f)] = hl[f].re, lam[2 * (size_t)(f0 + f) + 1] = hl[f].im;
+            if (zm) zm[f0 + f] = hz[f].re;
+            if (res) res[f0 + f] = hz[f].im;
+        }
+        if (hipGetLastError() != hipSuccess) return done(HPF_E_HIP);
+    }
+    int bad = 0;
+    if (hipMemcpy(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return done(HPF_E_HIP);
     return done(bad ? HPF_E_SINGULAR : HPF_OK);
 }

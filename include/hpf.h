@@ -436,6 +436,32 @@ int  hpf_penetration(int device, const hpf_zscan_net* net, int F, const double* 
                      const double* I, int chunk_f, int chunk_s, double* V, double* rss, double* vmax, int32_t* varg, double* vsum, double* vsumsq,
                      double* rss_max, int32_t* rss_arg, double* rss_sum, double* rss_sumsq);
 
+/* Resonance mode analysis: per point of a grid of F REAL harmonic orders h > 0, the eigenvalue of Y(h) of smallest modulus (the critical mode), its
+ * modal impedance and the participation factors of the buses -- which resonance the peaks of an impedance scan belong to, and which buses excite
+ * and observe it most.  The reference has no counterpart.  Stateless like hpf_impedance_scan: no handle; the Newton path is not involved.  net, h,
+ * y_extra, chunk, Y(h), the spanning tree and the ties are those of hpf_impedance_scan; the tree factor (w, t, the tie columns, W^-1) is formed
+ * once per frequency point by the scan's kernels, and `iters` steps of inverse iteration run around the right-hand-side walks of hpf_penetration
+ * with one scenario (csrc/hpf_resonance.hpp states every recurrence with its association):
+ *   x_i = 1 + i / n;   k = 1 .. iters:  y = Y^-1 x,  p = argmax_i |y_i|,  x = y / y_p (not after the last step)
+ *   mu = (x . y) / (x . x) without a conjugate (Y is complex symmetric),  lambda = 1 / mu
+ *   iters:   1 .. 256 steps, the same at every point; nothing is retried or adapted
+ *   lam:     [F] complex (interleaved re, im): the critical eigenvalue
+ *   zm:      [F] the critical modal impedance |mu| = 1 / |lambda|, |z| = sqrt(re^2 + im^2)
+ *   res:     [F] max_i |x_i - lambda y_i| / (|lambda| |y_p|) = || Y y - lambda y ||_inf / (|lambda| || y ||_inf) of the returned pair: large where
+ *            two modes cross or iters is too small -- how a caller knows that a point is not resolved
+ *   top:     [F] int32 the bus p of the last step (|y_p| largest, ties to the smallest bus; a NaN is the largest): the largest participation
+ *   pf:      [F][n] complex participation factors y_i^2 / (y . y), sum_i pf_i = 1; may be NULL.  Each of lam, zm, res, top may be NULL as well.
+ *   chunk:   as for hpf_impedance_scan; the scratch of a chunk (the factor, x, y, pf, the partial maxima and sums, the staging buffer) stays under
+ *            256 MiB.  Every output is bit-identical for every chunk length.
+ * All device arrays are [bus][chunk] or [tile of 32 buses][chunk], the frequency fastest, so a wavefront reads and writes 64 consecutive values;
+ * every reduction over the buses is a partial result per tile and then one thread per point over the tiles, the sums in ascending order; no
+ * atomics.  All device memory is per-call workspace and is released on every return path (hpf_debug_device_memory reads the same before and after).
+ * HPF_E_ARG, checked on the host before any HIP call: everything hpf_impedance_scan rejects for net, F, h, y_extra and chunk; iters outside
+ * 1 .. 256.  HPF_E_TOPOLOGY exactly as hpf_impedance_scan returns it.  HPF_E_SINGULAR, with the outputs still written, when any lam, zm, res or pf
+ * is not finite (a singular Y(h): lambda = 0 has no modal impedance). */
+int  hpf_resonance_modes(int device, const hpf_zscan_net* net, int F, const double* h, const double* y_extra, int iters, int chunk, double* lam,
+                         double* zm, double* res, int32_t* top, double* pf);
+
 /* Start state: warm-start the scenarios of a sweep from one solved case instead of the reference's flat start (HG:174-184) + pf (HG:244-275).  The
  * reference has no counterpart (hpf() always starts flat, HG:511-529).  The scenarios of a Monte-Carlo sweep sit close to each other: from the whole
  * raw state of the feeder solved at its nominal loads the harmonic NR needs 2 - 3 iterations where the flat start needs 20 - 30.

@@ -6,6 +6,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["hpf_lib.hip", "hpf_block.hip", "hpf_csr_solve.hip", "hpf_zscan.hip"]
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value", "-fPIC"]   # (tools/isa_hashes.py compiles with these)
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(HERE, "..", "include", "hpf.h")]   # (every header: an edit rebuilds)
 OUT = os.path.join(HERE, "libhpf.so")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
@@ -26,8 +27,7 @@ def build_lib(force=False, verbose=False, stamps=False):
         return OUT
     extra = os.environ.get("HPF_CFLAGS", "").split()          # experiments: e.g. HPF_CFLAGS=-DHPF_Q_OCC=5 HPF_BUILD_OUT=tools/bin/x.so
     out = os.environ.get("HPF_BUILD_OUT", out)
-    cmd = [os.path.join(ROCM, "bin", "hipcc"), "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-           "-Wno-unused-value", "-fPIC", "-shared"] + (["-DHPF_FACTOR_STAMPS"] if stamps else []) + extra + \
+    cmd = [os.path.join(ROCM, "bin", "hipcc")] + FLAGS + ["-shared"] + (["-DHPF_FACTOR_STAMPS"] if stamps else []) + extra + \
           [os.path.join(CSRC, f) for f in SOURCES] + \
           ["-o", out, "-L" + os.path.join(ROCM, "lib"), "-lrocsolver", "-lrocblas",
            "-Wl,-rpath," + os.path.join(ROCM, "lib")]

@@ -31,6 +31,17 @@ constexpr long long PEN_MAX_SN = 1ll << 27, PEN_MAX_NJ = 1ll << 30;
 // start value of a running maximum's argument: loses against every scenario
 constexpr int PEN_NO_S = 0x7fffffff;
 
+// scratch in complex values.  Per frequency point: w, t | Z (the column walks read it) | y_extra and its staging | the tie columns | W^-1;
+// per (point, scenario): r | the staging buffer of I and V (stage_rows) | the tie coefficients
+inline size_t pen_per_f(int n, int k, bool has_x) {
+    return (size_t)2 * n + (k ? n : 0) + (has_x ? (size_t)2 * n : 0) + (size_t)2 * k * n + (size_t)k * k;
+}
+inline size_t pen_stage_rows(int n, int n_inj, bool want_V) {
+    const size_t a = (size_t)n_inj, b = want_V ? n : 0;
+    return a > b ? a : b;
+}
+inline size_t pen_per_j(int n, int k, int n_inj, bool want_V) { return (size_t)n + pen_stage_rows(n, n_inj, want_V) + k; }
+
 // chunk lengths (Fc points, Sc scenarios): forced values as given (clipped to F, S); automatic ones (0) the largest that keep
 // Fc (per_f + Sc per_j) complex values of scratch under ZSCAN_SCRATCH_BYTES -- all scenarios first, then as many points as fit; where one point with
 // all scenarios does not fit, one point and as many scenarios as fit (a multiple of 64 from 64 on).  per_f: w, t, Z, y_extra, the tie columns, W^-1

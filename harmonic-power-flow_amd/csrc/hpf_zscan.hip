@@ -1,8 +1,9 @@
 // hpf_impedance_scan: driving-point and transfer impedances over a grid of harmonic orders (hpf_zscan.hpp has the arithmetic and the planner;
 // include/hpf.h the contract).  Every kernel maps a thread to (item, frequency point) with the frequency fastest: block b of a launch over m items
 // serves item b / fb, points (b % fb) * ZS_TPB + threadIdx.x, fb = ceil(Fc / ZS_TPB) -- a one-dimensional grid, so that the widest depth of a large
-// star still fits; the host keeps n * fb <= 2^30.  hpf_penetration (below, hpf_penetration.hpp) shares the factor kernels of the scan, and
-// hpf_resonance_modes (last, hpf_resonance.hpp) those and the penetration's walks.
+// star still fits; the host keeps n * fb <= 2^30.  hpf_penetration (below, hpf_penetration.hpp) and hpf_resonance_modes (last, hpf_resonance.hpp)
+// need the same Y(h): ZsFactor is the one host driver of the factor of a chunk (the scan's kernels) and of y = Y^-1 x (the penetration's walks);
+// the three entry points keep their own checks, chunk lengths, buffers and outputs.
 #include <algorithm>
 #include <utility>
 
@@ -171,135 +172,190 @@ bool zscan_args_ok(const hpf_zscan_net* net, int F, const double* h, const doubl
 
 unsigned zs_grid(long long items, int Fc) { return (unsigned)(items * ((Fc + ZS_TPB - 1) / ZS_TPB)); }
 
+// the one-dimensional grid of a kernel that takes 32 x 32 tiles of an [a][b] matrix
+unsigned zs_tiles(long long a, long long b) { return (unsigned)(((a + ZS_TILE - 1) / ZS_TILE) * ((b + ZS_TILE - 1) / ZS_TILE)); }
+
+void zs_transpose(hipStream_t st, const cplx* in, long long R, long long C, cplx* out) {
+    hipLaunchKernelGGL(k_zscan_transpose, dim3(zs_tiles(R, C)), dim3(ZS_TILE * 8), 0, st, in, R, C, out);
+}
+
+// a launch over n buses may have (2^30) / n blocks of ZS_TPB points: an automatic chunk length is clipped to that, a forced one has to fit (false)
+bool zs_clip_chunk(int n, int chunk, int& Fc) {
+    const long long fb_max = (1ll << 30) / n;
+    if ((Fc + ZS_TPB - 1) / ZS_TPB <= fb_max) return true;
+    if (chunk > 0) return false;
+    Fc = (int)fb_max * ZS_TPB;
+    return true;
+}
+
+// the end of a call, on every path after hipSetDevice: the per-call workspace is gone before the code goes back
+int zs_done(DevMem& ws, int code) {
+    hipDeviceSynchronize();
+    ws.clear();
+    return code;
+}
+
+// Y(h) of one call: the plan, the ties, the model and the factor of one chunk of frequency points on the device (w, t, Zd where wanted, the columns
+// of the selected buses and of the ties, W^-1), and the solve with it.  The blocks belong to the caller's DevMem, which records the ADDRESS of every
+// pointer below: the object is neither copied nor moved, and it is declared before the DevMem local that nulls its pointers.
+struct ZsFactor {
+    ZscanPlan P;
+    ZscanTies T;
+    ZscanView V{};
+    const hpf_zscan_net* net = nullptr;
+    const double* h = nullptr;
+    int n = 0, F = 0;
+    bool diag = false;                                   // the downward walk runs: Zd is wanted, or the tie columns read it
+    int *d_parent = nullptr, *d_pbranch = nullptr, *d_child_ptr = nullptr, *d_child = nullptr, *d_inc_ptr = nullptr, *d_inc = nullptr;
+    int *d_nodes = nullptr, *d_colbus = nullptr, *d_ta = nullptr, *d_tb = nullptr;
+    double *d_R = nullptr, *d_X = nullptr, *d_gsh = nullptr, *d_bsh = nullptr, *d_xsh = nullptr, *d_h = nullptr, *d_tR = nullptr, *d_tX = nullptr;
+    unsigned char* d_path = nullptr;
+    cplx *d_w = nullptr, *d_t = nullptr, *d_Zd = nullptr, *d_yx = nullptr, *d_cols = nullptr, *d_Winv = nullptr;
+
+    ZsFactor() = default;
+    ZsFactor(const ZsFactor&) = delete;
+    ZsFactor& operator=(const ZsFactor&) = delete;
+
+    // the host part, before any HIP call (the arguments passed zscan_args_ok): HPF_OK or HPF_E_TOPOLOGY
+    int plan(const hpf_zscan_net* net_, int F_, const double* h_, int n_sel = 0, const int32_t* sel = nullptr) {
+        net = net_, h = h_, n = net_->n, F = F_;
+        const int r = zscan_plan(n, net->nb, net->from, net->to, P);
+        if (r == HPF_OK) T = zscan_ties(P, net->from, net->to, net->R, net->X, n_sel, sel);
+        return r;
+    }
+
+    // plan, model and orders up, the arrays of a chunk of Fc points allocated; on a failure the caller clears ws
+    int upload(DevMem& ws, int Fc, bool has_x, bool want_diag) {
+        const size_t nF = (size_t)n * Fc, nb = (size_t)net->nb;
+        const int k = T.k;
+        int r;
+        diag = want_diag || k;
+        if ((r = ws.upload(&d_parent, P.parent)) || (r = ws.upload(&d_pbranch, P.pbranch)) || (r = ws.upload(&d_child_ptr, P.child_ptr)) ||
+            (r = ws.upload(&d_child, P.child)) || (r = ws.upload(&d_inc_ptr, P.inc_ptr)) || (r = ws.upload(&d_inc, P.inc)) ||
+            (r = ws.upload(&d_nodes, P.dep_nodes)) || (r = ws.upload(&d_R, net->R, nb)) || (r = ws.upload(&d_X, net->X, nb)) ||
+            (r = ws.upload(&d_gsh, net->gsh, (size_t)n)) || (r = ws.upload(&d_bsh, net->bsh, (size_t)n)) ||
+            (r = ws.upload(&d_xsh, net->xsh, (size_t)n)) || (r = ws.upload(&d_h, h, (size_t)F)) || (r = ws.alloc(&d_w, nF)) ||
+            (r = ws.alloc(&d_t, nF)))
+            return r;
+        if (diag && (r = ws.alloc(&d_Zd, nF))) return r;
+        if (has_x && (r = ws.alloc(&d_yx, nF))) return r;
+        if (T.ncol && ((r = ws.upload(&d_colbus, T.colbus)) || (r = ws.upload(&d_path, T.path)) || (r = ws.alloc(&d_cols, (size_t)T.ncol * nF))))
+            return r;
+        if (k && ((r = ws.upload(&d_ta, T.ta)) || (r = ws.upload(&d_tb, T.tb)) || (r = ws.upload(&d_tR, T.tR)) || (r = ws.upload(&d_tX, T.tX)) ||
+                  (r = ws.alloc(&d_Winv, (size_t)k * k * Fc))))
+            return r;
+        V = ZscanView{n, d_parent, d_pbranch, d_child_ptr, d_child, d_inc_ptr, d_inc, d_R, d_X, d_gsh, d_bsh, d_xsh};
+        return HPF_OK;
+    }
+
+    // launch(the buses of the depth, their number) for every depth but the first `skip` ones of the order: the root first, or the deepest depth first
+    template <class L>
+    void depths(bool root_first, int skip, L launch) const {
+        for (int q = skip; q < P.n_depths; ++q) {
+            const int d = root_first ? q : P.n_depths - 1 - q;
+            launch(d_nodes + P.dep_ptr[d], P.dep_ptr[d + 1] - P.dep_ptr[d]);
+        }
+    }
+
+    // the tie columns of a chunk of fc points: behind the selected ones
+    const cplx* tie_cols(int fc) const { return d_cols + (size_t)T.n_sel * n * fc; }
+
+    // the factor of the fc points from f0 on; y_extra (the caller's, or NULL) passes through `stage` [fc][n].  HPF_OK or HPF_E_HIP (the copy)
+    int factor(hipStream_t st, int f0, int fc, const double* y_extra, cplx* stage) {
+        const int k = T.k, ncol = T.ncol;
+        const double* hh = d_h + f0;
+        const dim3 tpb(ZS_TPB);
+        if (y_extra) {
+            if (hipMemcpy(stage, y_extra + (size_t)2 * f0 * n, sizeof(cplx) * (size_t)fc * n, hipMemcpyHostToDevice) != hipSuccess) return HPF_E_HIP;
+            zs_transpose(st, stage, fc, n, d_yx);
+        }
+        depths(false, 0, [&](const int* nodes, int m) {
+            hipLaunchKernelGGL(k_zscan_up, dim3(zs_grid(m, fc)), tpb, 0, st, V, nodes, m, fc, hh, d_yx, d_w, d_t);
+        });
+        if (diag)
+            depths(true, 0, [&](const int* nodes, int m) {
+                hipLaunchKernelGGL(k_zscan_down, dim3(zs_grid(m, fc)), tpb, 0, st, V, nodes, m, fc, d_w, d_t, d_Zd);
+            });
+        if (ncol) {
+            hipLaunchKernelGGL(k_zscan_col_walk, dim3(zs_grid(ncol, fc)), tpb, 0, st, V, d_colbus, ncol, fc, d_t, d_Zd, d_cols);
+            depths(true, 1, [&](const int* nodes, int m) {
+                hipLaunchKernelGGL(k_zscan_col_fill, dim3(zs_grid(m, fc), ncol), tpb, 0, st, V, nodes, m, fc, d_path, d_t, d_cols);
+            });
+        }
+        if (k) hipLaunchKernelGGL(k_zscan_tie_winv, dim3(zs_grid(1, fc)), tpb, 0, st, k, d_ta, d_tb, d_tR, d_tX, n, fc, hh, tie_cols(fc), d_Winv);
+        return HPF_OK;
+    }
+
+    // r [n][fc sc] <- Y^-1 r in place, with the factor of the chunk; coef [k][fc sc] (defined behind the penetration's kernels)
+    void solve(hipStream_t st, int fc, int sc, cplx* r, cplx* coef) const;
+};
+
 }  // namespace
 
 extern "C" int hpf_impedance_scan(int device, const hpf_zscan_net* net, int F, const double* h, const double* y_extra, int n_sel, const int32_t* sel,
                                   int chunk, double* Z, double* Zt, double* zpeak, int32_t* fpeak) {
     if (!zscan_args_ok(net, F, h, y_extra, n_sel, sel, chunk, Zt)) return HPF_E_ARG;
-    const int n = net->n, nb = net->nb;
-    ZscanPlan P;
-    int r = zscan_plan(n, nb, net->from, net->to, P);
+    ZsFactor Y;
+    int r = Y.plan(net, F, h, n_sel, sel);
     if (r != HPF_OK) return r;
-    const int k = (int)P.tie.size(), ncol = n_sel + 2 * k;
-    // columns: the selected buses first (they leave as Zt), then col(a_l), col(b_l) of every tie
-    std::vector<int> colbus(sel, sel + n_sel), ta(k), tb(k);
-    std::vector<double> tR(k), tX(k);
-    for (int l = 0; l < k; ++l) {
-        ta[l] = net->from[P.tie[l]], tb[l] = net->to[P.tie[l]];
-        tR[l] = net->R[P.tie[l]], tX[l] = net->X[P.tie[l]];
-        colbus.push_back(ta[l]);
-        colbus.push_back(tb[l]);
-    }
-    std::vector<unsigned char> path((size_t)ncol * n, 0);
-    for (int s = 0; s < ncol; ++s) zscan_mark_path(P, colbus[s], path.data() + (size_t)s * n);
-    // scratch per frequency point, in complex values: w, t, Zd | y_extra | columns | W^-1 | staging of the transposed copies
-    const size_t stage_rows = std::max<size_t>((Z || y_extra) ? n : 0, (size_t)n_sel * n);
-    const size_t per_f = (size_t)3 * n + (y_extra ? n : 0) + (size_t)ncol * n + (size_t)k * k + stage_rows;
-    int Fc = zscan_chunk(F, chunk, per_f);
-    const long long fb_max = (1ll << 30) / n;            // blocks of ZS_TPB points a launch over n buses may have
-    if ((Fc + ZS_TPB - 1) / ZS_TPB > fb_max) {
-        if (chunk > 0) return HPF_E_ARG;
-        Fc = (int)fb_max * ZS_TPB;
-    }
+    const int n = net->n, k = Y.T.k;
+    const size_t stage_rows = zscan_stage_rows(n, n_sel, y_extra != nullptr, Z != nullptr);
+    int Fc = zscan_chunk(F, chunk, zscan_per_f(n, k, n_sel, y_extra != nullptr, Z != nullptr));
+    if (!zs_clip_chunk(n, chunk, Fc)) return HPF_E_ARG;
 
     if (hipSetDevice(device) != hipSuccess) return HPF_E_HIP;
     int detail = 0;
-    int *d_parent = nullptr, *d_pbranch = nullptr, *d_child_ptr = nullptr, *d_child = nullptr, *d_inc_ptr = nullptr, *d_inc = nullptr;
-    int *d_nodes = nullptr, *d_colbus = nullptr, *d_ta = nullptr, *d_tb = nullptr, *d_pf = nullptr, *d_bad = nullptr;
-    double *d_R = nullptr, *d_X = nullptr, *d_gsh = nullptr, *d_bsh = nullptr, *d_xsh = nullptr, *d_h = nullptr, *d_tR = nullptr, *d_tX = nullptr;
-    unsigned char* d_path = nullptr;
+    int *d_pf = nullptr, *d_bad = nullptr;
     unsigned long long* d_pkey = nullptr;
-    cplx *d_w = nullptr, *d_t = nullptr, *d_Zd = nullptr, *d_yx = nullptr, *d_cols = nullptr, *d_Winv = nullptr, *d_stage = nullptr;
+    cplx* d_stage = nullptr;
     DevMem ws(&detail);                                  // per-call workspace (declared after the pointers it nulls): gone on every return path
-    auto done = [&](int code) {
-        hipDeviceSynchronize();
-        ws.clear();
-        return code;
-    };
-    const size_t nF = (size_t)n * Fc;
-    if ((r = ws.upload(&d_parent, P.parent)) || (r = ws.upload(&d_pbranch, P.pbranch)) || (r = ws.upload(&d_child_ptr, P.child_ptr)) ||
-        (r = ws.upload(&d_child, P.child)) || (r = ws.upload(&d_inc_ptr, P.inc_ptr)) || (r = ws.upload(&d_inc, P.inc)) ||
-        (r = ws.upload(&d_nodes, P.dep_nodes)) || (r = ws.upload(&d_R, net->R, (size_t)nb)) || (r = ws.upload(&d_X, net->X, (size_t)nb)) ||
-        (r = ws.upload(&d_gsh, net->gsh, (size_t)n)) || (r = ws.upload(&d_bsh, net->bsh, (size_t)n)) ||
-        (r = ws.upload(&d_xsh, net->xsh, (size_t)n)) || (r = ws.upload(&d_h, h, (size_t)F)) || (r = ws.alloc(&d_pkey, (size_t)n)) ||
-        (r = ws.alloc(&d_pf, (size_t)n)) || (r = ws.alloc(&d_bad, (size_t)n)) || (r = ws.alloc(&d_w, nF)) || (r = ws.alloc(&d_t, nF)) ||
-        (r = ws.alloc(&d_Zd, nF)))
-        return done(r);
-    if (y_extra && (r = ws.alloc(&d_yx, nF))) return done(r);
-    if (stage_rows && (r = ws.alloc(&d_stage, stage_rows * Fc))) return done(r);
-    if (ncol && ((r = ws.upload(&d_colbus, colbus)) || (r = ws.upload(&d_path, path)) || (r = ws.alloc(&d_cols, (size_t)ncol * nF)))) return done(r);
-    if (k && ((r = ws.upload(&d_ta, ta)) || (r = ws.upload(&d_tb, tb)) || (r = ws.upload(&d_tR, tR)) || (r = ws.upload(&d_tX, tX)) ||
-              (r = ws.alloc(&d_Winv, (size_t)k * k * Fc))))
-        return done(r);
+    if ((r = Y.upload(ws, Fc, y_extra != nullptr, true)) || (r = ws.alloc(&d_pkey, (size_t)n)) || (r = ws.alloc(&d_pf, (size_t)n)) ||
+        (r = ws.alloc(&d_bad, (size_t)n)))
+        return zs_done(ws, r);
+    if (stage_rows && (r = ws.alloc(&d_stage, stage_rows * Fc))) return zs_done(ws, r);
 
-    const ZscanView V{n, d_parent, d_pbranch, d_child_ptr, d_child, d_inc_ptr, d_inc, d_R, d_X, d_gsh, d_bsh, d_xsh};
     const hipStream_t st = nullptr;
-    auto transpose = [&](const cplx* in, long long R, long long C, cplx* out) {
-        const long long tiles = ((R + ZS_TILE - 1) / ZS_TILE) * ((C + ZS_TILE - 1) / ZS_TILE);
-        hipLaunchKernelGGL(k_zscan_transpose, dim3((unsigned)tiles), dim3(ZS_TILE * 8), 0, st, in, R, C, out);
-    };
     hipLaunchKernelGGL(k_zscan_peaks_init, dim3((n + 255) / 256), dim3(256), 0, st, n, d_pkey, d_pf, d_bad);
     for (int f0 = 0; f0 < F; f0 += Fc) {
         const int fc = std::min(Fc, F - f0);             // (the arrays of a short last chunk are [bus][fc])
-        const double* hh = d_h + f0;
-        if (y_extra) {
-            if (hipMemcpy(d_stage, y_extra + (size_t)2 * f0 * n, sizeof(cplx) * (size_t)fc * n, hipMemcpyHostToDevice) != hipSuccess)
-                return done(HPF_E_HIP);
-            transpose(d_stage, fc, n, d_yx);
-        }
-        for (int d = P.n_depths - 1; d >= 0; --d) {
-            const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
-            hipLaunchKernelGGL(k_zscan_up, dim3(zs_grid(m, fc)), dim3(ZS_TPB), 0, st, V, d_nodes + P.dep_ptr[d], m, fc, hh, d_yx, d_w, d_t);
-        }
-        for (int d = 0; d < P.n_depths; ++d) {
-            const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
-            hipLaunchKernelGGL(k_zscan_down, dim3(zs_grid(m, fc)), dim3(ZS_TPB), 0, st, V, d_nodes + P.dep_ptr[d], m, fc, d_w, d_t, d_Zd);
-        }
-        if (ncol) {
-            hipLaunchKernelGGL(k_zscan_col_walk, dim3(zs_grid(ncol, fc)), dim3(ZS_TPB), 0, st, V, d_colbus, ncol, fc, d_t, d_Zd, d_cols);
-            for (int d = 1; d < P.n_depths; ++d) {
-                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
-                hipLaunchKernelGGL(k_zscan_col_fill, dim3(zs_grid(m, fc), ncol), dim3(ZS_TPB), 0, st, V, d_nodes + P.dep_ptr[d], m, fc, d_path, d_t,
-                                   d_cols);
-            }
-        }
-        if (k) {
-            const cplx* tc = d_cols + (size_t)n_sel * n * fc;
-            hipLaunchKernelGGL(k_zscan_tie_winv, dim3(zs_grid(1, fc)), dim3(ZS_TPB), 0, st, k, d_ta, d_tb, d_tR, d_tX, n, fc, hh, tc, d_Winv);
-            hipLaunchKernelGGL(k_zscan_tie_fix, dim3(zs_grid(n, fc), 1), dim3(ZS_TPB), 0, st, k, n, fc, tc, d_Winv, (const int*)nullptr, d_Zd);
+        if ((r = Y.factor(st, f0, fc, y_extra, d_stage))) return zs_done(ws, r);
+        if (k) {                                         // the ties' correction of the diagonal and of the selected columns
+            const cplx* tc = Y.tie_cols(fc);
+            hipLaunchKernelGGL(k_zscan_tie_fix, dim3(zs_grid(n, fc), 1), dim3(ZS_TPB), 0, st, k, n, fc, tc, Y.d_Winv, (const int*)nullptr, Y.d_Zd);
             if (n_sel)
-                hipLaunchKernelGGL(k_zscan_tie_fix, dim3(zs_grid(n, fc), n_sel), dim3(ZS_TPB), 0, st, k, n, fc, tc, d_Winv, d_colbus, d_cols);
+                hipLaunchKernelGGL(k_zscan_tie_fix, dim3(zs_grid(n, fc), n_sel), dim3(ZS_TPB), 0, st, k, n, fc, tc, Y.d_Winv, Y.d_colbus, Y.d_cols);
         }
-        hipLaunchKernelGGL(k_zscan_peaks, dim3((n + ZS_TPB / 64 - 1) / (ZS_TPB / 64)), dim3(ZS_TPB), 0, st, n, fc, f0, d_Zd, d_pkey, d_pf, d_bad);
+        hipLaunchKernelGGL(k_zscan_peaks, dim3((n + ZS_TPB / 64 - 1) / (ZS_TPB / 64)), dim3(ZS_TPB), 0, st, n, fc, f0, Y.d_Zd, d_pkey, d_pf, d_bad);
         if (Z) {
-            transpose(d_Zd, n, fc, d_stage);
-            if (hipMemcpy(Z + (size_t)2 * f0 * n, d_stage, sizeof(cplx) * (size_t)fc * n, hipMemcpyDeviceToHost) != hipSuccess) return done(HPF_E_HIP);
+            zs_transpose(st, Y.d_Zd, n, fc, d_stage);
+            if (hipMemcpy(Z + (size_t)2 * f0 * n, d_stage, sizeof(cplx) * (size_t)fc * n, hipMemcpyDeviceToHost) != hipSuccess)
+                return zs_done(ws, HPF_E_HIP);
         }
         if (n_sel) {
-            transpose(d_cols, (long long)n_sel * n, fc, d_stage);
+            zs_transpose(st, Y.d_cols, (long long)n_sel * n, fc, d_stage);
             if (hipMemcpy(Zt + (size_t)2 * f0 * n_sel * n, d_stage, sizeof(cplx) * (size_t)fc * n_sel * n, hipMemcpyDeviceToHost) != hipSuccess)
-                return done(HPF_E_HIP);
+                return zs_done(ws, HPF_E_HIP);
         }
-        if (hipGetLastError() != hipSuccess) return done(HPF_E_HIP);
+        if (hipGetLastError() != hipSuccess) return zs_done(ws, HPF_E_HIP);
     }
     std::vector<unsigned long long> pkey((size_t)n);
     std::vector<int> pf((size_t)n), bad((size_t)n);
     if (hipMemcpy(pkey.data(), d_pkey, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(pf.data(), d_pf, sizeof(int) * n, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(bad.data(), d_bad, sizeof(int) * n, hipMemcpyDeviceToHost) != hipSuccess)
-        return done(HPF_E_HIP);
+        return zs_done(ws, HPF_E_HIP);
     bool singular = false;
     for (int i = 0; i < n; ++i) {
         if (zpeak) zpeak[i] = wave_key_value(pkey[i]);
         if (fpeak) fpeak[i] = pf[i];
         singular |= bad[i] != 0;
     }
-    return done(singular ? HPF_E_SINGULAR : HPF_OK);
+    return zs_done(ws, singular ? HPF_E_SINGULAR : HPF_OK);
 }
 
 // ---- hpf_penetration ---------------------------------------------------------------------------------------------------------------------------
 // V(h) = Y(h)^-1 I(h) for S scenarios (hpf_penetration.hpp has the arithmetic; include/hpf.h the contract).  The factor of a chunk of fc frequency
-// points (w, t, the tie columns, W^-1) comes from the scan's kernels above; the right-hand sides of a chunk of sc scenarios live in place as
+// points (w, t, the tie columns, W^-1) is ZsFactor::factor, the two walks and the tie correction ZsFactor::solve; the right-hand sides of a chunk of sc scenarios live in place as
 // r [n][J], j = f sc + s, J = fc sc.  The walks map a thread to (bus of the depth, j) with j fastest (zs_item over J): a wavefront reads 64
 // consecutive values of r and, with sc >= 64, one w_i / t_i.
 namespace {
@@ -445,135 +501,82 @@ bool pen_args_ok(int n, int F, int S, int n_inj, const int32_t* inj, const doubl
     return finite_all(I, (size_t)2 * S * F * n_inj);
 }
 
+void ZsFactor::solve(hipStream_t st, int fc, int sc, cplx* r, cplx* coef) const {
+    const int k = T.k, J = fc * sc;
+    const dim3 tpb(ZS_TPB);
+    depths(false, 1, [&](const int* nodes, int m) {      // (the deepest depth holds leaves only)
+        hipLaunchKernelGGL(k_pen_up, dim3(zs_grid(m, J)), tpb, 0, st, V, nodes, m, fc, sc, d_t, r);
+    });
+    depths(true, 0, [&](const int* nodes, int m) {
+        hipLaunchKernelGGL(k_pen_down, dim3(zs_grid(m, J)), tpb, 0, st, V, nodes, m, fc, sc, d_w, d_t, r);
+    });
+    if (k) {
+        hipLaunchKernelGGL(k_pen_tie_coef, dim3(zs_grid(1, J)), tpb, 0, st, k, d_ta, d_tb, fc, sc, d_Winv, r, coef);
+        hipLaunchKernelGGL(k_pen_tie_fix, dim3(zs_grid(n, J)), tpb, 0, st, k, n, fc, sc, tie_cols(fc), coef, r);
+    }
+}
+
 }  // namespace
 
 extern "C" int hpf_penetration(int device, const hpf_zscan_net* net, int F, const double* h, const double* y_extra, int S, int n_inj,
                                const int32_t* inj, const double* I, int chunk_f, int chunk_s, double* V, double* rss, double* vmax, int32_t* varg,
                                double* vsum, double* vsumsq, double* rss_max, int32_t* rss_arg, double* rss_sum, double* rss_sumsq) {
     if (!zscan_args_ok(net, F, h, y_extra, 0, nullptr, 0, nullptr) || !pen_args_ok(net->n, F, S, n_inj, inj, I, chunk_f, chunk_s)) return HPF_E_ARG;
-    const int n = net->n, nb = net->nb;
-    ZscanPlan P;
-    int r = zscan_plan(n, nb, net->from, net->to, P);
+    ZsFactor Y;
+    int r = Y.plan(net, F, h);
     if (r != HPF_OK) return r;
-    const int k = (int)P.tie.size(), ncol = 2 * k;
-    std::vector<int> colbus, ta(k), tb(k);
-    std::vector<double> tR(k), tX(k);
-    for (int l = 0; l < k; ++l) {
-        ta[l] = net->from[P.tie[l]], tb[l] = net->to[P.tie[l]];
-        tR[l] = net->R[P.tie[l]], tX[l] = net->X[P.tie[l]];
-        colbus.push_back(ta[l]);
-        colbus.push_back(tb[l]);
-    }
-    std::vector<unsigned char> path((size_t)ncol * n, 0);
-    for (int s = 0; s < ncol; ++s) zscan_mark_path(P, colbus[s], path.data() + (size_t)s * n);
+    const int n = net->n, k = Y.T.k;
     const bool want_rss = rss || rss_max || rss_arg || rss_sum || rss_sumsq;
-    // scratch in complex values.  Per frequency point: w, t | Z (the column walks read it) | y_extra and its staging | tie columns | W^-1;
-    // per (point, scenario): r | the staging buffer of I and V | the tie coefficients
-    const size_t stage_rows = std::max<size_t>((size_t)n_inj, V ? n : 0);
-    const size_t per_f = (size_t)2 * n + (k ? n : 0) + (y_extra ? (size_t)2 * n : 0) + (size_t)ncol * n + (size_t)k * k;
-    const size_t per_j = (size_t)n + stage_rows + k;
+    const size_t stage_rows = pen_stage_rows(n, n_inj, V != nullptr);
     int Fc, Sc;
-    pen_chunks(F, S, chunk_f, chunk_s, per_f, per_j, Fc, Sc);
+    pen_chunks(F, S, chunk_f, chunk_s, pen_per_f(n, k, y_extra != nullptr), pen_per_j(n, k, n_inj, V != nullptr), Fc, Sc);
     if ((long long)n * Fc * Sc > PEN_MAX_NJ) return HPF_E_ARG;   // (forced lengths only: the automatic ones stay inside the budget)
 
     if (hipSetDevice(device) != hipSuccess) return HPF_E_HIP;
     int detail = 0;
-    int *d_parent = nullptr, *d_pbranch = nullptr, *d_child_ptr = nullptr, *d_child = nullptr, *d_inc_ptr = nullptr, *d_inc = nullptr;
-    int *d_nodes = nullptr, *d_colbus = nullptr, *d_ta = nullptr, *d_tb = nullptr, *d_inj = nullptr, *d_varg = nullptr, *d_rarg = nullptr, *d_bad = nullptr;
-    double *d_R = nullptr, *d_X = nullptr, *d_gsh = nullptr, *d_bsh = nullptr, *d_xsh = nullptr, *d_h = nullptr, *d_tR = nullptr, *d_tX = nullptr;
+    int *d_inj = nullptr, *d_varg = nullptr, *d_rarg = nullptr, *d_bad = nullptr;
     double *d_vsum = nullptr, *d_vsumsq = nullptr, *d_sq = nullptr, *d_rsum = nullptr, *d_rsumsq = nullptr;
-    unsigned char* d_path = nullptr;
     unsigned long long *d_vkey = nullptr, *d_rkey = nullptr;
-    cplx *d_w = nullptr, *d_t = nullptr, *d_Zd = nullptr, *d_yx = nullptr, *d_yst = nullptr, *d_cols = nullptr, *d_Winv = nullptr;
-    cplx *d_r = nullptr, *d_stage = nullptr, *d_coef = nullptr;
+    cplx *d_yst = nullptr, *d_r = nullptr, *d_stage = nullptr, *d_coef = nullptr;
     DevMem ws(&detail);                                  // per-call workspace (declared after the pointers it nulls): gone on every return path
-    auto done = [&](int code) {
-        hipDeviceSynchronize();
-        ws.clear();
-        return code;
-    };
     const size_t nF = (size_t)n * Fc, Jmax = (size_t)Fc * Sc, Fn = (size_t)F * n;
     const std::vector<int> injv(inj, inj + n_inj);
-    if ((r = ws.upload(&d_parent, P.parent)) || (r = ws.upload(&d_pbranch, P.pbranch)) || (r = ws.upload(&d_child_ptr, P.child_ptr)) ||
-        (r = ws.upload(&d_child, P.child)) || (r = ws.upload(&d_inc_ptr, P.inc_ptr)) || (r = ws.upload(&d_inc, P.inc)) ||
-        (r = ws.upload(&d_nodes, P.dep_nodes)) || (r = ws.upload(&d_R, net->R, (size_t)nb)) || (r = ws.upload(&d_X, net->X, (size_t)nb)) ||
-        (r = ws.upload(&d_gsh, net->gsh, (size_t)n)) || (r = ws.upload(&d_bsh, net->bsh, (size_t)n)) ||
-        (r = ws.upload(&d_xsh, net->xsh, (size_t)n)) || (r = ws.upload(&d_h, h, (size_t)F)) || (r = ws.upload(&d_inj, injv)) ||
-        (r = ws.alloc(&d_w, nF)) || (r = ws.alloc(&d_t, nF)) || (r = ws.alloc(&d_r, n * Jmax)) || (r = ws.alloc(&d_stage, stage_rows * Jmax)) ||
-        (r = ws.alloc(&d_vkey, Fn)) || (r = ws.alloc(&d_varg, Fn)) || (r = ws.alloc(&d_vsum, Fn)) || (r = ws.alloc(&d_vsumsq, Fn)) ||
-        (r = ws.alloc(&d_bad, (size_t)1)))
-        return done(r);
-    if (y_extra && ((r = ws.alloc(&d_yx, nF)) || (r = ws.alloc(&d_yst, nF)))) return done(r);
+    if ((r = Y.upload(ws, Fc, y_extra != nullptr, false)) || (r = ws.upload(&d_inj, injv)) || (r = ws.alloc(&d_r, n * Jmax)) ||
+        (r = ws.alloc(&d_stage, stage_rows * Jmax)) || (r = ws.alloc(&d_vkey, Fn)) || (r = ws.alloc(&d_varg, Fn)) || (r = ws.alloc(&d_vsum, Fn)) ||
+        (r = ws.alloc(&d_vsumsq, Fn)) || (r = ws.alloc(&d_bad, (size_t)1)))
+        return zs_done(ws, r);
+    if (y_extra && (r = ws.alloc(&d_yst, nF))) return zs_done(ws, r);
     if (want_rss && ((r = ws.alloc(&d_sq, (size_t)n * S)) || (r = ws.alloc(&d_rkey, (size_t)n)) || (r = ws.alloc(&d_rarg, (size_t)n)) ||
                      (r = ws.alloc(&d_rsum, (size_t)n)) || (r = ws.alloc(&d_rsumsq, (size_t)n))))
-        return done(r);
-    if (k && ((r = ws.upload(&d_colbus, colbus)) || (r = ws.upload(&d_path, path)) || (r = ws.alloc(&d_cols, (size_t)ncol * nF)) ||
-              (r = ws.alloc(&d_Zd, nF)) || (r = ws.upload(&d_ta, ta)) || (r = ws.upload(&d_tb, tb)) || (r = ws.upload(&d_tR, tR)) ||
-              (r = ws.upload(&d_tX, tX)) || (r = ws.alloc(&d_Winv, (size_t)k * k * Fc)) || (r = ws.alloc(&d_coef, (size_t)k * Jmax))))
-        return done(r);
+        return zs_done(ws, r);
+    if (k && (r = ws.alloc(&d_coef, (size_t)k * Jmax))) return zs_done(ws, r);
 
-    const ZscanView Vw{n, d_parent, d_pbranch, d_child_ptr, d_child, d_inc_ptr, d_inc, d_R, d_X, d_gsh, d_bsh, d_xsh};
     const hipStream_t st = nullptr;
-    auto tiles = [](long long a, long long b) { return (unsigned)(((a + ZS_TILE - 1) / ZS_TILE) * ((b + ZS_TILE - 1) / ZS_TILE)); };
-    if (hipMemsetAsync(d_bad, 0, sizeof(int), st) != hipSuccess) return done(HPF_E_HIP);
+    if (hipMemsetAsync(d_bad, 0, sizeof(int), st) != hipSuccess) return zs_done(ws, HPF_E_HIP);
     for (int f0 = 0; f0 < F; f0 += Fc) {
         const int fc = std::min(Fc, F - f0);             // (the arrays of a short last chunk are [bus][fc])
-        const double* hh = d_h + f0;
-        // the factor of the chunk's points: the scan's kernels
-        if (y_extra) {
-            if (hipMemcpy(d_yst, y_extra + (size_t)2 * f0 * n, sizeof(cplx) * (size_t)fc * n, hipMemcpyHostToDevice) != hipSuccess)
-                return done(HPF_E_HIP);
-            hipLaunchKernelGGL(k_zscan_transpose, dim3(tiles(fc, n)), dim3(ZS_TILE * 8), 0, st, d_yst, (long long)fc, (long long)n, d_yx);
-        }
-        for (int d = P.n_depths - 1; d >= 0; --d) {
-            const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
-            hipLaunchKernelGGL(k_zscan_up, dim3(zs_grid(m, fc)), dim3(ZS_TPB), 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, hh, d_yx, d_w, d_t);
-        }
-        if (k) {
-            for (int d = 0; d < P.n_depths; ++d) {
-                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
-                hipLaunchKernelGGL(k_zscan_down, dim3(zs_grid(m, fc)), dim3(ZS_TPB), 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, d_w, d_t, d_Zd);
-            }
-            hipLaunchKernelGGL(k_zscan_col_walk, dim3(zs_grid(ncol, fc)), dim3(ZS_TPB), 0, st, Vw, d_colbus, ncol, fc, d_t, d_Zd, d_cols);
-            for (int d = 1; d < P.n_depths; ++d) {
-                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
-                hipLaunchKernelGGL(k_zscan_col_fill, dim3(zs_grid(m, fc), ncol), dim3(ZS_TPB), 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, d_path, d_t,
-                                   d_cols);
-            }
-            hipLaunchKernelGGL(k_zscan_tie_winv, dim3(zs_grid(1, fc)), dim3(ZS_TPB), 0, st, k, d_ta, d_tb, d_tR, d_tX, n, fc, hh, d_cols, d_Winv);
-        }
+        if ((r = Y.factor(st, f0, fc, y_extra, d_yst))) return zs_done(ws, r);
         for (int s0 = 0; s0 < S; s0 += Sc) {
             const int sc = std::min(Sc, S - s0);
             const int J = fc * sc;
             // I [s0 ..][f0 ..][:] -> stage [sc][fc][n_inj] -> r
             if (hipMemcpy2D(d_stage, sizeof(cplx) * (size_t)fc * n_inj, I + (size_t)2 * ((size_t)s0 * F + f0) * n_inj, sizeof(cplx) * (size_t)F * n_inj,
                             sizeof(cplx) * (size_t)fc * n_inj, (size_t)sc, hipMemcpyHostToDevice) != hipSuccess)
-                return done(HPF_E_HIP);
-            if (n_inj < n && hipMemsetAsync(d_r, 0, sizeof(cplx) * (size_t)n * J, st) != hipSuccess) return done(HPF_E_HIP);
-            hipLaunchKernelGGL(k_pen_scatter, dim3((unsigned)fc * tiles(sc, n_inj)), dim3(ZS_TILE * 8), 0, st, d_stage, d_inj, n_inj, fc, sc, d_r);
-            for (int d = P.n_depths - 2; d >= 0; --d) {      // (the deepest depth holds leaves only)
-                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
-                hipLaunchKernelGGL(k_pen_up, dim3(zs_grid(m, J)), dim3(ZS_TPB), 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, sc, d_t, d_r);
-            }
-            for (int d = 0; d < P.n_depths; ++d) {
-                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
-                hipLaunchKernelGGL(k_pen_down, dim3(zs_grid(m, J)), dim3(ZS_TPB), 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, sc, d_w, d_t, d_r);
-            }
-            if (k) {
-                hipLaunchKernelGGL(k_pen_tie_coef, dim3(zs_grid(1, J)), dim3(ZS_TPB), 0, st, k, d_ta, d_tb, fc, sc, d_Winv, d_r, d_coef);
-                hipLaunchKernelGGL(k_pen_tie_fix, dim3(zs_grid(n, J)), dim3(ZS_TPB), 0, st, k, n, fc, sc, d_cols, d_coef, d_r);
-            }
+                return zs_done(ws, HPF_E_HIP);
+            if (n_inj < n && hipMemsetAsync(d_r, 0, sizeof(cplx) * (size_t)n * J, st) != hipSuccess) return zs_done(ws, HPF_E_HIP);
+            hipLaunchKernelGGL(k_pen_scatter, dim3((unsigned)fc * zs_tiles(sc, n_inj)), dim3(ZS_TILE * 8), 0, st, d_stage, d_inj, n_inj, fc, sc, d_r);
+            Y.solve(st, fc, sc, d_r, d_coef);
             const long long rows = (long long)n * fc;
             hipLaunchKernelGGL(k_pen_fold<false>, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, rows, sc, s0, n, fc, f0, d_r, (double*)nullptr,
                                d_vkey, d_varg, d_vsum, d_vsumsq, d_bad);
             if (want_rss) hipLaunchKernelGGL(k_pen_fold_sq, dim3(zs_grid(n, sc)), dim3(ZS_TPB), 0, st, n, fc, sc, f0, s0, S, d_r, d_sq);
             if (V) {
-                hipLaunchKernelGGL(k_pen_copy_out, dim3((unsigned)fc * tiles(n, sc)), dim3(ZS_TILE * 8), 0, st, d_r, n, fc, sc, d_stage);
+                hipLaunchKernelGGL(k_pen_copy_out, dim3((unsigned)fc * zs_tiles(n, sc)), dim3(ZS_TILE * 8), 0, st, d_r, n, fc, sc, d_stage);
                 if (hipMemcpy2D(V + (size_t)2 * ((size_t)s0 * F + f0) * n, sizeof(cplx) * (size_t)F * n, d_stage, sizeof(cplx) * (size_t)fc * n,
                                 sizeof(cplx) * (size_t)fc * n, (size_t)sc, hipMemcpyDeviceToHost) != hipSuccess)
-                    return done(HPF_E_HIP);
+                    return zs_done(ws, HPF_E_HIP);
             }
-            if (hipGetLastError() != hipSuccess) return done(HPF_E_HIP);
+            if (hipGetLastError() != hipSuccess) return zs_done(ws, HPF_E_HIP);
         }
     }
     if (want_rss)
@@ -590,24 +593,24 @@ extern "C" int hpf_penetration(int device, const hpf_zscan_net* net, int F, cons
     int bad = 0;
     if (hipMemcpy(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess || !fetch_max(vmax, d_vkey, Fn) ||
         !fetch(varg, d_varg, sizeof(int) * Fn) || !fetch(vsum, d_vsum, sizeof(double) * Fn) || !fetch(vsumsq, d_vsumsq, sizeof(double) * Fn))
-        return done(HPF_E_HIP);
+        return zs_done(ws, HPF_E_HIP);
     if (want_rss) {
         if (!fetch_max(rss_max, d_rkey, (size_t)n) || !fetch(rss_arg, d_rarg, sizeof(int) * n) || !fetch(rss_sum, d_rsum, sizeof(double) * n) ||
             !fetch(rss_sumsq, d_rsumsq, sizeof(double) * n))
-            return done(HPF_E_HIP);
+            return zs_done(ws, HPF_E_HIP);
         if (rss) {                                       // [n][S] on the device (the scenario fastest) -> the caller's [S][n]
             std::vector<double> a((size_t)n * S);
-            if (hipMemcpy(a.data(), d_sq, sizeof(double) * a.size(), hipMemcpyDeviceToHost) != hipSuccess) return done(HPF_E_HIP);
+            if (hipMemcpy(a.data(), d_sq, sizeof(double) * a.size(), hipMemcpyDeviceToHost) != hipSuccess) return zs_done(ws, HPF_E_HIP);
             for (int i = 0; i < n; ++i)
                 for (int s = 0; s < S; ++s) rss[(size_t)s * n + i] = a[(size_t)i * S + s];
         }
     }
-    return done(bad ? HPF_E_SINGULAR : HPF_OK);
+    return zs_done(ws, bad ? HPF_E_SINGULAR : HPF_OK);
 }
 
 // ---- hpf_resonance_modes -----------------------------------------------------------------------------------------------------------------------
 // The critical mode of Y(h) per frequency point by inverse iteration (hpf_resonance.hpp has the arithmetic; include/hpf.h the contract).  The factor
-// of a chunk comes from the scan's kernels, y = Y^-1 x from the penetration's walks with sc = 1 (r = y [n][fc], in place); the kernels below are the
+// of a chunk is ZsFactor::factor, y = Y^-1 x is ZsFactor::solve with sc = 1 (r = y [n][fc], in place); the kernels below are the
 // loop around them.  x, y and pf are [bus][fc], the partial keys and sums [tile][fc], the per-point values [fc]: a wavefront reads 64 consecutive
 // values everywhere.  No atomics: every reduction over the buses is a partial per tile of RMA_TILE buses and then one thread per point over the tiles.
 namespace {
@@ -717,112 +720,41 @@ __global__ __launch_bounds__(ZS_TPB) void k_rma_finish(int n, int fc, const cplx
 extern "C" int hpf_resonance_modes(int device, const hpf_zscan_net* net, int F, const double* h, const double* y_extra, int iters, int chunk,
                                    double* lam, double* zm, double* res, int32_t* top, double* pf) {
     if (!zscan_args_ok(net, F, h, y_extra, 0, nullptr, chunk, nullptr) || iters < 1 || iters > RMA_MAX_ITERS) return HPF_E_ARG;
-    const int n = net->n, nb = net->nb;
-    ZscanPlan P;
-    int r = zscan_plan(n, nb, net->from, net->to, P);
+    ZsFactor Y;
+    int r = Y.plan(net, F, h);
     if (r != HPF_OK) return r;
-    const int k = (int)P.tie.size(), ncol = 2 * k, tiles = rma_tiles(n);
-    std::vector<int> colbus, ta(k), tb(k);
-    std::vector<double> tR(k), tX(k);
-    for (int l = 0; l < k; ++l) {
-        ta[l] = net->from[P.tie[l]], tb[l] = net->to[P.tie[l]];
-        tR[l] = net->R[P.tie[l]], tX[l] = net->X[P.tie[l]];
-        colbus.push_back(ta[l]);
-        colbus.push_back(tb[l]);
-    }
-    std::vector<unsigned char> path((size_t)ncol * n, 0);
-    for (int s = 0; s < ncol; ++s) zscan_mark_path(P, colbus[s], path.data() + (size_t)s * n);
+    const int n = net->n, k = Y.T.k, tiles = rma_tiles(n);
     int Fc = zscan_chunk(F, chunk, rma_per_f(n, k, y_extra != nullptr, pf != nullptr));
-    const long long fb_max = (1ll << 30) / n;            // blocks of ZS_TPB points a launch over n buses may have
-    if ((Fc + ZS_TPB - 1) / ZS_TPB > fb_max) {
-        if (chunk > 0) return HPF_E_ARG;
-        Fc = (int)fb_max * ZS_TPB;
-    }
+    if (!zs_clip_chunk(n, chunk, Fc)) return HPF_E_ARG;
 
     if (hipSetDevice(device) != hipSuccess) return HPF_E_HIP;
     int detail = 0;
-    int *d_parent = nullptr, *d_pbranch = nullptr, *d_child_ptr = nullptr, *d_child = nullptr, *d_inc_ptr = nullptr, *d_inc = nullptr;
-    int *d_nodes = nullptr, *d_colbus = nullptr, *d_ta = nullptr, *d_tb = nullptr, *d_parg = nullptr, *d_piv = nullptr, *d_bad = nullptr;
-    double *d_R = nullptr, *d_X = nullptr, *d_gsh = nullptr, *d_bsh = nullptr, *d_xsh = nullptr, *d_h = nullptr, *d_tR = nullptr, *d_tX = nullptr;
-    unsigned char* d_path = nullptr;
+    int *d_parg = nullptr, *d_piv = nullptr, *d_bad = nullptr;
     unsigned long long* d_pkey = nullptr;
-    cplx *d_w = nullptr, *d_t = nullptr, *d_Zd = nullptr, *d_yx = nullptr, *d_cols = nullptr, *d_Winv = nullptr, *d_coef = nullptr, *d_stage = nullptr;
-    cplx *d_x = nullptr, *d_y = nullptr, *d_pf = nullptr, *d_part = nullptr, *d_sums = nullptr, *d_yp = nullptr, *d_lam = nullptr, *d_zr = nullptr;
-    cplx* d_ginv = nullptr;
+    cplx *d_coef = nullptr, *d_stage = nullptr, *d_x = nullptr, *d_y = nullptr, *d_pf = nullptr, *d_part = nullptr, *d_sums = nullptr;
+    cplx *d_yp = nullptr, *d_lam = nullptr, *d_zr = nullptr, *d_ginv = nullptr;
     DevMem ws(&detail);                                  // per-call workspace (declared after the pointers it nulls): gone on every return path
-    auto done = [&](int code) {
-        hipDeviceSynchronize();
-        ws.clear();
-        return code;
-    };
     const size_t nF = (size_t)n * Fc, tF = (size_t)tiles * Fc;
-    if ((r = ws.upload(&d_parent, P.parent)) || (r = ws.upload(&d_pbranch, P.pbranch)) || (r = ws.upload(&d_child_ptr, P.child_ptr)) ||
-        (r = ws.upload(&d_child, P.child)) || (r = ws.upload(&d_inc_ptr, P.inc_ptr)) || (r = ws.upload(&d_inc, P.inc)) ||
-        (r = ws.upload(&d_nodes, P.dep_nodes)) || (r = ws.upload(&d_R, net->R, (size_t)nb)) || (r = ws.upload(&d_X, net->X, (size_t)nb)) ||
-        (r = ws.upload(&d_gsh, net->gsh, (size_t)n)) || (r = ws.upload(&d_bsh, net->bsh, (size_t)n)) ||
-        (r = ws.upload(&d_xsh, net->xsh, (size_t)n)) || (r = ws.upload(&d_h, h, (size_t)F)) || (r = ws.alloc(&d_w, nF)) ||
-        (r = ws.alloc(&d_t, nF)) || (r = ws.alloc(&d_x, nF)) || (r = ws.alloc(&d_y, nF)) || (r = ws.alloc(&d_pkey, tF)) ||
+    if ((r = Y.upload(ws, Fc, y_extra != nullptr, false)) || (r = ws.alloc(&d_x, nF)) || (r = ws.alloc(&d_y, nF)) || (r = ws.alloc(&d_pkey, tF)) ||
         (r = ws.alloc(&d_parg, tF)) || (r = ws.alloc(&d_part, 3 * tF)) || (r = ws.alloc(&d_sums, (size_t)3 * Fc)) ||
         (r = ws.alloc(&d_piv, (size_t)Fc)) || (r = ws.alloc(&d_yp, (size_t)Fc)) || (r = ws.alloc(&d_lam, (size_t)Fc)) ||
         (r = ws.alloc(&d_zr, (size_t)Fc)) || (r = ws.alloc(&d_ginv, (size_t)Fc)) || (r = ws.alloc(&d_bad, (size_t)1)))
-        return done(r);
-    if (y_extra && (r = ws.alloc(&d_yx, nF))) return done(r);
-    if (pf && (r = ws.alloc(&d_pf, nF))) return done(r);
-    if ((y_extra || pf) && (r = ws.alloc(&d_stage, nF))) return done(r);
-    if (k && ((r = ws.upload(&d_colbus, colbus)) || (r = ws.upload(&d_path, path)) || (r = ws.alloc(&d_cols, (size_t)ncol * nF)) ||
-              (r = ws.alloc(&d_Zd, nF)) || (r = ws.upload(&d_ta, ta)) || (r = ws.upload(&d_tb, tb)) || (r = ws.upload(&d_tR, tR)) ||
-              (r = ws.upload(&d_tX, tX)) || (r = ws.alloc(&d_Winv, (size_t)k * k * Fc)) || (r = ws.alloc(&d_coef, (size_t)k * Fc))))
-        return done(r);
+        return zs_done(ws, r);
+    if (pf && (r = ws.alloc(&d_pf, nF))) return zs_done(ws, r);
+    if ((y_extra || pf) && (r = ws.alloc(&d_stage, nF))) return zs_done(ws, r);
+    if (k && (r = ws.alloc(&d_coef, (size_t)k * Fc))) return zs_done(ws, r);
 
-    const ZscanView Vw{n, d_parent, d_pbranch, d_child_ptr, d_child, d_inc_ptr, d_inc, d_R, d_X, d_gsh, d_bsh, d_xsh};
     const hipStream_t st = nullptr;
-    auto transpose = [&](const cplx* in, long long R, long long C, cplx* out) {
-        const long long t2 = ((R + ZS_TILE - 1) / ZS_TILE) * ((C + ZS_TILE - 1) / ZS_TILE);
-        hipLaunchKernelGGL(k_zscan_transpose, dim3((unsigned)t2), dim3(ZS_TILE * 8), 0, st, in, R, C, out);
-    };
     std::vector<cplx> hl((size_t)Fc), hz((size_t)Fc);
-    if (hipMemsetAsync(d_bad, 0, sizeof(int), st) != hipSuccess) return done(HPF_E_HIP);
+    if (hipMemsetAsync(d_bad, 0, sizeof(int), st) != hipSuccess) return zs_done(ws, HPF_E_HIP);
     for (int f0 = 0; f0 < F; f0 += Fc) {
         const int fc = std::min(Fc, F - f0);             // (the arrays of a short last chunk are [bus][fc])
-        const double* hh = d_h + f0;
         const dim3 g_n(zs_grid(n, fc)), g_t(zs_grid(tiles, fc)), g_1(zs_grid(1, fc)), tpb(ZS_TPB);
-        // the factor of the chunk's points: the scan's kernels
-        if (y_extra) {
-            if (hipMemcpy(d_stage, y_extra + (size_t)2 * f0 * n, sizeof(cplx) * (size_t)fc * n, hipMemcpyHostToDevice) != hipSuccess)
-                return done(HPF_E_HIP);
-            transpose(d_stage, fc, n, d_yx);
-        }
-        for (int d = P.n_depths - 1; d >= 0; --d) {
-            const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
-            hipLaunchKernelGGL(k_zscan_up, dim3(zs_grid(m, fc)), tpb, 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, hh, d_yx, d_w, d_t);
-        }
-        if (k) {
-            for (int d = 0; d < P.n_depths; ++d) {
-                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
-                hipLaunchKernelGGL(k_zscan_down, dim3(zs_grid(m, fc)), tpb, 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, d_w, d_t, d_Zd);
-            }
-            hipLaunchKernelGGL(k_zscan_col_walk, dim3(zs_grid(ncol, fc)), tpb, 0, st, Vw, d_colbus, ncol, fc, d_t, d_Zd, d_cols);
-            for (int d = 1; d < P.n_depths; ++d) {
-                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
-                hipLaunchKernelGGL(k_zscan_col_fill, dim3(zs_grid(m, fc), ncol), tpb, 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, d_path, d_t, d_cols);
-            }
-            hipLaunchKernelGGL(k_zscan_tie_winv, g_1, tpb, 0, st, k, d_ta, d_tb, d_tR, d_tX, n, fc, hh, d_cols, d_Winv);
-        }
-        // inverse iteration: y = Y^-1 x by the penetration's walks with one scenario, the pivot, the scaling
+        if ((r = Y.factor(st, f0, fc, y_extra, d_stage))) return zs_done(ws, r);
+        // inverse iteration: y = Y^-1 x with one scenario (in place), the pivot, the scaling
         hipLaunchKernelGGL(k_rma_start, g_n, tpb, 0, st, n, fc, d_x, d_y);
         for (int it = 1; it <= iters; ++it) {
-            for (int d = P.n_depths - 2; d >= 0; --d) {      // (the deepest depth holds leaves only)
-                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
-                hipLaunchKernelGGL(k_pen_up, dim3(zs_grid(m, fc)), tpb, 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, 1, d_t, d_y);
-            }
-            for (int d = 0; d < P.n_depths; ++d) {
-                const int m = P.dep_ptr[d + 1] - P.dep_ptr[d];
-                hipLaunchKernelGGL(k_pen_down, dim3(zs_grid(m, fc)), tpb, 0, st, Vw, d_nodes + P.dep_ptr[d], m, fc, 1, d_w, d_t, d_y);
-            }
-            if (k) {
-                hipLaunchKernelGGL(k_pen_tie_coef, g_1, tpb, 0, st, k, d_ta, d_tb, fc, 1, d_Winv, d_y, d_coef);
-                hipLaunchKernelGGL(k_pen_tie_fix, g_n, tpb, 0, st, k, n, fc, 1, d_cols, d_coef, d_y);
-            }
+            Y.solve(st, fc, 1, d_y, d_coef);
             hipLaunchKernelGGL(k_rma_pivot<0>, g_t, tpb, 0, st, n, fc, d_y, d_pkey, d_parg, d_piv, d_yp);
             hipLaunchKernelGGL(k_rma_pivot<1>, g_1, tpb, 0, st, n, fc, d_y, d_pkey, d_parg, d_piv, d_yp);
             if (it < iters) hipLaunchKernelGGL(k_rma_scale, g_n, tpb, 0, st, n, fc, d_yp, d_x, d_y);
@@ -833,21 +765,21 @@ extern "C" int hpf_resonance_modes(int device, const hpf_zscan_net* net, int F, 
         hipLaunchKernelGGL(k_rma_finish<1>, g_t, tpb, 0, st, n, fc, d_x, d_y, d_sums, d_yp, d_lam, d_zr, d_ginv, d_pf, d_pkey, d_parg, d_bad);
         hipLaunchKernelGGL(k_rma_finish<2>, g_1, tpb, 0, st, n, fc, d_x, d_y, d_sums, d_yp, d_lam, d_zr, d_ginv, d_pf, d_pkey, d_parg, d_bad);
         if (pf) {
-            transpose(d_pf, n, fc, d_stage);
-            if (hipMemcpy(pf + (size_t)2 * f0 * n, d_stage, sizeof(cplx) * (size_t)fc * n, hipMemcpyDeviceToHost) != hipSuccess) return done(HPF_E_HIP);
+            zs_transpose(st, d_pf, n, fc, d_stage);
+            if (hipMemcpy(pf + (size_t)2 * f0 * n, d_stage, sizeof(cplx) * (size_t)fc * n, hipMemcpyDeviceToHost) != hipSuccess) return zs_done(ws, HPF_E_HIP);
         }
         if (hipMemcpy(hl.data(), d_lam, sizeof(cplx) * fc, hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(hz.data(), d_zr, sizeof(cplx) * fc, hipMemcpyDeviceToHost) != hipSuccess ||
             (top && hipMemcpy(top + f0, d_piv, sizeof(int) * fc, hipMemcpyDeviceToHost) != hipSuccess))
-            return done(HPF_E_HIP);
+            return zs_done(ws, HPF_E_HIP);
         for (int f = 0; f < fc; ++f) {
             if (lam) lam[2 * (size_t)(f0 + f)] = hl[f].re, lam[2 * (size_t)(f0 + f) + 1] = hl[f].im;
             if (zm) zm[f0 + f] = hz[f].re;
             if (res) res[f0 + f] = hz[f].im;
         }
-        if (hipGetLastError() != hipSuccess) return done(HPF_E_HIP);
+        if (hipGetLastError() != hipSuccess) return zs_done(ws, HPF_E_HIP);
     }
     int bad = 0;
-    if (hipMemcpy(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return done(HPF_E_HIP);
-    return done(bad ? HPF_E_SINGULAR : HPF_OK);
+    if (hipMemcpy(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return zs_done(ws, HPF_E_HIP);
+    return zs_done(ws, bad ? HPF_E_SINGULAR : HPF_OK);
 }

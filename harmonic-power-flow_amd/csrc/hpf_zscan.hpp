@@ -127,6 +127,42 @@ inline void zscan_mark_path(const ZscanPlan& P, int j, unsigned char* mark) {
     for (int a = j; a >= 0; a = P.parent[a]) mark[a] = 1;
 }
 
+// the ties and the columns of one call, as the host hands them to the kernels and to the emulation: the columns of the n_sel selected buses first
+// (the scan's: they leave as Zt), then col(a_l), col(b_l) of every tie l < k
+struct ZscanTies {
+    int k = 0, n_sel = 0, ncol = 0;          // ncol = n_sel + 2 k
+    std::vector<int> colbus;                 // [ncol]
+    std::vector<int> ta, tb;                 // [k] the ties' end buses
+    std::vector<double> tR, tX;              // [k] ... and series impedance
+    std::vector<unsigned char> path;         // [ncol][n] 1 on the column bus and its ancestors
+};
+
+inline ZscanTies zscan_ties(const ZscanPlan& P, const int32_t* from, const int32_t* to, const double* R, const double* X, int n_sel = 0,
+                            const int32_t* sel = nullptr) {
+    ZscanTies T;
+    T.k = (int)P.tie.size(), T.n_sel = n_sel, T.ncol = n_sel + 2 * T.k;
+    T.colbus.assign(sel, sel + n_sel);
+    for (int e : P.tie) {
+        T.ta.push_back(from[e]), T.tb.push_back(to[e]);
+        T.tR.push_back(R[e]), T.tX.push_back(X[e]);
+        T.colbus.push_back(from[e]);
+        T.colbus.push_back(to[e]);
+    }
+    T.path.assign((size_t)T.ncol * P.n, 0);
+    for (int s = 0; s < T.ncol; ++s) zscan_mark_path(P, T.colbus[s], T.path.data() + (size_t)s * P.n);
+    return T;
+}
+
+// the scan's scratch per frequency point, in complex values: w, t, Zd | y_extra | the columns | W^-1 | the staging buffer of the transposed copies
+// (stage_rows: y_extra in and Z out take n, the selected columns out n_sel n)
+inline size_t zscan_stage_rows(int n, int n_sel, bool has_x, bool want_Z) {
+    const size_t a = (want_Z || has_x) ? n : 0, b = (size_t)n_sel * n;
+    return a > b ? a : b;
+}
+inline size_t zscan_per_f(int n, int k, int n_sel, bool has_x, bool want_Z) {
+    return (size_t)3 * n + (has_x ? n : 0) + (size_t)(n_sel + 2 * k) * n + (size_t)k * k + zscan_stage_rows(n, n_sel, has_x, want_Z);
+}
+
 // chunk length for a grid of F points: the forced one, or the automatic one from the scratch budget.  cplx_per_f = complex values of scratch per
 // frequency point
 inline int zscan_chunk(int F, int chunk, size_t cplx_per_f) {

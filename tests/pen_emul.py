@@ -11,7 +11,7 @@ import zscan_ref as ref
 
 SRC = os.path.join(ze.HERE, "cpu_emul", "pen_emul.cpp")
 LIB = os.path.join(ze.HERE, "cpu_emul", "libhpf_pen_emul.so")
-HDRS = ze.HDRS + [os.path.join(ze.CSRC, "hpf_penetration.hpp")]
+HDRS = ze.HDRS                                              # (hpf_penetration.hpp and zfactor_emul.hpp are among them)
 OUTPUTS = ("V", "rss", "vmax", "varg", "vsum", "vsumsq", "rss_max", "rss_arg", "rss_sum", "rss_sumsq")
 
 

@@ -12,7 +12,7 @@ import zscan_ref as ref
 
 SRC = os.path.join(ze.HERE, "cpu_emul", "rma_emul.cpp")
 LIB = os.path.join(ze.HERE, "cpu_emul", "libhpf_rma_emul.so")
-HDRS = ze.HDRS + [os.path.join(ze.CSRC, f) for f in ("hpf_penetration.hpp", "hpf_resonance.hpp")]
+HDRS = ze.HDRS + [os.path.join(ze.CSRC, "hpf_resonance.hpp")]
 OUTPUTS = ("lam", "zm", "res", "top", "pf")
 GRID = np.linspace(0.5, 50.5, 130)
 BANKS = {"syn12": {5: 0.002, 9: 0.02}, "syn40": {17: 0.01, 33: 0.004}}

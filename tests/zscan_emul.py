@@ -11,7 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "cpu_emul", "zscan_emul.cpp")
 LIB = os.path.join(HERE, "cpu_emul", "libhpf_zscan_emul.so")
 CSRC = os.path.join(os.path.dirname(HERE), "harmonic-power-flow_amd", "csrc")
-HDRS = [os.path.join(CSRC, f) for f in ("hpf_zscan.hpp", "hpf_waveform.hpp", "hpf_distortion.hpp", "hpf_assembly.hpp")]
+HDRS = [os.path.join(CSRC, f) for f in ("hpf_zscan.hpp", "hpf_penetration.hpp", "hpf_waveform.hpp", "hpf_distortion.hpp", "hpf_assembly.hpp")] + \
+    [os.path.join(HERE, "cpu_emul", "zfactor_emul.hpp")]     # (the factor and the solve the three emulations share)
 INPUTS = os.path.join(HERE, "golden", "inputs")
 
 

@@ -12,10 +12,13 @@ import subprocess
 import sys
 import tempfile
 
-REPO = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REPO = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else HERE
 CSRC = os.path.join(REPO, "harmonic-power-flow_amd", "csrc")
-SOURCES = ["hpf_lib.hip", "hpf_block.hip", "hpf_csr_solve.hip"]
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-Wno-unused-value", "-fPIC"] + os.environ.get("HPF_CFLAGS", "").split()
+sys.path.insert(0, os.path.join(HERE, "harmonic-power-flow_amd"))
+import build                                                # noqa: E402  (this tree's list of translation units and flags, for either root)
+SOURCES = build.SOURCES
+FLAGS = build.FLAGS + os.environ.get("HPF_CFLAGS", "").split()
 
 
 def functions(asm):
